@@ -15,9 +15,12 @@ N > 1: one process per GPU; `python bench.py --gpus N` without a launcher re-exe
 torch.distributed.run (127.0.0.1 rendezvous).  Clips are sharded across ranks, no data-path collective ("replicas
 only", weak scaling); RCCL carries the barriers and the max-over-ranks of the timing only.
 
-Prints ONE JSON line on rank 0 with the contract fields plus `roofline` (dominant kernel family; every kernel of one
-serialized step timed live with HIP events on the launch stream), `cpu_baseline` (the CPU oracle, a port of the
-reference, timed on this host on a bounded sample) and `pcie_inclusive`.
+Prints ONE JSON line on rank 0 with the contract fields.  A plain run does only what that line needs: set-up, warm-up, the
+timed steps and, with `--dump-outputs DIR`, the last timed step's results (poses, expressions, trans) as DIR/<name>.npy.
+`--full` adds everything else the benchmark measures: `pcie_inclusive`, `roofline` (dominant kernel family; every kernel
+of one serialized step timed live with HIP events on the launch stream), `code_agreement`, `other_precisions`,
+`cpu_baseline` (the CPU oracle, a port of the reference, timed on this host on a bounded sample), `config1`,
+`batch_sweep`, `lstm_models` and `train_step`.
 """
 import argparse
 import json
@@ -127,6 +130,22 @@ def timed_pipeline(pipe, audio, steps, warmup, barrier, reduce_max):
     out = rest[-1] if rest else out
     barrier()
     return reduce_max(time.perf_counter() - t0), out
+
+
+OUTPUT_NAMES = ("poses", "expressions", "trans")       # what ClipRunner.__call__ hands its caller, in its order
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(directory, outputs):
+    """Write the arrays of the last timed step as DIR/<name>.npy (float32), for output-for-output comparison of two builds.  A batch
+    whose arrays exceed 64 MB in all is cut to its first clips (the same clips in every run with the same arguments)."""
+    arrays = [np.asarray(a, dtype=np.float32) for a in outputs]
+    per_clip = sum(a[:1].nbytes for a in arrays)
+    clips = min(len(arrays[0]), DUMP_BUDGET_BYTES // per_clip)
+    os.makedirs(directory, exist_ok=True)
+    for name, a in zip(OUTPUT_NAMES, arrays):
+        np.save(os.path.join(directory, name + ".npy"), np.ascontiguousarray(a[:clips]))
+    log(f"outputs of the last timed step ({clips} of {len(arrays[0])} clips) written to {directory}")
 
 
 def result_line(precision, elapsed, steps, warmup, world, frames_per_step, batch, frames_in, launch):
@@ -871,6 +890,10 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true", help="also run every measurement beyond the headline line (PCIe-inclusive rate, roofline, "
+                                                        "code agreement, other precisions, CPU baselines, config 1, batch sweep, DisCo / CaMN, "
+                                                        "training step); the --no-* switches below trim it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's results (rank 0) as DIR/<name>.npy, float32")
     ap.add_argument("--batch", type=int, default=64, help="clips per GPU per step (BASELINE config 2: 64)")
     ap.add_argument("--frames", type=int, default=128)
     ap.add_argument("--precision", default="f16x3", choices=["f16x3", "bf16", "fp32"],
@@ -903,6 +926,8 @@ def main():
     ap.add_argument("--train-timeout", type=float, default=480.0, help="watchdog of the N-rank training-step leg (seconds)")
     ap.add_argument("--train-batch", type=int, default=56, help="clips per GPU of the training-step leg at N > 1 ranks (BASELINE configs[2]: 56)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # no launcher: become one — one process per GPU, the driver's own torchrun recipe
@@ -956,19 +981,22 @@ def main():
     frames_per_step = poses.shape[0] * poses.shape[1]
     assert np.isfinite(poses).all()
     log(f"timed: {1e3 * elapsed / args.steps:.2f} ms/step")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out)
     result = result_line(args.precision, elapsed, args.steps, args.warmup, world, frames_per_step, args.batch, args.frames,
                          "eager" if args.no_graph else "hipGraph replay")
 
-    # the same step with the audio batch crossing PCIe inside the timed region (pinned host -> HBM), SURVEY §8(d)
-    el_pcie, _ = timed_steps(lambda: runner(audio_host), args.steps, 1, barrier, reduce_max)
-    result["pcie_inclusive"] = {"value": frames_per_step * world * args.steps / el_pcie, "ms_per_step": 1e3 * el_pcie / args.steps,
-                                "h2d_bytes_per_step": audio_host.numel() * 4,
-                                "note": "SURVEY 8(d)'s definition of the metric (H2D of the audio inside the timed step: pinned host -> HBM in every step, "
-                                        "D2H of the three result arrays in both figures).  `value` above is the HBM-resident rate because the document that "
-                                        "fixes the bench contract says so — the round's task statement, section (4) Measurement: '`value` is whole-job throughput "
-                                        "with inputs already resident in HBM when the timed region starts (if the boundary hands over host buffers, note the "
-                                        "PCIe-inclusive rate in DESIGN.md - it is never `value`)' (quoted in DESIGN.md section 6); the figure that conforms to "
-                                        "SURVEY 8(d) is THIS object"}
+    if args.full:
+        # the same step with the audio batch crossing PCIe inside the timed region (pinned host -> HBM), SURVEY §8(d)
+        el_pcie, _ = timed_steps(lambda: runner(audio_host), args.steps, 1, barrier, reduce_max)
+        result["pcie_inclusive"] = {"value": frames_per_step * world * args.steps / el_pcie, "ms_per_step": 1e3 * el_pcie / args.steps,
+                                    "h2d_bytes_per_step": audio_host.numel() * 4,
+                                    "note": "SURVEY 8(d)'s definition of the metric (H2D of the audio inside the timed step: pinned host -> HBM in every step, "
+                                            "D2H of the three result arrays in both figures).  `value` above is the HBM-resident rate because the document that "
+                                            "fixes the bench contract says so — the round's task statement, section (4) Measurement: '`value` is whole-job throughput "
+                                            "with inputs already resident in HBM when the timed region starts (if the boundary hands over host buffers, note the "
+                                            "PCIe-inclusive rate in DESIGN.md - it is never `value`)' (quoted in DESIGN.md section 6); the figure that conforms to "
+                                            "SURVEY 8(d) is THIS object"}
 
     if args.pipeline > 1:
         from pantomatrix_amd.runtime import ClipPipeline
@@ -989,7 +1017,7 @@ def main():
             result[key] = {"error": f"{type(e).__name__}: {e}"[:500]}
             torch.cuda.empty_cache()
 
-    if rank == 0 and not args.no_roofline:
+    if args.full and rank == 0 and not args.no_roofline:
         def roofline():
             records, _marker_ms = profile_kernels(runner, model, vq)
             serial_ms = None if args.no_graph else serialized_graph_ms(model, vq, args, n_samples, audio, args.steps)
@@ -998,9 +1026,9 @@ def main():
                 rep.setdefault("vq_argmin", {})["n_1m"] = vq_argmin_large(dev)
             return rep
         guarded("roofline", roofline)
-    if rank == 0 and world == 1 and not args.no_roofline:
+    if args.full and rank == 0 and world == 1 and not args.no_roofline:
         guarded("code_agreement", lambda: code_agreement(model, vq, audio, args.batch))
-    if world == 1 and args.also:
+    if args.full and world == 1 and args.also:
         del runner, model, vq
         torch.cuda.empty_cache()
 
@@ -1028,7 +1056,7 @@ def main():
                 torch.cuda.empty_cache()
             return others
         guarded("other_precisions", other_precisions)
-    if (world > 1 and not args.no_other_configs) or (args.train and pdist.is_initialized()):
+    if (args.full and world > 1 and not args.no_other_configs) or (args.train and pdist.is_initialized()):
         # BASELINE configs[2] at N ranks: EVERY rank runs the captured 56-clip step with its RCCL collectives (and the same step without them)
         log(f"rank {rank}/{world}: the training step at {world} ranks (DDP bucket all-reduces + SyncBatchNorm inside the captured graph)")
         # Under a WATCHDOG: the leg holds collectives (eager warm-up steps, captured graphs); a rank that fails alone would leave the others in
@@ -1060,14 +1088,14 @@ def main():
             result["train_step"] = box["out"]
     if rank == 0:
         result["host"] = host_info()
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         guarded("cpu_baseline", lambda: cpu_baseline(args.frames))
-    if rank == 0 and world == 1 and not args.no_other_configs:
+    if args.full and rank == 0 and world == 1 and not args.no_other_configs:
         # BASELINE configs[0] on the device (one clip: 128 frames and 28 s) and the batch sweep
         log("config 1 (B = 1) and the batch sweep")
         guarded("config1", lambda: bench_config1(args.precision, dev, args, cpu=not args.no_cpu_baseline))
         guarded("batch_sweep", lambda: bench_batch_sweep(args.precision, dev, args))
-    if rank == 0 and world == 1 and not args.no_other_configs:
+    if args.full and rank == 0 and world == 1 and not args.no_other_configs:
         # BASELINE configs[2] / [3] / [4] beside the headline metric (bounded: a few steps each); models of the headline run are released
         torch.cuda.empty_cache()
         for key, what, fn in (("lstm_models", "DisCo / CaMN inference", bench_lstm_models), ("train_step", "one EMAGE training step", bench_train_step)):

@@ -23,12 +23,18 @@ def test_spawn_command_is_the_drivers_recipe():
 
 def test_gpus_flag_spawns_ranks_and_fails_loudly_without_gpus():
     """On this CPU box the spawned ranks must refuse to run (no CPU path) and the parent must report the failure:
-    `python bench.py --gpus 2` never silently benches one device."""
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0"],
+    `python bench.py --gpus 2` never silently benches one device.  On a box with GPUs the parent itself refuses one GPU more than
+    it sees, before it spawns anything."""
+    import torch
+    gpus = torch.cuda.device_count() + 1 if torch.cuda.is_available() else 2
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--steps", "1", "--warmup", "0"],
                        capture_output=True, text=True, timeout=600, env={**os.environ, "OMP_NUM_THREADS": "1"})
     assert r.returncode != 0
-    assert "re-executing as -m torch.distributed.run --nnodes=1 --nproc-per-node=2" in r.stderr
-    assert "needs an MI355X" in r.stderr          # raised inside the spawned ranks
+    if torch.cuda.is_available():
+        assert f"--gpus {gpus} but only {gpus - 1} GPU(s) visible" in r.stderr and "re-executing" not in r.stderr
+    else:
+        assert "re-executing as -m torch.distributed.run --nnodes=1 --nproc-per-node=2" in r.stderr
+        assert "needs an MI355X" in r.stderr      # raised inside the spawned ranks
     assert "motion-frames" not in r.stdout        # no bench line from a run that did not happen
 
 
@@ -118,7 +124,7 @@ def test_train_step_leg_on_two_gloo_ranks():
 
 
 def test_main_prints_one_json_line_and_reports_a_failing_extra(monkeypatch, capsys):
-    """bench.main() end to end with the device work stubbed out (a stand-in runner, stand-in profiling): ONE JSON line with the
+    """bench.main(--full) end to end with the device work stubbed out (a stand-in runner, stand-in profiling): ONE JSON line with the
     contract's keys and every additional object; an exception inside an additional object (here: the training-step line) is reported
     in that object's place and does not cost the headline line."""
     import json
@@ -144,7 +150,7 @@ def test_main_prints_one_json_line_and_reports_a_failing_extra(monkeypatch, caps
     def failing_train_step(dev, cpu=True):
         raise RuntimeError("out of memory (stand-in)")
 
-    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "2", "--warmup", "1"])
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "2", "--warmup", "1", "--full"])
     monkeypatch.setattr(torch.cuda, "is_available", lambda: True)
     monkeypatch.setattr(torch.cuda, "set_device", lambda d: None)
     monkeypatch.setattr(torch.cuda, "synchronize", lambda *a, **k: None)
@@ -176,3 +182,73 @@ def test_main_prints_one_json_line_and_reports_a_failing_extra(monkeypatch, caps
     assert d["lstm_models"]["camn"]["ms_per_step"] == 72.0 and d["config1"]["b1_28s"]["ms"] == 25.0 and set(d["batch_sweep"]["by_batch"]) == {"1", "8", "64", "256"}
     assert d["host"]["usable_cores"] >= 1
     assert d["train_step"] == {"error": "RuntimeError: out of memory (stand-in)"}
+
+
+def test_plain_run_times_exactly_the_steps_and_dumps_the_last_outputs(monkeypatch, capsys, tmp_path):
+    """A plain bench.main() (no --full): `--steps` timed steps after `--warmup` ones, the contract's keys and nothing measured beside
+    them, and with --dump-outputs the last timed step's arrays as float32 .npy files."""
+    import json
+    import numpy as np
+    import torch
+    import bench
+    from pantomatrix_amd import dist as pd
+    from pantomatrix_amd import synthetic
+
+    class _Audio:
+        def pin_memory(self):
+            return self
+
+        def to(self, dev):
+            return self
+
+    calls = []
+
+    def runner(a=None):
+        calls.append(1)
+        k = float(len(calls))
+        return np.full((64, 120, 165), k, np.float32), np.full((64, 120, 100), -k, np.float32), np.full((64, 120, 3), 2 * k, np.float64)
+
+    def must_not_run(*a, **k):
+        raise AssertionError("a plain run measures the headline only")
+
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "7", "--warmup", "2", "--dump-outputs", str(tmp_path / "out")])
+    monkeypatch.setattr(torch.cuda, "is_available", lambda: True)
+    monkeypatch.setattr(torch.cuda, "set_device", lambda d: None)
+    monkeypatch.setattr(torch.cuda, "synchronize", lambda *a, **k: None)
+    monkeypatch.setattr(synthetic, "synthetic_audio", lambda *a, **k: _Audio())
+    monkeypatch.setattr(pd, "init", lambda backend, dev=None: None)
+    monkeypatch.setattr(bench, "build", lambda precision, dev, args: (object(), object(), runner, 68267))
+    for name in ("profile_kernels", "serialized_graph_ms", "roofline_report", "vq_argmin_large", "code_agreement", "cpu_baseline",
+                 "bench_lstm_models", "bench_train_step", "bench_train_step_ranks", "bench_config1", "bench_batch_sweep"):
+        monkeypatch.setattr(bench, name, must_not_run)
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE"):
+        monkeypatch.delenv(k, raising=False)
+    bench.main()
+    assert len(calls) == 9
+    lines = [ln for ln in capsys.readouterr().out.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert key in d, key
+    assert d["steps"] == 7 and d["warmup"] == 2 and d["higher_is_better"] is True and d["dtype"] == "f16x3"
+    assert abs(d["value"] - 64 * 120 * 7 / (7 * d["ms_per_step"] * 1e-3)) < 1e-6 * d["value"]
+    for key in ("roofline", "cpu_baseline", "pcie_inclusive", "other_precisions", "code_agreement", "lstm_models", "train_step", "config1", "batch_sweep"):
+        assert key not in d, key
+    out = {n: np.load(tmp_path / "out" / f"{n}.npy") for n in ("poses", "expressions", "trans")}
+    assert out["poses"].shape == (64, 120, 165) and out["expressions"].shape == (64, 120, 100) and out["trans"].shape == (64, 120, 3)
+    assert all(a.dtype == np.float32 for a in out.values())
+    assert (out["poses"] == 9).all() and (out["expressions"] == -9).all() and (out["trans"] == 18).all()     # the last timed step's
+
+
+def test_dump_outputs_keeps_the_first_clips_within_64_mb(tmp_path):
+    import numpy as np
+    import bench
+    clip = np.arange(1024, dtype=np.float32).reshape(1024, 1, 1)         # every clip carries its own index
+    big = (clip + np.zeros((1024, 120, 165), np.float32), -clip + np.zeros((1024, 120, 100), np.float32), 2 * clip + np.zeros((1024, 120, 3), np.float32))
+    bench.dump_outputs(str(tmp_path), big)
+    kept = (64 << 20) // (120 * (165 + 100 + 3) * 4)
+    out = {n: np.load(tmp_path / f"{n}.npy") for n in bench.OUTPUT_NAMES}
+    assert sum(a.nbytes for a in out.values()) <= 64 << 20
+    assert out["poses"].shape == (kept, 120, 165) and out["expressions"].shape == (kept, 120, 100) and out["trans"].shape == (kept, 120, 3)
+    first = np.arange(kept, dtype=np.float32).reshape(kept, 1, 1)
+    assert (out["poses"] == first).all() and (out["expressions"] == -first).all() and (out["trans"] == 2 * first).all()

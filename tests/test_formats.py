@@ -1,7 +1,6 @@
 """On-disk formats either side of the path: BEAT2 npz schema (reference emage_utils/motion_io.py) and WAV input."""
 import os
 import struct
-import sys
 
 import numpy as np
 import pytest
@@ -39,31 +38,34 @@ def test_mask_select_recover_and_upsample():
     assert np.array_equal(mio.time_upsample_numpy(x, 1), x)
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/emage_utils"), reason="reference tree not present")
-def test_formats_match_reference(tmp_path):
-    """Same arrays through the reference's numpy helpers (imported read-only; its module imports `smplx`, stubbed)."""
-    import types
-    sys.modules.setdefault("smplx", types.ModuleType("smplx"))
-    sys.path.insert(0, "/root/reference")
-    try:
-        from emage_utils import motion_io as ref
-    finally:
-        sys.path.remove("/root/reference")
+MASKS = ("local_upper", "local_full")
+SAVED_ARRAYS = ("betas", "poses", "expressions", "trans")
+
+
+def reference_inputs():
     rng = np.random.default_rng(2)
     x = rng.standard_normal((9, 165)).astype(np.float32)
-    for name in ("local_upper", "local_full"):
-        assert mio.MASK_DICT[name] == ref.MASK_DICT[name]
-        assert np.array_equal(mio.select_with_mask(x, mio.MASK_DICT[name]), ref.select_with_mask(x, ref.MASK_DICT[name]))
-        s = ref.select_with_mask(x, ref.MASK_DICT[name])
-        assert np.array_equal(mio.recover_from_mask(s, mio.MASK_DICT[name]), ref.recover_from_mask(s, ref.MASK_DICT[name]))
-    assert np.allclose(mio.time_upsample_numpy(x, 3), ref.time_upsample_numpy(x, 3), atol=1e-6)
     e, t = rng.standard_normal((9, 100)).astype(np.float32), rng.standard_normal((9, 3)).astype(np.float32)
+    return x, e, t
+
+
+def test_formats_match_reference(tmp_path, golden_dir):
+    """Same arrays as the reference's numpy helpers produce on the same inputs (tests/golden/make_golden_reference.py recorded them in
+    reference_formats.npz)."""
+    ref = np.load(os.path.join(golden_dir, "reference_formats.npz"))
+    x, e, t = reference_inputs()
+    for name in MASKS:
+        assert mio.MASK_DICT[name] == [bool(v) for v in ref[f"fmt_mask_{name}"]]
+        assert np.array_equal(mio.select_with_mask(x, mio.MASK_DICT[name]), ref[f"fmt_select_{name}"])
+        s = ref[f"fmt_select_{name}"]
+        assert np.array_equal(mio.recover_from_mask(s, mio.MASK_DICT[name]), ref[f"fmt_recover_{name}"])
+    assert np.allclose(mio.time_upsample_numpy(x, 3), ref["fmt_upsample3"], atol=1e-6)
     mio.beat_format_save(str(tmp_path / "a.npz"), x, expressions=e, trans=t, upsample=2)
-    ref.beat_format_save(str(tmp_path / "b.npz"), x, expressions=e, trans=t, upsample=2)
-    a, b = np.load(tmp_path / "a.npz", allow_pickle=True), np.load(tmp_path / "b.npz", allow_pickle=True)
-    assert set(a.files) == set(b.files)
-    for k in ("betas", "poses", "expressions", "trans"):
-        assert a[k].shape == b[k].shape and np.allclose(a[k], b[k], atol=1e-6)
+    a = np.load(tmp_path / "a.npz", allow_pickle=True)
+    assert set(a.files) == {str(f) for f in ref["fmt_save_files"]}
+    for k in SAVED_ARRAYS:
+        b = ref[f"fmt_save_{k}"]
+        assert a[k].shape == b.shape and np.allclose(a[k], b, atol=1e-6)
 
 
 def test_wav_reader(tmp_path):

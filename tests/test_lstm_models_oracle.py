@@ -1,5 +1,5 @@
-"""DisCo / CaMN inference oracle (oracle/lstm_models_oracle.py) against the reference modules run
-live in the build container and against the golden fixture generated from them.  CPU only."""
+"""DisCo / CaMN inference oracle (oracle/lstm_models_oracle.py) against the reference modules' outputs
+and against the golden fixture generated from them.  CPU only."""
 import os
 
 import numpy as np
@@ -7,7 +7,6 @@ import pytest
 import torch
 
 from oracle import lstm_models_oracle as lo
-from oracle import reference_harness as rh
 from pantomatrix_amd import synthetic
 
 CFG = dict(lo.DEFAULT_CFG)
@@ -45,15 +44,27 @@ def test_lstm_direction_matches_torch():
     assert torch.allclose(got, want, atol=1e-6)
 
 
-@pytest.mark.skipif(not rh.available(), reason="needs /root/reference (build container only)")
+def case_tag(with_seed_motion):
+    return "seeded" if with_seed_motion else "plain"
+
+
 @pytest.mark.parametrize("kind", ["disco", "camn"])
 @pytest.mark.parametrize("with_seed_motion", [False, True])
-def test_matches_reference_live(kind, with_seed_motion):
+def test_matches_reference_live(golden_dir, kind, with_seed_motion):
+    """Every output of the reference module on the same weights and inputs (recorded by tests/golden/make_golden_reference.py, which
+    loads the weights strictly: the spec IS the reference's key / shape set).  The motion outputs are those of lstm_models.npz."""
+    g = np.load(os.path.join(golden_dir, "reference_lstm.npz"))
+    m = np.load(os.path.join(golden_dir, "lstm_models.npz"))
     sd = weights(kind)
-    model = rh.build_reference_lstm_model(kind, CFG, sd)         # strict load: the spec IS the reference's key / shape set
+    assert [str(k) for k in g[f"lstm_{kind}_keys"]] == list(sd)
+    assert [str(s) for s in g[f"lstm_{kind}_shapes"]] == [",".join(str(d) for d in v.shape) for v in sd.values()]
     audio, spk, motion = inputs(with_seed_motion=with_seed_motion)
-    with torch.no_grad():
-        ref = model(audio, spk, seed_frames=CFG["seed_frames"], seed_motion=motion)
+    tag = case_tag(with_seed_motion)
+    motion_outputs = {"motion": torch.from_numpy(m[f"{kind}_{tag}_motion"]).reshape(tuple(g[f"lstm_{kind}_motion_shape"])),
+                      "motion_axis_angle": torch.from_numpy(m[f"{kind}_{tag}_axis_angle"])}
+    ref = {str(k): motion_outputs[str(k)] if str(k) in motion_outputs else torch.from_numpy(g[f"lstm_{kind}_{k}"])
+           for k in g[f"lstm_{kind}_outputs"]}
+    assert set(motion_outputs) <= set(ref)
     got = run_oracle(kind, sd, audio, spk, motion)
     for k, v in ref.items():
         assert got[k].shape == v.shape, (k, got[k].shape, v.shape)

@@ -1,12 +1,16 @@
 """Host logic of the train-mode forward (pantomatrix_amd/training.py) on CPU stand-ins of the kernels: the order in which the
 dropout masks are consumed, the BatchNorm bookkeeping, the un-folded WavEncoder — against oracle/emage_train_oracle.py, which
 is pinned to the reference's training step (tests/test_train_oracle.py)."""
+import contextlib
+
 import pytest
 import torch
+import torch.nn.functional as F
 
 import common
 import fake_ops
 import train_common as tc
+from oracle import emage_oracle as orc
 from oracle import emage_train_oracle as tro
 from pantomatrix_amd import training
 
@@ -91,8 +95,10 @@ def test_step_losses_host_logic(golden_dir):
     assert float((stats[key] - ref_stats[key]).abs().max()) < 1e-5
 
 
-def _oracle_grads(seed, use_audio=True):
-    """Autograd gradients of rec_loss + cls_loss of ONE train-mode forward of the oracle (same draws as oracle_forward(seed))."""
+def _oracle_grads(seed, use_audio=True, ffn=None):
+    """Autograd gradients of rec_loss + cls_loss of ONE train-mode forward of the oracle (same draws as oracle_forward(seed)).
+    ffn: a dict that receives, per feed-forward block name, (x, w, b, h, a) of every call — the linear1 input, weight, bias and
+    pre-activation, and the ReLU output with its gradient retained (what kink_allowance needs)."""
     from pantomatrix_amd import synthetic
     from pantomatrix_amd.configuration_emage_audio import EmageAudioConfig
     cfg = EmageAudioConfig(**common.cfg_dicts()[0])
@@ -107,7 +113,7 @@ def _oracle_grads(seed, use_audio=True):
     index = {q: torch.randint(0, 256, (2, motion.shape[1]), generator=g) for q in ("face", "upper", "hands", "lower")}
     masks = []
     torch.manual_seed(seed)
-    with tc.recorded_masks(masks):
+    with tc.recorded_masks(masks), _recorded_ffn(ffn):
         pred = tro.forward_train(work, audio, spk, motion, mask, use_audio=use_audio)
     loss = tro.rec_loss(pred, latent, cfg) + tro.cls_loss(pred, index, cfg)
     loss.backward()
@@ -115,15 +121,63 @@ def _oracle_grads(seed, use_audio=True):
     return (audio, spk, motion, mask), masks, index, latent, grads
 
 
+@contextlib.contextmanager
+def _recorded_ffn(ffn):
+    """tro._ffn_train with the same operations and draws, recording (x, w, b, h, a) per call into `ffn` (a no-op for ffn=None)."""
+    if ffn is None:
+        yield
+        return
+    saved = tro._ffn_train
+
+    def ffn_train(sd, name, x, p):
+        h = orc._linear(sd, name + ".linear1", x)
+        a = F.relu(h)
+        a.retain_grad()
+        ffn.setdefault(name, []).append((x.detach(), sd[name + ".linear1.weight"].detach(), sd[name + ".linear1.bias"].detach(),
+                                         h.detach(), a))
+        return orc._linear(sd, name + ".linear2", tro._drop(a, p))
+
+    tro._ffn_train = ffn_train
+    try:
+        yield
+    finally:
+        tro._ffn_train = saved
+
+
+KINK_ULPS = 4
+
+
+def kink_allowance(ffn):
+    """The ReLU kink of the feed-forward blocks: a sample whose linear1 pre-activation h lies within KINK_ULPS fp32 ulps of the scale
+    of its dot product (sum |x_k w_k| + |b|) can land on either side of 0 in two fp32 implementations that sum in different orders
+    (measured: one sample of one unit of one block, at 0.2 ulps, on one host CPU and not another).  Such a sample then contributes da * x to that unit's
+    row of linear1.weight and da to its bias in one backward and nothing in the other (da: the gradient at the ReLU output).
+    Returns {parameter name: per-entry allowance}, the sum of |da| |x| over the ambiguous samples of each unit — zero for every
+    unit without one, which is therefore held to the strict tolerance."""
+    eps = torch.finfo(torch.float32).eps
+    out = {}
+    for name, calls in ffn.items():
+        aw, ab = torch.zeros_like(calls[0][1]), torch.zeros_like(calls[0][2])
+        for x, w, b, h, a in calls:
+            x2, h2, da = x.reshape(-1, x.shape[-1]), h.reshape(-1, h.shape[-1]), a.grad.reshape(-1, a.shape[-1])
+            scale = x2.abs() @ w.abs().t() + b.abs()
+            amb = (h2.abs() <= KINK_ULPS * eps * scale).float()             # (samples, units)
+            aw += (amb * da.abs()).t() @ x2.abs()
+            ab += (amb * da.abs()).sum(0)
+        out[name + ".linear1.weight"], out[name + ".linear1.bias"] = aw, ab
+    return out
+
+
 FRONT_END = ("audio_encoder_face.", "audio_encoder_body.", "motion_encoder.", "mask_embedding")
 
 
-def compare_grads(grads, ref, rel=2e-4, to_cpu=False):
+def compare_grads(grads, ref, rel=2e-4, to_cpu=False, allowance=None):
     """Every parameter the oracle's autograd reaches: present, and equal to `rel` of its own scale (plus 2e-6 of the largest
     gradient: conv biases in front of a train-mode BatchNorm have a true gradient of 0 and carry fp32 noise).
     The WavEncoders get an L2 criterion instead: a LeakyReLU pre-activation within fp32 rounding of 0 takes the other slope in
     two fp32 implementations that round differently (measured: 1 of 159 000 activations of a block), which moves the affected
-    channel's gradient — and everything upstream of it — by a percent; torch's own fp32 and fp64 runs differ the same way."""
+    channel's gradient — and everything upstream of it — by a percent; torch's own fp32 and fp64 runs differ the same way.
+    allowance: {name: per-entry extra tolerance} for the feed-forward ReLU kink (kink_allowance)."""
     gmax = max(float(v.abs().max()) for v in ref.values())
     missing = [k for k in ref if k not in grads and float(ref[k].abs().max()) > 1e-6 * gmax]
     assert not missing, missing[:8]
@@ -136,9 +190,12 @@ def compare_grads(grads, ref, rel=2e-4, to_cpu=False):
         if k.startswith(("audio_encoder_face.", "audio_encoder_body.")):
             assert float((g - r).norm()) <= 5e-2 * float(r.norm()) + 2e-5 * gmax, (k, float((g - r).norm()), float(r.norm()))
             continue
-        err = float((g - r).abs().max())
+        lim = rel * float(r.abs().max()) + 2e-6 * gmax
+        extra = allowance[k] if allowance is not None and k in allowance else torch.zeros_like(r)
+        over = (g - r).abs() - extra
+        err = float(over.max())
         worst = max(worst, err / (float(r.abs().max()) + 1e-3 * gmax))
-        assert err <= rel * float(r.abs().max()) + 2e-6 * gmax, (k, err, float(r.abs().max()))
+        assert err <= lim, (k, err, float(r.abs().max()), int((extra > 0).any(dim=-1).sum()) if extra.dim() > 1 else int((extra > 0).sum()))
     assert not [k for k in grads if k not in ref and float(grads[k].abs().max()) > 1e-6 * gmax]
     return worst
 
@@ -159,14 +216,16 @@ def test_backward_host_logic(use_audio):
     training oracle: EVERY trainable parameter that takes part in the forward — the 16 transformer layers, projections, MLP
     heads, speaker embeddings, and the convolutional front ends (both WavEncoders with their train-mode BatchNorms, the motion
     pre-encoder, the mask embedding)."""
-    (audio, spk, motion, mask), masks, index, latent, ref = _oracle_grads(seed=4, use_audio=use_audio)
+    ffn = {}
+    (audio, spk, motion, mask), masks, index, latent, ref = _oracle_grads(seed=4, use_audio=use_audio, ffn=ffn)
     model, _ = common.product_models(precision="fp32")
     fwd = training.TrainForward(model)
     with fake_ops.installed(), torch.no_grad():
         fwd(audio, spk, motion, mask, masks, use_audio=use_audio, tape=True)
         grads = fwd.backward(index, latent)
     assert len(ref) > 400 and any(k.startswith("audio_encoder_face.") for k in grads) and "mask_embedding" in grads
-    compare_grads(grads, ref)
+    assert len(ffn) >= 16                                                 # every feed-forward block recorded
+    compare_grads(grads, ref, allowance=kink_allowance(ffn))
 
 
 def test_trainer_step_host_logic(golden_dir):

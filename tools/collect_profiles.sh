@@ -6,7 +6,7 @@ O=$R/gpurun_out/r01
 mkdir -p $O
 (timeout 900 python -m pytest tests -m gpu -q -p no:cacheprovider 2>&1 | tail -15) > $O/pytest_gpu.txt
 (timeout 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | grep -v amdgpu.ids | tail -3) > $O/smoke.txt
-(timeout 500 python bench.py --steps 20 --warmup 3) > $O/bench.json 2> $O/bench.err
+(timeout 500 python bench.py --steps 20 --warmup 3 --full) > $O/bench.json 2> $O/bench.err
 (timeout 200 python tools/bench_gemm.py --ablate --configs 25,20) 2>&1 | grep -v amdgpu.ids > $O/gemm_ablation.txt
 (timeout 200 python tools/bench_gemm.py --configs 0,10,11,13,19,20,25,26) 2>&1 | grep -v amdgpu.ids > $O/gemm_sweep.txt
 (timeout 100 python tools/bf16_agreement.py) 2>&1 | grep -v amdgpu.ids > $O/bf16_agreement.txt

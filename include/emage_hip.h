@@ -127,7 +127,8 @@ int emage_gather_rows(const float* table, const int64_t* idx, int idx_rows, long
  * EMAGE_H2:  A / out / (res_is_f32 = 0) res are pre-split images (csrc/h2.h: per 8 columns 32 bytes [8 fp16 hi | 8 fp16 lo] of 16 x),
  *        out_f32 / out_t float32; W is the same image of W * w_scale, rows K-contiguous.  res == out_f32 (fp32, ldr == ldf) accumulates:
  *        out_f32 += contraction (a weight gradient added straight into the parameter's gradient, loss.backward()'s accumulation T:174).
- *        A bare contraction (no bias / slope / out / out_t) with few tiles and K >= 2048 is cut into K-slices added with fp32 atomics.
+ *        A bare contraction (no bias / slope / out / out_t, no LayerNorm fold or st_out) with few tiles and K >= 2048 is cut into K-slices
+ *        added with fp32 atomics.
  */
 int emage_gemm(int dtype, const void* A, int lda, const void* W, const float* bias, const float* slope,
                const void* res, int ldr, int res_is_f32, int res_first,
@@ -180,7 +181,9 @@ typedef struct emage_gemm_problem {
      *   rs_stats (M, rs_np) pairs, rs_np * 32 == N: `res` (an EMAGE_H2 image, res_is_f32 = 0) is the raw sum s' of a folded LayerNorm,
      *       the residual added is (s' - mu) rstd rs_gamma[n] + rs_beta[n];
      *   st_out (M, N / 32) pairs: partial statistics of THIS launch's output rows (values as stored to out / out_f32); N % 64 == 0, no
-     *       out_t, launches that take the 64 x 64 tile (N < 1024) only. */
+     *       out_t, launches that take the 64 x 64 tile (N < 1024) only.
+     * A launch with any of these is never cut into K-slices by the atomic or the two-pass split-K (the epilogue of a slice sees partial
+     * sums only); the in-launch fix-up below runs its one epilogue on the summed tile. */
     const float* ln_stats; const float* ln_c; const float* rs_stats; const float* rs_gamma; const float* rs_beta; float* st_out;
     int ln_np, rs_np;
     float ln_eps;

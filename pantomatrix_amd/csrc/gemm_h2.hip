@@ -50,6 +50,13 @@ static inline long h2_split_k_tiles() { return (g_h2_variant & 1024) ? 384 : (g_
 static inline bool h2_accumulates_in_place(const GemmArgs& a) {
     return a.res && a.res_is_f32 && a.out_f32 && (const void*)a.res == (const void*)a.out_f32 && a.ldr == a.ldf;
 }
+// A "bare" contraction, the only kind split-K (atomic or two-pass) may cut into K-slices: only out_f32 (optionally accumulating in place),
+// no bias / activation / residual, no LayerNorm fold and no row statistics out — a slice's epilogue sees its partial sums only (the
+// weight gradients of a training step), and K >= 2048.
+static inline bool h2_bare(const GemmArgs& a) {
+    return a.taps == 1 && !a.out && !a.out_t && (!a.res || h2_accumulates_in_place(a)) && !a.bias && !a.slope && a.out_f32 &&
+           !a.ln_stats && !a.rs_stats && !a.st_out && a.K / 32 >= 64;
+}
 
 // second pass of a workspace split-K: out[m][n] (+)= plane_0[m][n] + plane_1[m][n] + ... in slice order — a fixed association, so the
 // result is the same bits on every run (the atomic form adds the slices in arrival order).  4 columns per thread.
@@ -111,7 +118,7 @@ int launch_h2(GemmArgs& a, hipStream_t s) {
     // res == out_f32 (fp32, same pitch): "out_f32 += contraction" — a weight gradient accumulated straight into the parameter's gradient.
     // One slice: the epilogue's residual add does it in place.  Split-K: the atomics land on the existing contents (no clearing, no residual)
     const bool accumulate = h2_accumulates_in_place(a);
-    const bool bare = a.taps == 1 && !a.out && !a.out_t && (!a.res || accumulate) && !a.bias && !a.slope && a.out_f32 && nk_all >= 64;
+    const bool bare = h2_bare(a);
     float* const ws = a.ws;
     const long ws_floats = a.ws_plane;                 // emage_gemm_ws: capacity of the workspace in floats (gemm.hip)
     a.ws = nullptr; a.ws_plane = 0; a.ldws = 0;
@@ -245,7 +252,7 @@ void h2_tiles(GemmArgs& a) {
 template <int BM, int BN>
 bool h2_wants_split_k(const GemmArgs& a) {
     const long tiles = (long)((a.M + BM - 1) / BM) * (((a.n_store > a.N ? a.n_store : a.N) + BN - 1) / BN);
-    return a.taps == 1 && !a.out && !a.out_t && (!a.res || h2_accumulates_in_place(a)) && !a.bias && !a.slope && a.out_f32 && tiles <= h2_split_k_tiles() && a.K / 32 >= 64;
+    return h2_bare(a) && tiles <= h2_split_k_tiles();
 }
 
 template <int BM, int BN, int WM, int WN, int NS, int NLW, bool PIPE, bool PRE = false, int OCC = 1, bool DILV = false, bool LNF = false>
@@ -446,12 +453,12 @@ int gemm_h2_dispatch(GemmArgs& a, hipStream_t s) {
     // Kept behind emage_set_tuning key 5 bit 524288 for A/B only
     if (cfg == 120 && g_h2_force_config < 0 && (g_h2_variant & 524288)) {
         const long t64 = (long)((a.M + 63) / 64) * ((((a.n_store > a.N ? a.n_store : a.N)) + 63) / 64);
-        const bool bare = a.taps == 1 && !a.out && !a.out_t && !a.bias && !a.slope && a.out_f32 && a.K / 32 >= 64;
+        const bool bare = h2_bare(a);
         if (t64 <= 256 && !bare) cfg = 188;
     }
     if (cfg == 120 && g_h2_force_config < 0 && ((g_h2_variant & 1048576) || g_h2_small_cfg > 0)) {       // tools A/B: lone-block grids on 8 waves / on any 64 x 64 configuration
         const long t64 = (long)((a.M + 63) / 64) * ((((a.n_store > a.N ? a.n_store : a.N)) + 63) / 64);
-        const bool bare = a.taps == 1 && !a.out && !a.out_t && !a.bias && !a.slope && a.out_f32 && a.K / 32 >= 64;
+        const bool bare = h2_bare(a);
         if (t64 <= 256 && !bare) cfg = g_h2_small_cfg > 0 ? g_h2_small_cfg : 189;
     }
 #endif

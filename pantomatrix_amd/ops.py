@@ -571,7 +571,8 @@ def gemm(dtype, a, w, bias=None, slope=None, res=None, out=None, out_f32=None, o
     lout = m if lout is None else lout
     if k_real is not None:
         _META["k_real"] = k_real
-    if workspace is not None:
+    fold = ln is not None or res_ln is not None or stats_out is not None
+    if workspace is not None and not fold:
         assert workspace.is_contiguous() and workspace.device == a.device
         _gemm_ws(dtype, a, w, bias, slope, res, out, out_f32, out_t, n, cp, n_store, t_col0, t_rows, bool(res_first), taps, stride, pad,
                  lin, lout, m, float(w_scale), float(act_scale(dtype) if a_scale is None else a_scale), bool(res_h2), workspace)
@@ -584,8 +585,9 @@ def gemm(dtype, a, w, bias=None, slope=None, res=None, out=None, out_f32=None, o
     # folded W gamma / W beta + b; res_ln = (row statistics of `res`, gamma, beta) — `res` is the raw sum of a folded LayerNorm; stats_out: the
     # (M, n / 32, 2) partial row statistics of this launch's output
     # splitk = (scratch (float32, contiguous), counters (int32, ZERO, left zero)): lets a launch of few rows cut its K range into slices that meet
-    # inside the launch (emage_gemm_problem: sk_ws / sk_count); launches on one stream may share the pair
-    assert dtype & 0xff == H2 and workspace is None
+    # inside the launch (emage_gemm_problem: sk_ws / sk_count); launches on one stream may share the pair.  `workspace` is not passed on: a
+    # folding launch never takes the two-pass split-K (gemm_h2.hip: h2_bare), and emage_gemm_ws has no fold fields
+    assert dtype & 0xff == H2
     ln_stats, ln_c = ln if ln is not None else (None, None)
     rs_stats, rs_gamma, rs_beta = res_ln if res_ln is not None else (None, None, None)
     sk_ws, sk_count = splitk if splitk is not None else (None, None)

@@ -836,6 +836,83 @@ def test_gemm_layernorm_fold(m):
             assert torch.equal(a_, b_), nm
 
 
+@pytest.mark.parametrize("k", [2048, 3584])
+@pytest.mark.parametrize("m", [64, 256])
+def test_gemm_stats_out_over_a_long_k(m, k):
+    """A bias-less contraction whose only outputs are out_f32 and its partial row statistics (st_out), over a K long enough (>= 2048) and
+    few enough tiles that a bare contraction is cut into K-slices.  A K-slice only holds partial sums, so its epilogue must not write row
+    statistics: such a launch is not split by the atomic form nor by the two-pass (workspace) form, while the in-launch fix-up (`splitk=`)
+    runs the ordinary epilogue once on the summed tile.  All three modes against float64: out_f32, the per-32-column {mean, M2}, and the
+    (mu, rstd) a consumer merges from them.  The same problem in a grouped call writes the same bits, in as many launches as the
+    library's grouping filter implies."""
+    n, eps = 768, 1e-5
+    g = _g(900 + m + k)
+    a = torch.randn(m, k, generator=g)
+    w = torch.randn(n, k, generator=g) / math.sqrt(k)
+    ref = a.double() @ w.double().t()                          # ~N(0, 1) entries
+    grp = ref.reshape(m, n // 32, 32)
+    mean_ref = grp.mean(dim=2)
+    dev_ref = grp - mean_ref[..., None]
+    m2_ref = (dev_ref ** 2).sum(dim=2)
+    tol = 4e-5                                                 # per value: split-fp16 operands, fp32 accumulation (test_gemm_layernorm_fold)
+    tol_m2 = 2.0 * tol * dev_ref.abs().sum(dim=2) + 32.0 * tol * tol       # M2 = sum d^2 with every d off by at most 2 tol
+    a_h2 = ops.h2_pack(a).to(DEV)
+    w_p, w_s = ops.split_f16_weights_h2(w)
+    w_p = w_p.to(DEV)
+    ws = torch.empty(8 << 20, dtype=torch.float32, device=DEV)
+    scratch = torch.empty(8 << 20, dtype=torch.float32, device=DEV)
+    counters = torch.zeros(256, dtype=torch.int32, device=DEV)
+    modes = {"atomic": {}, "workspace": dict(workspace=ws), "fixup": dict(splitk=(scratch, counters))}
+
+    def run(**kw):
+        out = torch.full((m, n), float("nan"), device=DEV)
+        st = torch.full((m, n // 32, 2), float("nan"), device=DEV)
+        ops.gemm(H2, a_h2, w_p, None, None, None, None, out, None, n=n, cp=k, w_scale=w_s, stats_out=st, **kw)
+        return out, st
+
+    got = {mode: run(**kw) for mode, kw in modes.items()}
+    torch.cuda.synchronize()
+    assert int(counters.abs().sum()) == 0
+    for mode, (out, st) in got.items():
+        name = f"stats_out.{mode}.m{m}.k{k}"
+        out, st = out.cpu(), st.cpu()
+        _cmp(f"{name}.out_f32", out, ref, atol=tol)
+        _cmp(f"{name}.mean", st[..., 0], mean_ref, atol=tol)
+        err_m2 = (st[..., 1].double() - m2_ref).abs()
+        assert int((~(err_m2 <= tol_m2)).sum()) == 0, f"{name}.m2: max err {float(err_m2.max()):.3e} (tolerance from the values' {tol:g})"
+        mu, rstd = F._merge_row_stats(st, eps)
+        _cmp(f"{name}.mu", mu, ref.mean(dim=1), atol=tol)
+        _cmp(f"{name}.rstd", rstd, 1.0 / torch.sqrt(ref.var(dim=1, unbiased=False) + eps), atol=0.0, rtol=1e-4)     # var off by ~2 tol E|d|
+        print(f"{name}: max err out {float((out.double() - ref).abs().max()):.2e}, mean {float((st[..., 0].double() - mean_ref).abs().max()):.2e}, "
+              f"M2 {float(err_m2.max()):.2e}")
+    # the atomic and two-pass forms take the one unsplit launch (the same bits); the fix-up really cut K (other bits)
+    assert torch.equal(got["atomic"][0], got["workspace"][0]) and torch.equal(got["atomic"][1], got["workspace"][1])
+    assert not torch.equal(got["atomic"][0], got["fixup"][0]), "the fix-up launch was not split"
+    # grouped: the problem, a short-K statistics problem of the same tile configuration, and the problem with the fix-up scratch
+    b = torch.randn(m, 768, generator=g)
+    w2 = torch.randn(n, 768, generator=g) / math.sqrt(768)
+    b_h2 = ops.h2_pack(b).to(DEV)
+    w2_p, w2_s = ops.split_f16_weights_h2(w2)
+    w2_p = w2_p.to(DEV)
+    probs = [(a_h2, w_p, w_s, k, {}), (b_h2, w2_p, w2_s, 768, {}), (a_h2, w_p, w_s, k, dict(splitk=(scratch, counters)))]
+    bufs = lambda: (torch.full((m, n), float("nan"), device=DEV), torch.full((m, n // 32, 2), float("nan"), device=DEV))
+    single, grouped = [bufs() for _ in probs], [bufs() for _ in probs]
+    for (aa, ww, sc, kk, kw), (o, st) in zip(probs, single):
+        ops.gemm(H2, aa, ww, None, None, None, None, o, None, n=n, cp=kk, w_scale=sc, stats_out=st, **kw)
+    with ops.lockstep() as ls:
+        for (aa, ww, sc, kk, kw), (o, st) in zip(probs, grouped):
+            with ls.chain():
+                ops.gemm(H2, aa, ww, None, None, None, None, o, None, n=n, cp=kk, w_scale=sc, stats_out=st, **kw)
+    torch.cuda.synchronize()
+    assert ls.launches == [("group", 3)]
+    # the first two share one launch (same configuration, neither split); the fix-up problem is cut into K-slices and launched alone
+    assert ops.grouped_launch_count(ls.groups[0]) == 2
+    for i, ((o1, s1), (o2, s2)) in enumerate(zip(single, grouped)):
+        assert torch.equal(o1.view(torch.int32), o2.view(torch.int32)) and torch.equal(s1.view(torch.int32), s2.view(torch.int32)), i
+    assert torch.equal(single[0][0], got["atomic"][0]) and torch.equal(single[2][1], got["fixup"][1])
+    assert int(counters.abs().sum()) == 0
+
+
 SPLITK_CASES = [
     # name, M-structure (nb, lin, lout), cin, n, taps, stride, pad, flags
     ("sk_out_proj", (1, 64, 64), 768, 768, 1, 1, 0, dict(bias=True, res="h2", want="f32")),

@@ -257,6 +257,30 @@ int emage_attention_dropout(int dtype, const void* q, int ldq, const void* k, in
                             void* out, int ldo, int B, int H, int Tq, int Tk, int hd, const float* pmask, void* stream);
 
 /*
+ * One self-attention site in ONE launch: the qkv projection of emage_gemm (EMAGE_H2) and emage_attention on its q / k / V^T, with
+ * q, k and v kept on chip.  One workgroup per (clip, head) computes the 64 x 576 block [q_h | k_h | v_h] of the projection, stages it in
+ * LDS and runs the attention of that head.  `out` is bit for bit what the two-launch sequence writes:
+ *     emage_gemm(dtype, A, lda, W, bias, out_f32 = qk (B T, 2 d), out_t = vt (V^T, t_col0 = 2 d, t_rows = T), M = B T, N = 3 d, Cp = d,
+ *                a_scale, w_scale)   (with the LayerNorm fold: the same problem with ln_stats / ln_c / ln_eps, emage_gemm_grouped)
+ *     emage_attention(dtype, qk, 2 d, qk + d, 2 d, vt, T, d, out, ldo, B, H, T, T, d / H)
+ * Only T = 64, d = 768, H = 4 (hd = 192) and dtype EMAGE_H2 (with any activation shift: `out` is the image of that scale, A is read with
+ * a_scale) are supported; anything else is EMAGE_EINVAL.
+ * A:    (B T, lda) EMAGE_H2 image, lda % 8 == 0, lda >= d; with ln_stats the RAW pre-norm sum of a folded LayerNorm (emage_gemm_problem).
+ * W:    (3 d, d) packed image of the in_proj weight times w_scale (rows q | k | v, as emage_gemm takes it); bias (3 d) fp32, required.
+ * ln_stats / ln_c / ln_eps: the LayerNorm fold of emage_gemm_problem (ln_np = 24); NULL ln_stats = off, ln_c then required.
+ * out:  (B T, ldo) EMAGE_H2 image, ldo % 8 == 0, ldo >= d.  Pointers 16-byte aligned.
+ * The grouped form runs 1..4 independent problems of the same T / d / H in one launch (the part-wise decoder stacks in lock step).
+ */
+typedef struct emage_qkv_attention_problem {
+    const void* A; const void* W; const float* bias; const float* ln_stats; const float* ln_c; void* out;
+    int lda, ldo, B;
+    float a_scale, w_scale, ln_eps;
+} emage_qkv_attention_problem;
+int emage_qkv_attention(int dtype, const void* A, int lda, const void* W, const float* bias, const float* ln_stats, const float* ln_c,
+                        float ln_eps, void* out, int ldo, int B, int T, int d, int H, float a_scale, float w_scale, void* stream);
+int emage_qkv_attention_grouped(int dtype, const emage_qkv_attention_problem* problems, int n_problems, int T, int d, int H, void* stream);
+
+/*
  * K5 — LayerNorm(C, eps) over rows (post-norm of every transformer sub-layer):
  *   y = (x - mean) * rsqrt(var + eps) * gamma + beta (+ add[m][:])
  * x: (M, ldx) `dtype` — the residual stream is stored in the compute dtype (fp32 in parity mode, bf16 in bf16

@@ -10,7 +10,7 @@ LIB_PATH = os.path.join(_HERE, "csrc", "libemage_hip.so")
 TOOLS_LIB_PATH = os.path.join(_HERE, "csrc", "libemage_hip_tools.so")   # -DEMAGE_TOOLS twin: every tile configuration + emage_set_tuning
 
 F32, BF16, F16X3, H2 = 0, 1, 2, 3
-ABI_VERSION = 17
+ABI_VERSION = 18
 
 _p, _i, _f, _l = C.c_void_p, C.c_int, C.c_float, C.c_long
 
@@ -23,6 +23,13 @@ class GemmProblem(C.Structure):
                 + [(n, _p) for n in ("ln_stats", "ln_c", "rs_stats", "rs_gamma", "rs_beta", "st_out")]       # the LayerNorm fold (round 6; all NULL = off)
                 + [("ln_np", _i), ("rs_np", _i), ("ln_eps", _f)]
                 + [("sk_ws", _p), ("sk_ws_bytes", _l), ("sk_count", _p), ("sk_tiles", _i)])             # split-K fix-up scratch (round 6; NULL = off)
+
+
+class QkvAttentionProblem(C.Structure):
+    """`emage_qkv_attention_problem` of include/emage_hip.h (emage_qkv_attention_grouped takes an array of them)."""
+    _fields_ = ([(n, _p) for n in ("A", "W", "bias", "ln_stats", "ln_c", "out")]
+                + [(n, _i) for n in ("lda", "ldo", "B")]
+                + [(n, _f) for n in ("a_scale", "w_scale", "ln_eps")])
 
 
 class FinalizeEntry(C.Structure):
@@ -47,6 +54,8 @@ SIGNATURES = {
     "emage_wav_block0": [_i, _p, _l, _i, _i, _l, _i, _p, _p, _f, _p, _p, _i, _i, _i, _p, _p, _p, _i, _i, _p, _i, _i, _i, _f, _f, _p],
     "emage_attention": [_i, _p, _i, _p, _i, _p, _i, _i, _p, _i, _i, _i, _i, _i, _i, _p],
     "emage_attention_dropout": [_i, _p, _i, _p, _i, _p, _i, _i, _p, _i, _i, _i, _i, _i, _i, _p, _p],
+    "emage_qkv_attention": [_i, _p, _i, _p, _p, _p, _p, _f, _p, _i, _i, _i, _i, _i, _f, _f, _p],
+    "emage_qkv_attention_grouped": [_i, C.POINTER(QkvAttentionProblem), _i, _i, _i, _i, _p],
     "emage_bn_stats_workspace_bytes": [_i, _i],
     "emage_bn_stats": [_p, _i, _i, _i, _p, _l, _p, _p, _p, _p, _f, _p],
     "emage_bn_apply": [_p, _i, _p, _p, _p, _p, _p, _i, _p, _p, _p, _p, _f, _f, _p, _i, _i, _i, _p],

@@ -148,9 +148,13 @@ __device__ __forceinline__ void attn_stage_kv(const AttnArgs& p, const int b, co
     }
 }
 
-template <typename T, int HD, int NT, int DSP = DS, bool X3 = false, bool H2OUT = false, bool LDSKV = false>
+// QLDS (qkv_attention.hip): K, V^T AND Q are already staged in LDS by the caller — Q as the split planes of attn_stage_kv's K layout at
+// smem + AttnLds::BYTES (one row per query) — and the workgroup has passed its barrier: no global operand reads, no staging here.  The
+// fragments are the same split fp16 planes of the same float32 values, so the result is bit for bit that of the LDSKV path.
+template <typename T, int HD, int NT, int DSP = DS, bool X3 = false, bool H2OUT = false, bool LDSKV = false, bool QLDS = false>
 __device__ __forceinline__ void attn_tile(const AttnArgs& p, const int b, const int h, const int qt, const int dpart, unsigned char* smem = nullptr) {
     static_assert(!LDSKV || (X3 && DSP == 1 && NT <= 4 && NT % 2 == 0), "staged K / V^T: split-f16 form, Tk <= 64");
+    static_assert(!QLDS || LDSKV, "staged Q: staged K / V^T too");
     constexpr int EPC = Elem<T>::EPC;
     static_assert(!X3 || (EPC == 4 && NT % 2 == 0), "split-f16 attention: fp32 operands, key tiles pair up");
     constexpr int ES = 16 / EPC;
@@ -171,10 +175,12 @@ __device__ __forceinline__ void attn_tile(const AttnArgs& p, const int b, const 
 
     const int qrow = min(q0 + fr, p.Tq - 1);
     const int qoff = ((b * p.Tq + qrow) * p.ldq + h * HD + fg * EPC) * ES;
-    uint4 qf[NSTEP];
+    uint4 qf[QLDS ? 1 : NSTEP];
+    if constexpr (!QLDS) {
 #pragma unroll
-    for (int s = 0; s < NSTEP; ++s) qf[s] = bload128(rq, qoff, s * 64);
-    if constexpr (LDSKV) {
+        for (int s = 0; s < NSTEP; ++s) qf[s] = bload128(rq, qoff, s * 64);
+    }
+    if constexpr (LDSKV && !QLDS) {
         // the workgroup's K / V^T go to LDS behind this wave's Q loads (already in flight); EVERY wave of the workgroup takes part,
         // also one whose query tile lies past Tq (it leaves behind the barrier)
         attn_stage_kv<HD, NT, H2OUT>(p, b, h, smem);
@@ -240,7 +246,10 @@ __device__ __forceinline__ void attn_tile(const AttnArgs& p, const int b, const 
     if constexpr (X3) {
         SplitF16 qs[NSTEP / 2];                // Q is re-used by every key tile: split once
 #pragma unroll
-        for (int s = 0; s < NSTEP / 2; ++s) qs[s] = split_chunks(qf[2 * s], qf[2 * s + 1], p.h2s);
+        for (int s = 0; s < NSTEP / 2; ++s) {
+            if constexpr (QLDS) qs[s] = lds_frag(smem + AttnLds<HD, NT>::BYTES, AttnLds<HD, NT>::KROW, qrow, s);
+            else qs[s] = split_chunks(qf[2 * s], qf[2 * s + 1], p.h2s);
+        }
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt) {
             f32x4 acc = {0.f, 0.f, 0.f, 0.f};

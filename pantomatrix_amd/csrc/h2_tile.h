@@ -16,6 +16,8 @@
 #pragma once
 #include "gemm_tile.h"
 #include "h2.h"
+#include <cstddef>
+#include <type_traits>
 
 namespace emage_dev {
 
@@ -342,8 +344,12 @@ __device__ __forceinline__ void h2_tile_epilogue(const GemmArgs& p, f32x4 (&acc)
 // accumulator is that of KPB = 1, so the result is the same bits.  Plain K-loop only (not PIPE / DILV).
 // LNF: the instantiation carries the LayerNorm-fold paths (GemmArgs::ln_stats / rs_stats / st_out); the plain one ignores those fields
 // SKF: the instantiation carries the in-kernel split-K fix-up (GemmArgs::sk_ws / sk_count)
-template <int BM, int BN, int WM, int WN, int NS, int NLW, bool PIPE, bool PRE, bool DILV = false, bool TRACE = false, int KPB = 1, bool LNF = false, bool SKF = false>
-__device__ __forceinline__ void gemm_h2_tile(const GemmArgs& p, const int m0, const int n0, unsigned char* smem, const int split = 0) {
+// SEG3 (qkv_attention.hip): the BN tile rows are three slices of BN / 3 W rows, p.N / 3 rows apart (q, k, v of one head of a packed in_proj)
+// EPI: a callable that replaces the epilogue — epi(acc, first row of the wave tile, wm, wn, fr, fg, ln_mu, ln_rs), with every compute wave
+// past the K-loop (the operand ring is still being read by other waves: the callable synchronises before it reuses it)
+template <int BM, int BN, int WM, int WN, int NS, int NLW, bool PIPE, bool PRE, bool DILV = false, bool TRACE = false, int KPB = 1, bool LNF = false, bool SKF = false,
+          bool SEG3 = false, typename EPI = std::nullptr_t>
+__device__ __forceinline__ void gemm_h2_tile(const GemmArgs& p, const int m0, const int n0, unsigned char* smem, const int split = 0, EPI epi = nullptr) {
     constexpr int ES = 4, BK = 32, RB = 128, RPI = 8;
     constexpr int NCW = WM * WN, NL = NLW ? NLW : NCW;
     constexpr int WTM = BM / WM, WTN = BN / WN, FM = WTM / 16, FN = WTN / 16, FP = FN / 2;
@@ -411,7 +417,7 @@ __device__ __forceinline__ void gemm_h2_tile(const GemmArgs& p, const int m0, co
 #pragma unroll
     for (int j = 0; j < GB; ++j) {
         const int row = (lw + NL * j) * RPI + lrow;
-        const int n = n0 + row;
+        const int n = n0 + row + (SEG3 ? (row / (BN / 3)) * (p.N / 3 - BN / 3) : 0);
         const int lc = lslot ^ swzW<8>(row);
         b_voff[j] = n < p.N ? (unsigned)n * (unsigned)(p.K * ES) + (unsigned)((2 * (lc & 3) + (lc >> 2)) * 16) : OOB;
     }
@@ -740,6 +746,10 @@ __device__ __forceinline__ void gemm_h2_tile(const GemmArgs& p, const int m0, co
         // prologue, the compiler's vmcnt(0) for these loads also drained the first K-tiles' DMA: +1 us per launch, profiles/r06_ln_fold_per_launch_v3.txt)
         if (p.ln_stats && !EMAGE_DBG(p, 256 | 512)) ln_wave_finish<WTM, FM>(fr, p.ln_eps, lnp, ln_mu, ln_rs);     // (wave-uniform conditions: the lane exchanges inside need every lane)
         if (p.rs_stats && !EMAGE_DBG(p, 256 | 512)) ln_wave_finish<WTM, FM>(fr, p.ln_eps, rsp, rs_mu, rs_rs);
+    }
+    if constexpr (!std::is_same_v<EPI, std::nullptr_t>) {
+        epi(acc, m0 + wm * WTM, wm, wn, fr, fg, ln_mu, ln_rs);
+        return;
     }
     h2_tile_epilogue<FM, FN, false, PRE, PM, PP, LNF, SKF>(p, acc, m0 + wm * WTM, n0 + wn * WTN, fr, fg, vt_tile, pre_r, split, ln_mu, ln_rs, rs_mu, rs_rs);
     if (vt_tile) { __syncthreads(); return; }

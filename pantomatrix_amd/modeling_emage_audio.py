@@ -93,6 +93,9 @@ class _EmageModule(torch.nn.Module):
         self.group_gemms = True                # part-wise stacks (VQ part decoders, refinement layers + heads, ...) walk in lock step and
                                                # their contractions share launches (ops.lockstep / emage_gemm_grouped); False = one stream
                                                # lane per chain, one launch per contraction (the round-3 form; same bits)
+        self.fuse_self_attention = True        # EMAGE_H2 eval forward, 64-frame windows of enough clips to fill the GPU: each self-attention site's qkv
+                                               # projection and attention run as ONE launch (ops.qkv_attention: q / k / v never leave the chip);
+                                               # False = the two launches (same bits)
         self.group_face_body = False           # forward(): the 4 face decoder layers walk in lock step with the first 4 audio cross-attention
                                                # layers of the body (same shapes, different weights: 6 contractions per layer pair share
                                                # launches) instead of running on two stream lanes; same bits (A/B switch)
@@ -1184,6 +1187,13 @@ class EmageAudioModel(_WavEncoderMixin, _EmageModule):
         """x: _X.  Returns the pre-norm sum x + out_proj(attention) at residual precision (stats: as an `_S`, for a folded LayerNorm)."""
         d, h = self.config.hidden_size, spec.N_HEAD
         m = b * t
+        if self._fused_self_attn(cx, b, t, d, h):
+            att = cx.lo(m, d)
+            key = name + ".sa.qkv"
+            e = cx.pk.w[key] if x.ln is None else cx.pk.w[key + "@" + x.ln[1]]
+            assert e["cp"] == d and e["n"] == 3 * d
+            ops.qkv_attention(cx.h2dt, x.a, e["w"], e["b"], att, b, w_scale=e.get("ws", 1.0), ln=None if x.ln is None else (x.ln[0], e["c"]))
+            return cx.gemm_s(att, name + ".sa.out", x, stats)
         qk = cx.f32(m, 2 * d) if cx.h2 else cx.lo(m, 2 * d)          # the attention kernel reads float32 q / k / v^T in the split modes
         vt = cx.vt_buffer(b, d, t)
         if cx.h2:
@@ -1193,6 +1203,14 @@ class EmageAudioModel(_WavEncoderMixin, _EmageModule):
         att = cx.lo(m, d)
         ops.attention(cx.gdt, qk[:, :d], qk[:, d:], vt, d, att, b, h, t, t, d // h)
         return cx.gemm_s(att, name + ".sa.out", x, stats)
+
+    def _fused_self_attn(self, cx, b, t, d, h):
+        """Whether a self-attention site runs as one `ops.qkv_attention` launch: EMAGE_H2 eval forward on the GPU, a full 64-frame window, and at
+        least one (clip, head) workgroup per CU — with fewer, the two-launch form spreads the projection over more CUs (B = 1: 4 workgroups) —
+        and at least 16 clips (1024 rows: below, the folded projection takes a tile whose LayerNorm statistics merge in another order)."""
+        if not (self.fuse_self_attention and cx.h2 and not self.training and cx.dev.type == "cuda" and ops.qkv_attention_supported(cx.h2dt, t, d, h)):
+            return False
+        return b >= 16 and b * h >= torch.cuda.get_device_properties(cx.dev).multi_processor_count
 
     def _ln(self, cx, key, s, add=None, want_f32=False):
         """LayerNorm of a pre-norm sum (residual precision) -> _X; `add`: float32 / storage-type tensor folded in behind the norm.

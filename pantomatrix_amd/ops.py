@@ -139,14 +139,15 @@ class Lockstep:
 
     @staticmethod
     def _groupable(entry):
-        return entry[0] == "gemm" and entry[2][0] & 0xff == H2
+        return entry[0] in _GROUPED and entry[2][0] & 0xff == H2
 
     def _issue(self, entry):
         _fire(entry[0], [entry], lambda: entry[1](*entry[2]))
         self.launches.append((entry[0], 1))
 
     def _issue_group(self, entries):
-        _fire("gemm_grouped", entries, lambda: _gemm_grouped_entries(entries))
+        kind, issue = _GROUPED[entries[0][0]]
+        _fire(kind, entries, lambda: issue(entries))
         self.launches.append(("group", len(entries)))
         self.groups.append(entries)
 
@@ -164,11 +165,16 @@ class Lockstep:
                     ptr[ci] += 1
             if not heads:
                 break
-            if len(heads) == 1 or not self.enabled:
-                for e in heads:
-                    self._issue(e)
-            else:
-                self._issue_group(heads)
+            # heads of one kind (contractions / fused self-attention sites) share a grouped call, in the order of their first head
+            kinds = {}
+            for e in heads:
+                kinds.setdefault(e[0], []).append(e)
+            for same in kinds.values():
+                if len(same) == 1 or not self.enabled:
+                    for e in same:
+                        self._issue(e)
+                else:
+                    self._issue_group(same)
         self.chains = []
 
 
@@ -595,6 +601,70 @@ def gemm(dtype, a, w, bias=None, slope=None, res=None, out=None, out_f32=None, o
     _gemm(dtype, a, w, bias, slope, res, out, out_f32, out_t, n, cp, n_store, t_col0, t_rows, bool(res_first), taps, stride, pad,
           lin, lout, m, float(w_scale), float(act_scale(dtype) if a_scale is None else a_scale), bool(res_h2),
           ln_stats, ln_c, rs_stats, rs_gamma, rs_beta, stats_out, float(ln_eps), sk_ws, sk_count)
+
+
+# Fused self-attention site (include/emage_hip.h: emage_qkv_attention): qkv projection + attention of every (clip, head) in one launch
+_QKV_T, _QKV_D, _QKV_H = 64, 768, 4
+_QKV_MAXG = 4                             # problems per grouped launch
+
+
+def qkv_attention_supported(dtype, t, d, h):
+    """Shapes `qkv_attention` is built for: EMAGE_H2 (any activation shift), T = 64 frames, d = 768, 4 heads."""
+    return dtype & 0xff == H2 and t == _QKV_T and d == _QKV_D and h == _QKV_H
+
+
+def _qkv_fields(a, w, bias, ln_stats, ln_c, out, b, w_scale, a_scale, ln_eps):
+    return dict(A=_ptr(a), W=_ptr(w), bias=_ptr(bias), ln_stats=_ptr(ln_stats), ln_c=_ptr(ln_c), out=_ptr(out), lda=_ld(a), ldo=_ld(out), B=b,
+                a_scale=a_scale, w_scale=w_scale, ln_eps=ln_eps)
+
+
+@_op("qkv_attention", "(int dtype, Tensor a, Tensor w, Tensor bias, Tensor? ln_stats, Tensor? ln_c, Tensor(a!) out, int b, float w_scale, "
+                      "float a_scale, float ln_eps) -> ()")
+def _qkv_attention(dtype, a, w, bias, ln_stats, ln_c, out, b, w_scale, a_scale, ln_eps):
+    f = _qkv_fields(a, w, bias, ln_stats, ln_c, out, b, w_scale, a_scale, ln_eps)
+    check(_lib.load().emage_qkv_attention(dtype, f["A"], f["lda"], f["W"], f["bias"], f["ln_stats"], f["ln_c"], f["ln_eps"], f["out"], f["ldo"],
+                                          b, _QKV_T, _QKV_D, _QKV_H, a_scale, w_scale, _stream()), "qkv_attention")
+
+
+@_op("qkv_attention_grouped", "(int dtype, Tensor(a!)[] tensors, int[] desc, float[] scales) -> ()")
+def _qkv_attention_grouped(dtype, tensors, desc, scales):
+    n = len(desc) // 9
+    arr = (_lib.QkvAttentionProblem * n)()
+    for i in range(n):
+        for j, name in enumerate(("A", "W", "bias", "ln_stats", "ln_c", "out", "lda", "ldo", "B")):
+            v = desc[9 * i + j]
+            setattr(arr[i], name, (v or None) if j < 6 else v)
+        arr[i].a_scale, arr[i].w_scale, arr[i].ln_eps = scales[3 * i], scales[3 * i + 1], scales[3 * i + 2]
+    check(_lib.load().emage_qkv_attention_grouped(dtype, arr, n, _QKV_T, _QKV_D, _QKV_H, _stream()), "qkv_attention_grouped")
+
+
+def _qkv_attention_grouped_entries(entries):
+    """Recorded `emage::qkv_attention` calls (Lockstep) of ONE dtype -> grouped calls of up to _QKV_MAXG problems each."""
+    dtype = entries[0][2][0]
+    for i in range(0, len(entries), _QKV_MAXG):
+        tensors, desc, scales = [], [], []
+        for _name, _op_, args, _meta in entries[i:i + _QKV_MAXG]:
+            assert args[0] == dtype
+            f = _qkv_fields(*args[1:])
+            desc += [int(f[k] or 0) for k in ("A", "W", "bias", "ln_stats", "ln_c", "out", "lda", "ldo", "B")]
+            scales += [float(f["a_scale"]), float(f["w_scale"]), float(f["ln_eps"])]
+            tensors += [t for t in args[1:7] if torch.is_tensor(t)]
+        _qkv_attention_grouped.op(dtype, tensors, desc, scales)
+
+
+def qkv_attention(dtype, a, w, bias, out, b, *, w_scale, a_scale=None, ln=None, ln_eps=1e-5):
+    """One self-attention site in one launch (include/emage_hip.h: emage_qkv_attention): `out` (B*64, ldo) EMAGE_H2 image <- the attention of
+    the qkv projection of `a` with the packed in_proj `w` / `bias` — bit-identical to `gemm` (q / k float32, V^T) + `attention`.
+    ln = (row statistics of `a`, c): `a` is the raw pre-norm sum of a folded LayerNorm and `w` / `bias` its folded twins (see `gemm`).
+    Inside a `lockstep()` the sites at the heads of the chains share grouped launches."""
+    _dev(a)
+    ln_stats, ln_c = ln if ln is not None else (None, None)
+    _qkv_attention(dtype, a, w, bias, ln_stats, ln_c, out, int(b), float(w_scale), float(act_scale(dtype) if a_scale is None else a_scale),
+                   float(ln_eps) if ln is not None else 0.0)
+
+
+_GROUPED = {"gemm": ("gemm_grouped", lambda entries: _gemm_grouped_entries(entries)),
+            "qkv_attention": ("qkv_attention_grouped", lambda entries: _qkv_attention_grouped_entries(entries))}
 
 
 @_op("wav_conv_in", "(int dtype, Tensor wav, Tensor w, Tensor? bias, Tensor? slope, Tensor(a!) out, int lout, int stride, int pad, "

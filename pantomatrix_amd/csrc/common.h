@@ -2,6 +2,9 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <iterator>
+#include <type_traits>
+#include <utility>
 #include "../../include/emage_hip.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -60,4 +63,22 @@ static inline int device_cus() {
 static inline int launch_status() {
     hipError_t e = hipGetLastError();
     return (int)e;
+}
+
+// Tile-configuration tables (gemm.hip, gemm_h2.hip, gemm_h2_pp.hip): a constexpr array of rows, each with an `id`.  with_config calls
+// f.template operator()<row>() for the row of that id — the row arrives as a template argument, so f can name the kernel it describes —
+// and returns its result; an id without a row is EMAGE_EINVAL.  (The id is compared as an integral_constant: reading ROWS[I].id through the
+// reference parameter crashes this compiler's code generation.)
+template <auto& ROWS> constexpr bool unique_config_ids() {
+    for (size_t i = 0; i < std::size(ROWS); ++i)
+        for (size_t j = i + 1; j < std::size(ROWS); ++j)
+            if (ROWS[i].id == ROWS[j].id) return false;
+    return true;
+}
+template <auto& ROWS, typename F> int with_config(int id, F&& f) {
+    int rc = EMAGE_EINVAL;
+    [&]<size_t... I>(std::index_sequence<I...>) {
+        (void)((id == std::integral_constant<int, ROWS[I].id>::value && (rc = f.template operator()<ROWS[I]>(), true)) || ...);
+    }(std::make_index_sequence<std::size(ROWS)>{});
+    return rc;
 }

@@ -97,14 +97,7 @@ __global__ __launch_bounds__(NTHREADS) void gemm_kernel(GemmArgs p) {
     const int lane = tid & 63, wave = tid >> 6;
     const int wm = wave / WN, wn = wave % WN;
 
-    // XCD-aware tile order: consecutive block ids round-robin over the 8 XCDs, so give each XCD a
-    // contiguous run of tiles (neighbouring tiles share A rows / W columns in that XCD's L2).
-    const int nblk = p.tiles_m * p.tiles_n;
-    int bid = blockIdx.x;
-    {
-        const int q = nblk >> 3, r = nblk & 7, xcd = bid & 7, idx = bid >> 3;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
+    const int bid = xcd_run_order(blockIdx.x, p.tiles_m * p.tiles_n);
     const int tile_n = bid % p.tiles_n, tile_m = bid / p.tiles_n;
     const int m0 = tile_m * BM, n0 = tile_n * BN;
 
@@ -202,93 +195,93 @@ __global__ __launch_bounds__(NTHREADS) void gemm_kernel(GemmArgs p) {
     gemm_epilogue<T, FM, FN>(p, acc, m0 + wm * WTM, n0 + wn * WTN, fr, fg);
 }
 #endif   // EMAGE_TOOLS: the register-staged reference kernel
-template <typename T, int BM, int BN, int WM, int WN, int NS, int KC, bool X3, int KPS, bool FPRE>
-__global__ __launch_bounds__(WM * WN * 64, (WM * WN == 4 ? lds_blocks<BM, BN, NS, KC, KPS>() : 1)) void gemm_pipe_kernel(GemmArgs p) {
-    __shared__ __attribute__((aligned(128))) unsigned char smem[pipe_smem_bytes<T, BM, BN, NS, KC, KPS>()];
-    // XCD-aware tile order: consecutive block ids round-robin over the 8 XCDs, so each XCD walks a contiguous run of
-    // tiles (neighbouring tiles share A rows / W columns in that XCD's L2)
-    const int nblk = p.tiles_m * p.tiles_n;
-    int bid = blockIdx.x;
-    {
-        const int q = nblk >> 3, r = nblk & 7, xcd = bid & 7, idx = bid >> 3;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
+
+// One ring-kernel tile configuration: the template arguments of gemm_pipe_tile, by name
+struct PipeTile {
+    int bm, bn;                  // block tile
+    int wm = 4, wn = 2;          // wave grid
+    int ns = 2;                  // ring depth
+    int kc = 8;                  // 16-byte chunks per K-tile row
+    int kps = 1;                 // K-tiles per ring slot and barrier
+    bool fpre = false;           // bias / slope / residual fetched ahead of the K-loop
+};
+struct PipeRow {
+    int id;
+    PipeTile t;
+    bool f32_only = false;       // fp32-storage modes only (two K-tiles per slot: an even K-tile count is guaranteed there)
+};
+// THE tile configurations of the LDS-DMA ring kernels; launch_pipe and gemm_pipe_kernel take their row from here.  25, 32, 33, 34, 36 are
+// what the heuristic selects (the product library carries nothing else); the rest are kept for tools/bench_gemm.py sweeps
+constexpr PipeRow PIPE_CONFIGS[] = {
+    {25, {.bm = 64, .bn = 64, .wm = 2}},
+    {32, {.bm = 64, .bn = 192, .ns = 3}},                                     // 8 waves (two per SIMD): a lone block per CU hides its own latencies
+    {33, {.bm = 64, .bn = 192}},
+    {34, {.bm = 128, .bn = 128}},
+    {36, {.bm = 128, .bn = 64, .ns = 3}},
+#ifdef EMAGE_TOOLS
+    {18, {.bm = 128, .bn = 128, .wm = 2}},
+    {27, {.bm = 64, .bn = 192, .wm = 2}},                                     // one (clip, head) per block at T = 64, hd = 192
+    {37, {.bm = 128, .bn = 192}},
+    {38, {.bm = 128, .bn = 128, .ns = 3}},                                    // deeper rings / fatter tiles: sweeps of the per-CU operand stream
+    {39, {.bm = 128, .bn = 128, .ns = 4}},
+    {40, {.bm = 64, .bn = 192, .ns = 4}},
+    {41, {.bm = 128, .bn = 256}},
+    {42, {.bm = 128, .bn = 192, .ns = 3}},
+    {43, {.bm = 64, .bn = 64, .wm = 2, .ns = 4}},                             // deeper rings for small grids (measured: no gain,
+    {44, {.bm = 64, .bn = 64, .wm = 2, .ns = 3}},                             // profiles/r02_gemm_sweep_f16x3_ring_depth_small_grids.txt)
+    {49, {.bm = 64, .bn = 192, .fpre = true}},                                // 33 with bias / slope / residual fetched ahead of the K-loop
+    // two K-tiles per ring slot / barrier: fp32-storage modes only
+    {45, {.bm = 64, .bn = 192, .kps = 2}, true},
+    {46, {.bm = 128, .bn = 128, .kps = 2}, true},
+    {47, {.bm = 64, .bn = 64, .wm = 2, .kps = 2}, true},
+    {48, {.bm = 128, .bn = 64, .kps = 2}, true},
+#endif
+};
+static_assert(unique_config_ids<PIPE_CONFIGS>(), "one row per id");
+
+template <typename T, bool X3, PipeTile C>
+__global__ __launch_bounds__(C.wm * C.wn * 64, (C.wm * C.wn == 4 ? lds_blocks<C.bm, C.bn, C.ns, C.kc, C.kps>() : 1)) void gemm_pipe_kernel(GemmArgs p) {
+    __shared__ __attribute__((aligned(128))) unsigned char smem[pipe_smem_bytes<T, C.bm, C.bn, C.ns, C.kc, C.kps>()];
+    const int bid = xcd_run_order(blockIdx.x, p.tiles_m * p.tiles_n);
     const int tile_n = bid % p.tiles_n, tile_m = bid / p.tiles_n;
-    gemm_pipe_tile<T, BM, BN, WM, WN, NS, KC, FPRE, X3, EPI_LINEAR, KPS>(p, tile_m * BM, tile_n * BN, smem);
+    gemm_pipe_tile<T, C.bm, C.bn, C.wm, C.wn, C.ns, C.kc, C.fpre, X3, EPI_LINEAR, C.kps>(p, tile_m * C.bm, tile_n * C.bn, smem);
 }
 
 #ifdef EMAGE_TOOLS
 template <typename T, int BM, int BN, int WM, int WN>
 int launch(GemmArgs& a, hipStream_t s) {
-    a.tiles_m = (a.M + BM - 1) / BM;
-    const int ncols = a.n_store > a.N ? a.n_store : a.N;
-    a.tiles_n = (ncols + BN - 1) / BN;
+    set_tile_grid(a, BM, BN);
     hipLaunchKernelGGL((gemm_kernel<T, BM, BN, WM, WN>), dim3(a.tiles_m * a.tiles_n), dim3(NTHREADS), 0, s, a);
     return launch_status();
 }
-
 #endif
 
-template <typename T, bool X3, int BM, int BN, int WM, int WN, int NS, int KC = 8, int KPS = 1, bool FPRE = false>
+template <typename T, bool X3, PipeTile C>
 int launch_pipe(GemmArgs& a, hipStream_t s) {
-    a.tiles_m = (a.M + BM - 1) / BM;
-    const int ncols = a.n_store > a.N ? a.n_store : a.N;
-    a.tiles_n = (ncols + BN - 1) / BN;
-    hipLaunchKernelGGL((gemm_pipe_kernel<T, BM, BN, WM, WN, NS, KC, X3, KPS, FPRE>), dim3(a.tiles_m * a.tiles_n), dim3(WM * WN * 64), 0, s, a);
+    set_tile_grid(a, C.bm, C.bn);
+    hipLaunchKernelGGL((gemm_pipe_kernel<T, X3, C>), dim3(a.tiles_m * a.tiles_n), dim3(C.wm * C.wn * 64), 0, s, a);
     return launch_status();
 }
 
-// Tile configurations.  0 / 3: register-staged kernels (the independent implementation tools/bench_gemm.py validates
-// the ring kernels against).  The rest are LDS-DMA ring kernels; 25, 32, 33, 34, 36 are what the heuristic selects,
-// 18 / 27 / 37 are kept for tools/bench_gemm.py sweeps.
 template <typename T, bool X3>
 int run_config(int cfg, GemmArgs& a, hipStream_t s) {
-    // the product library carries the five configurations the heuristic selects; everything else is the tools build's
-    switch (cfg) {
-        case 25: return launch_pipe<T, X3, 64, 64, 2, 2, 2>(a, s);
-        case 32: return launch_pipe<T, X3, 64, 192, 4, 2, 3, 8>(a, s);    // 8 waves (two per SIMD): a lone block per CU hides its own latencies
-        case 33: return launch_pipe<T, X3, 64, 192, 4, 2, 2, 8>(a, s);
-        case 34: return launch_pipe<T, X3, 128, 128, 4, 2, 2, 8>(a, s);
-        case 36: return launch_pipe<T, X3, 128, 64, 4, 2, 3, 8>(a, s);
-        default: break;
-    }
 #ifdef EMAGE_TOOLS
-    if constexpr (!X3) {
+    if constexpr (!X3) {     // 0 / 3: register-staged kernels (the independent implementation tools/bench_gemm.py validates the ring kernels against)
         if (cfg == 0) return launch<T, 128, 128, 2, 2>(a, s);
         if (cfg == 3) return launch<T, 64, 64, 2, 2>(a, s);
     }
-    switch (cfg) {
-        case 18: return launch_pipe<T, X3, 128, 128, 2, 2, 2>(a, s);
-        case 27: return launch_pipe<T, X3, 64, 192, 2, 2, 2, 8>(a, s);    // one (clip, head) per block at T = 64, hd = 192
-        case 37: return launch_pipe<T, X3, 128, 192, 4, 2, 2, 8>(a, s);
-        case 38: return launch_pipe<T, X3, 128, 128, 4, 2, 3, 8>(a, s);   // deeper rings / fatter tiles: sweeps of the per-CU operand stream
-        case 39: return launch_pipe<T, X3, 128, 128, 4, 2, 4, 8>(a, s);
-        case 40: return launch_pipe<T, X3, 64, 192, 4, 2, 4, 8>(a, s);
-        case 41: return launch_pipe<T, X3, 128, 256, 4, 2, 2, 8>(a, s);
-        case 42: return launch_pipe<T, X3, 128, 192, 4, 2, 3, 8>(a, s);
-        case 43: return launch_pipe<T, X3, 64, 64, 2, 2, 4>(a, s);         // deeper rings for small grids (measured: no gain,
-        case 44: return launch_pipe<T, X3, 64, 64, 2, 2, 3>(a, s);         // profiles/r02_gemm_sweep_f16x3_ring_depth_small_grids.txt)
-        case 49: return launch_pipe<T, X3, 64, 192, 4, 2, 2, 8, 1, true>(a, s);   // 33 with bias / slope / residual fetched ahead of the K-loop
-        default: break;
-    }
-    if constexpr (sizeof(T) == 4) {      // fp32-storage modes: two K-tiles per ring slot / barrier (even K-tile count guaranteed)
-        switch (cfg) {
-            case 45: return launch_pipe<T, X3, 64, 192, 4, 2, 2, 8, 2>(a, s);
-            case 46: return launch_pipe<T, X3, 128, 128, 4, 2, 2, 8, 2>(a, s);
-            case 47: return launch_pipe<T, X3, 64, 64, 2, 2, 2, 8, 2>(a, s);
-            case 48: return launch_pipe<T, X3, 128, 64, 4, 2, 2, 8, 2>(a, s);
-            default: break;
-        }
-    }
 #endif
-    return EMAGE_EINVAL;
+    return with_config<PIPE_CONFIGS>(cfg, [&]<PipeRow R>() {
+        if constexpr (R.f32_only && sizeof(T) != 4) return (int)EMAGE_EINVAL;
+        else return launch_pipe<T, X3, R.t>(a, s);
+    });
 }
 
 template <typename T, bool X3>
 int dispatch(GemmArgs& a, hipStream_t s) {
     if (g_force_config >= 0) return run_config<T, X3>(g_force_config, a, s);
-    const int ncols = a.n_store > a.N ? a.n_store : a.N;
-    const long t128 = (long)((a.M + 127) / 128) * ((ncols + 127) / 128);
+    const int ncols = store_cols(a);
+    const long t128 = tile_count(a, 128, 128);
     // measured on MI355X (tools/bench_gemm.py, profiles/r01_gemm_sweep_8wave.txt): with M = 4096 the operand stream, not
     // MFMA, bounds these launches.  Many small resident blocks (64x64, 5 per CU) win on narrow outputs; everywhere else
     // 8-wave blocks (two waves per SIMD hide a block's own DMA / epilogue latency) beat the 4-wave tiles of the same shape
@@ -315,47 +308,6 @@ int dispatch(GemmArgs& a, hipStream_t s) {
 }  // namespace
 
 namespace {
-// argument checks of emage_gemm / emage_gemm_grouped -> the kernels' argument block
-int make_args(GemmArgs& a, int dtype, const void* A, int lda, const void* W, const float* bias, const float* slope,
-              const void* res, int ldr, int res_is_f32, int res_first,
-              void* out, int ldo, int n_store, float* out_f32, int ldf,
-              void* out_t, int t_col0, int t_rows, int t_ld,
-              int M, int N, int Cp, int taps, int stride, int pad, int Lin, int Lout, float a_scale, float w_scale) {
-    const int epc = dtype == EMAGE_BF16 ? 8 : 4;
-    if (!A || !W || M <= 0 || N <= 0 || taps <= 0 || Cp <= 0 || Cp % 64 != 0) return EMAGE_EINVAL;
-    if (dtype != EMAGE_BF16 && dtype != EMAGE_F32 && dtype != EMAGE_F16X3 && dtype != EMAGE_H2) return EMAGE_EINVAL;
-    if (dtype == EMAGE_H2) {       // 32-byte groups of 8 logical columns: every row of every h2 operand starts on a group
-        if (lda % 8 || (res && ldr % (res_is_f32 ? 4 : 8)) || (res && ((uintptr_t)res & 15))) return EMAGE_EINVAL;
-        if (out && (ldo % 8 || ((uintptr_t)out & 15) || ldo < ((((out_t ? t_col0 : N) > n_store ? (out_t ? t_col0 : N) : n_store) + 7) & ~7))) return EMAGE_EINVAL;
-        if ((bias && ((uintptr_t)bias & 15)) || (slope && ((uintptr_t)slope & 15))) return EMAGE_EINVAL;
-    }
-    if (lda % epc != 0 || lda < Cp) return EMAGE_EINVAL;                 // 16-byte aligned operand rows
-    if (((uintptr_t)A | (uintptr_t)W) & 15) return EMAGE_EINVAL;
-    if (Lout <= 0 || Lin <= 0 || M % Lout != 0 || stride <= 0) return EMAGE_EINVAL;
-    if (!out && !out_f32 && !out_t) return EMAGE_EINVAL;
-    if (out_t && (t_rows <= 0 || M % t_rows != 0 || t_ld < t_rows || t_col0 < 0 || t_col0 > N)) return EMAGE_EINVAL;
-    if ((dtype == EMAGE_F16X3 || dtype == EMAGE_H2) && !(a_scale > 0.f && w_scale > 0.f)) return EMAGE_EINVAL;
-    {   // operands are addressed through 32-bit buffer offsets: each must span less than 2 GiB (the host splits larger batches)
-        const long es = dtype == EMAGE_BF16 ? 2 : 4;
-        const long a_span = ((((long)(M / Lout)) * Lin - 1) * lda + Cp + (long)pad * lda) * es;
-        if (a_span >= (1L << 31) || (long)N * taps * Cp * es >= (1L << 31)) return EMAGE_EINVAL;
-    }
-    a.A = A; a.W = W; a.bias = bias; a.slope = slope; a.res = res; a.out = out; a.out_f32 = out_f32; a.out_t = out_t;
-    a.lda = lda; a.ldr = ldr; a.ldo = ldo; a.ldf = ldf; a.res_is_f32 = res_is_f32; a.res_first = res_first; a.n_store = out ? n_store : 0;
-    a.t_col0 = out_t ? t_col0 : N; a.t_rows = t_rows > 0 ? t_rows : 1; a.t_ld = t_ld;
-    a.tiles_m = a.tiles_n = 0;
-    a.dbg = g_debug_skip;
-    a.trace = nullptr; a.cstate = nullptr; a.ldc = 0; a.ksplit = 1; a.nk_split = 0; a.ws = nullptr; a.ws_plane = 0; a.ldws = 0; a.tile_order = 0;
-    a.sk_ws = nullptr; a.sk_count = nullptr; a.sk_ws_bytes = 0; a.sk_tiles = 0;
-    a.ln_stats = nullptr; a.ln_np = 0; a.ln_c = nullptr; a.rs_stats = nullptr; a.rs_np = 0; a.rs_gamma = nullptr; a.rs_beta = nullptr; a.st_out = nullptr; a.ln_eps = 0.f;
-    a.M = M; a.N = N; a.K = taps * Cp; a.Cp = Cp; a.taps = taps; a.stride = stride; a.pad = pad; a.Lin = Lin; a.Lout = Lout;
-    const bool split = dtype == EMAGE_F16X3 || dtype == EMAGE_H2;
-    a.a_scale = split ? a_scale : 1.f;
-    a.o_scale = split ? 1.f / (a_scale * w_scale) : 1.f;
-    a.h2s = emage_dev::H2_SCALE; a.h2i = emage_dev::H2_INV;
-    return 0;
-}
-
 // the LayerNorm-fold fields of an emage_gemm_problem (include/emage_hip.h) -> GemmArgs; EMAGE_H2 only
 int apply_fold(int dtype, GemmArgs& a, const emage_gemm_problem& q) {
     if (!q.ln_stats && !q.rs_stats && !q.st_out) return 0;
@@ -376,28 +328,55 @@ int apply_fold(int dtype, GemmArgs& a, const emage_gemm_problem& q) {
     return 0;
 }
 
+// the checks of emage_gemm / emage_gemm_ws / emage_gemm_grouped: one problem (include/emage_hip.h) -> the kernels' argument block
+int make_args(GemmArgs& a, int dtype, const emage_dev::H2Scale& hs, const emage_gemm_problem& q) {
+    const int M = q.M, N = q.N, Cp = q.Cp, taps = q.taps, lda = q.lda;
+    const int epc = dtype == EMAGE_BF16 ? 8 : 4;
+    if (!q.A || !q.W || M <= 0 || N <= 0 || taps <= 0 || Cp <= 0 || Cp % 64 != 0) return EMAGE_EINVAL;
+    if (dtype != EMAGE_BF16 && dtype != EMAGE_F32 && dtype != EMAGE_F16X3 && dtype != EMAGE_H2) return EMAGE_EINVAL;
+    if (dtype == EMAGE_H2) {       // 32-byte groups of 8 logical columns: every row of every h2 operand starts on a group
+        if (lda % 8 || (q.res && q.ldr % (q.res_is_f32 ? 4 : 8)) || (q.res && ((uintptr_t)q.res & 15))) return EMAGE_EINVAL;
+        const int row_cols = q.out_t ? q.t_col0 : N;
+        if (q.out && (q.ldo % 8 || ((uintptr_t)q.out & 15) || q.ldo < (((row_cols > q.n_store ? row_cols : q.n_store) + 7) & ~7))) return EMAGE_EINVAL;
+        if ((q.bias && ((uintptr_t)q.bias & 15)) || (q.slope && ((uintptr_t)q.slope & 15))) return EMAGE_EINVAL;
+    }
+    if (lda % epc != 0 || lda < Cp) return EMAGE_EINVAL;                 // 16-byte aligned operand rows
+    if (((uintptr_t)q.A | (uintptr_t)q.W) & 15) return EMAGE_EINVAL;
+    if (q.Lout <= 0 || q.Lin <= 0 || M % q.Lout != 0 || q.stride <= 0) return EMAGE_EINVAL;
+    if (!q.out && !q.out_f32 && !q.out_t) return EMAGE_EINVAL;
+    if (q.out_t && (q.t_rows <= 0 || M % q.t_rows != 0 || q.t_ld < q.t_rows || q.t_col0 < 0 || q.t_col0 > N)) return EMAGE_EINVAL;
+    if ((dtype == EMAGE_F16X3 || dtype == EMAGE_H2) && !(q.a_scale > 0.f && q.w_scale > 0.f)) return EMAGE_EINVAL;
+    {   // operands are addressed through 32-bit buffer offsets: each must span less than 2 GiB (the host splits larger batches)
+        const long es = dtype == EMAGE_BF16 ? 2 : 4;
+        const long a_span = ((((long)(M / q.Lout)) * q.Lin - 1) * lda + Cp + (long)q.pad * lda) * es;
+        if (a_span >= (1L << 31) || (long)N * taps * Cp * es >= (1L << 31)) return EMAGE_EINVAL;
+    }
+    a = GemmArgs{};                // every optional field off: no trace, cell state, split-K, workspace, fold; XCD-aware tile order
+    a.A = q.A; a.W = q.W; a.bias = q.bias; a.slope = q.slope; a.res = q.res; a.out = q.out; a.out_f32 = q.out_f32; a.out_t = q.out_t;
+    a.lda = lda; a.ldr = q.ldr; a.ldo = q.ldo; a.ldf = q.ldf; a.res_is_f32 = q.res_is_f32; a.res_first = q.res_first; a.n_store = q.out ? q.n_store : 0;
+    a.t_col0 = q.out_t ? q.t_col0 : N; a.t_rows = q.t_rows > 0 ? q.t_rows : 1; a.t_ld = q.t_ld;
+    a.dbg = g_debug_skip;
+    a.ksplit = 1;
+    a.M = M; a.N = N; a.K = taps * Cp; a.Cp = Cp; a.taps = taps; a.stride = q.stride; a.pad = q.pad; a.Lin = q.Lin; a.Lout = q.Lout;
+    const bool split = dtype == EMAGE_F16X3 || dtype == EMAGE_H2;
+    a.a_scale = split ? q.a_scale : 1.f;
+    a.o_scale = split ? 1.f / (q.a_scale * q.w_scale) : 1.f;
+    a.h2s = hs.s; a.h2i = hs.inv;
+    const int rf = apply_fold(dtype, a, q);
+    if (rf) return rf;
+    if (q.sk_ws && q.sk_count && dtype == EMAGE_H2) {      // split-K fix-up workspace (optional: the dispatch decides)
+        if (((uintptr_t)q.sk_ws & 15) || q.sk_ws_bytes <= 0 || q.sk_tiles <= 0) return EMAGE_EINVAL;
+        a.sk_ws = (float*)q.sk_ws; a.sk_count = q.sk_count; a.sk_ws_bytes = q.sk_ws_bytes; a.sk_tiles = q.sk_tiles;
+    }
+    return 0;
+}
+
 int dispatch_one(int dtype, GemmArgs& a, hipStream_t s) {
     if (dtype == EMAGE_H2) return gemm_h2_dispatch(a, s);
     if (dtype == EMAGE_F16X3) return dispatch<float, true>(a, s);
     return dtype == EMAGE_BF16 ? dispatch<bf16_t, false>(a, s) : dispatch<float, false>(a, s);
 }
 }  // namespace
-
-extern "C" int emage_gemm(int dtype, const void* A, int lda, const void* W, const float* bias, const float* slope,
-                          const void* res, int ldr, int res_is_f32, int res_first,
-                          void* out, int ldo, int n_store, float* out_f32, int ldf,
-                          void* out_t, int t_col0, int t_rows, int t_ld,
-                          int M, int N, int Cp, int taps, int stride, int pad, int Lin, int Lout,
-                          float a_scale, float w_scale, void* stream) {
-    GemmArgs a;
-    emage_dev::H2Scale hs;
-    if (emage_dev::h2_dtype(dtype, hs)) return EMAGE_EINVAL;
-    const int rc = make_args(a, dtype, A, lda, W, bias, slope, res, ldr, res_is_f32, res_first, out, ldo, n_store, out_f32, ldf, out_t, t_col0, t_rows, t_ld,
-                             M, N, Cp, taps, stride, pad, Lin, Lout, a_scale, w_scale);
-    if (rc) return rc;
-    a.h2s = hs.s; a.h2i = hs.inv;
-    return dispatch_one(dtype, a, (hipStream_t)stream);
-}
 
 // emage_gemm with a caller-owned workspace: a split-K contraction (EMAGE_H2: bare weight-gradient shapes, see gemm_h2.hip) stores its
 // K-slices' partial tiles as planes of the workspace and sums them in slice order with a second launch — no atomics, bit-reproducible.
@@ -407,19 +386,31 @@ extern "C" int emage_gemm_ws(int dtype, const void* A, int lda, const void* W, c
                              void* out_t, int t_col0, int t_rows, int t_ld,
                              int M, int N, int Cp, int taps, int stride, int pad, int Lin, int Lout,
                              float a_scale, float w_scale, void* workspace, size_t workspace_bytes, void* stream) {
+    const emage_gemm_problem q{.A = A, .W = W, .bias = bias, .slope = slope, .res = res, .out = out, .out_f32 = out_f32, .out_t = out_t,
+                               .lda = lda, .ldr = ldr, .res_is_f32 = res_is_f32, .res_first = res_first, .ldo = ldo, .n_store = n_store, .ldf = ldf,
+                               .t_col0 = t_col0, .t_rows = t_rows, .t_ld = t_ld, .M = M, .N = N, .Cp = Cp, .taps = taps, .stride = stride, .pad = pad,
+                               .Lin = Lin, .Lout = Lout, .a_scale = a_scale, .w_scale = w_scale};      // no fold, no fix-up workspace
     GemmArgs a;
     emage_dev::H2Scale hs;
     if (emage_dev::h2_dtype(dtype, hs)) return EMAGE_EINVAL;
-    const int rc = make_args(a, dtype, A, lda, W, bias, slope, res, ldr, res_is_f32, res_first, out, ldo, n_store, out_f32, ldf, out_t, t_col0, t_rows, t_ld,
-                             M, N, Cp, taps, stride, pad, Lin, Lout, a_scale, w_scale);
+    const int rc = make_args(a, dtype, hs, q);
     if (rc) return rc;
-    a.h2s = hs.s; a.h2i = hs.inv;
     if (workspace && (((uintptr_t)workspace & 15) || workspace_bytes < 16)) return EMAGE_EINVAL;
     if (workspace && dtype == EMAGE_H2) {
         a.ws = (float*)workspace;
         a.ws_plane = (long)(workspace_bytes / sizeof(float));       // the dispatch turns the capacity (in floats) into the plane stride it uses
     }
     return dispatch_one(dtype, a, (hipStream_t)stream);
+}
+
+extern "C" int emage_gemm(int dtype, const void* A, int lda, const void* W, const float* bias, const float* slope,
+                          const void* res, int ldr, int res_is_f32, int res_first,
+                          void* out, int ldo, int n_store, float* out_f32, int ldf,
+                          void* out_t, int t_col0, int t_rows, int t_ld,
+                          int M, int N, int Cp, int taps, int stride, int pad, int Lin, int Lout,
+                          float a_scale, float w_scale, void* stream) {
+    return emage_gemm_ws(dtype, A, lda, W, bias, slope, res, ldr, res_is_f32, res_first, out, ldo, n_store, out_f32, ldf, out_t, t_col0, t_rows, t_ld,
+                         M, N, Cp, taps, stride, pad, Lin, Lout, a_scale, w_scale, nullptr, 0, stream);
 }
 
 namespace {
@@ -430,18 +421,8 @@ int grouped(int dtype, const emage_gemm_problem* problems, int n_problems, hipSt
     if (emage_dev::h2_dtype(dtype, hs)) return EMAGE_EINVAL;
     GemmArgs args[MAX_PROBLEMS];
     for (int i = 0; i < n_problems; ++i) {         // every problem is checked before the first launch
-        const emage_gemm_problem& q = problems[i];
-        const int rc = make_args(args[i], dtype, q.A, q.lda, q.W, q.bias, q.slope, q.res, q.ldr, q.res_is_f32, q.res_first, q.out, q.ldo, q.n_store,
-                                 q.out_f32, q.ldf, q.out_t, q.t_col0, q.t_rows, q.t_ld, q.M, q.N, q.Cp, q.taps, q.stride, q.pad, q.Lin, q.Lout,
-                                 q.a_scale, q.w_scale);
+        const int rc = make_args(args[i], dtype, hs, problems[i]);
         if (rc) return rc;
-        args[i].h2s = hs.s; args[i].h2i = hs.inv;
-        const int rf = apply_fold(dtype, args[i], q);
-        if (rf) return rf;
-        if (q.sk_ws && q.sk_count && dtype == EMAGE_H2) {      // split-K fix-up workspace (optional: the dispatch decides)
-            if (((uintptr_t)q.sk_ws & 15) || q.sk_ws_bytes <= 0 || q.sk_tiles <= 0) return EMAGE_EINVAL;
-            args[i].sk_ws = (float*)q.sk_ws; args[i].sk_count = q.sk_count; args[i].sk_ws_bytes = q.sk_ws_bytes; args[i].sk_tiles = q.sk_tiles;
-        }
     }
     if (dtype == EMAGE_H2) return gemm_h2_dispatch_group(args, n_problems, s, count_only);
     if (count_only) return n_problems;

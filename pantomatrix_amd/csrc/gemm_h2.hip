@@ -22,21 +22,148 @@ namespace {
 
 using namespace emage_dev;
 
-template <int BM, int BN, int WM, int WN, int NS, int NLW, bool PIPE, bool PRE, int OCC, bool DILV, bool TRACE, int KPB = 1, bool LNF = false, bool SKF = false>
-__global__ __launch_bounds__((WM * WN + NLW) * 64, OCC * (WM * WN + NLW) / 4) void gemm_h2_kernel(GemmArgs p) {
-    __shared__ __attribute__((aligned(128))) unsigned char smem[h2_smem_bytes<BM, BN, NS, KPB>()];
-    // XCD-aware tile order (gemm.hip): each XCD walks a contiguous run of tiles; split-K: slice s = blockIdx / tiles
+// One tile configuration: what gemm_h2_tile (h2_tile.h) takes as template arguments, by name
+struct H2Tile {
+    int bm, bn;                  // block tile
+    int wm = 2, wn = 2;          // grid of compute waves (wave tile bm / wm x bn / wn)
+    int ns = 3;                  // ring depth in K-tiles
+    int nlw = 0;                 // loader waves
+    bool pipe = false;           // register-pipelined K-loop
+    bool pre = false;            // residual fetched ahead of the K-loop
+    int occ = 1;                 // resident blocks per CU the launch bounds ask for, in blocks of 4 waves
+    bool dilv = false;           // DMA issue interleaved with the MFMAs
+    bool trace = false;          // phase tracer
+    int kpb = 1;                 // K-tiles per ring slot and barrier
+    bool lnf = false;            // the LayerNorm-fold paths (GemmArgs::ln_stats / rs_stats / st_out)
+    constexpr int waves() const { return wm * wn + nlw; }
+    constexpr int threads() const { return waves() * 64; }
+};
+enum : int { GROUP = 1, FIXUP = 2 };
+struct H2Row {
+    int id;
+    H2Tile t;
+    int flags = 0;               // GROUP: has a grouped kernel (emage_gemm_grouped); FIXUP: has the split-K form with the in-kernel fix-up (SKF)
+};
+
+// THE tile configurations (id: block tile, compute-wave grid [wave tile], ring depth, loader waves, K-loop form); every launcher, kernel and
+// predicate below takes its row from here.  The product library carries the rows the heuristics select; the rest are the tools build's
+constexpr H2Row H2_CONFIGS[] = {
+    {100, {.bm = 64, .bn = 192, .wm = 4, .ns = 2}, GROUP},                    // 8 waves 16x96 (the F16X3 shape)
+    {170, {.bm = 128, .bn = 192, .wn = 4, .ns = 2}, GROUP},                   // 8 waves 64x48: grids of many tiles per CU (round 4)
+    {113, {.bm = 128, .bn = 128, .wm = 4}, GROUP},
+    {119, {.bm = 128, .bn = 256, .wm = 4, .ns = 2}, GROUP},                   // 8 waves 32x128
+    {120, {.bm = 64, .bn = 64, .occ = 2}, GROUP | FIXUP},                     // 768-wide / small outputs: 4 waves 32x32, three blocks per CU
+    // the same two tiles WITH the LayerNorm-fold paths (GemmArgs::ln_stats / rs_stats / st_out; round 6): taken only by launches that fold
+    {1100, {.bm = 64, .bn = 192, .wm = 4, .ns = 2, .lnf = true}, GROUP},
+    {1120, {.bm = 64, .bn = 64, .occ = 2, .lnf = true}, GROUP | FIXUP},
+#ifdef EMAGE_TOOLS
+    {101, {.bm = 64, .bn = 192, .wm = 4}},
+    {102, {.bm = 64, .bn = 192, .wn = 4}},                                    // 8 waves 32x48
+    {103, {.bm = 64, .bn = 192, .pipe = true}},                               // 4 waves 32x96, pipelined
+    {104, {.bm = 64, .bn = 192, .ns = 4, .pipe = true}},
+    {105, {.bm = 64, .bn = 192, .nlw = 4, .pipe = true}},                     // 4 compute + 4 loader waves
+    {106, {.bm = 64, .bn = 192, .nlw = 4}},
+    {107, {.bm = 64, .bn = 192, .wn = 4, .nlw = 4}},                          // 8 compute (32x48) + 4 loaders
+    {108, {.bm = 128, .bn = 96, .wm = 4, .wn = 1, .pipe = true}},             // 4 waves 32x96
+    {109, {.bm = 128, .bn = 96, .wm = 4, .wn = 1, .nlw = 4, .pipe = true}},
+    {110, {.bm = 128, .bn = 96, .wm = 4, .nlw = 4}},                          // 8 compute 32x48 + 4 loaders
+    {111, {.bm = 128, .bn = 128, .pipe = true}},                              // 4 waves 64x64
+    {112, {.bm = 128, .bn = 128, .wm = 4, .ns = 2}},                          // 8 waves 32x64
+    {115, {.bm = 128, .bn = 192, .pipe = true}},                              // 4 waves 64x96
+    {116, {.bm = 128, .bn = 192, .wm = 4}},                                   // 8 waves 32x96
+    {118, {.bm = 128, .bn = 256, .pipe = true}},                              // 4 waves 64x128
+    {188, {.bm = 64, .bn = 64, .ns = 8}},                                     // round 5 (negative): a LONE block per CU with a ring of 8 for grids of at most one tile per CU
+    {189, {.bm = 64, .bn = 64, .wn = 4}},                                     // round 5: the same tile on 8 waves of 32 x 16 (2 DMA instructions per wave and K-tile instead of 4)
+    {121, {.bm = 64, .bn = 64, .pipe = true, .occ = 2}},
+    {122, {.bm = 64, .bn = 128, .pipe = true}},                               // 4 waves 32x64
+    {123, {.bm = 128, .bn = 64, .wm = 4, .wn = 1, .pipe = true}},             // 4 waves 32x64
+    {124, {.bm = 64, .bn = 96, .pipe = true, .occ = 2}},                      // 4 waves 32x48
+    {125, {.bm = 64, .bn = 192, .pipe = true, .pre = true}},                  // 103 + residual prefetch
+    {126, {.bm = 64, .bn = 192, .nlw = 4, .pre = true}},                      // 106 + residual prefetch
+    {127, {.bm = 128, .bn = 96, .wm = 4, .wn = 1, .pipe = true, .pre = true}},// 108 + residual prefetch
+    {128, {.bm = 64, .bn = 192, .wm = 4, .pre = true}},                       // 101 + residual prefetch
+    {129, {.bm = 128, .bn = 96, .wm = 4, .wn = 1, .ns = 4, .pipe = true, .pre = true}},
+    {130, {.bm = 64, .bn = 64, .ns = 2, .occ = 3}},
+    {131, {.bm = 128, .bn = 128, .wm = 4, .nlw = 4}},                         // 8 compute 32x64 + 4 loaders
+    {132, {.bm = 128, .bn = 192, .wm = 4, .nlw = 4}},                         // 8 compute 32x96 + 4 loaders
+    // DMA issue interleaved with the MFMAs (DILV)
+    {140, {.bm = 64, .bn = 192, .wm = 4, .ns = 2, .dilv = true}},
+    {141, {.bm = 64, .bn = 192, .wm = 4, .dilv = true}},
+    {142, {.bm = 64, .bn = 192, .wn = 4, .dilv = true}},
+    {143, {.bm = 64, .bn = 192, .pipe = true, .dilv = true}},
+    {144, {.bm = 64, .bn = 192, .wm = 4, .pipe = true, .dilv = true}},        // 8 waves, pipelined fragments + interleaved DMA
+    {145, {.bm = 128, .bn = 128, .wm = 4, .dilv = true}},
+    {146, {.bm = 128, .bn = 128, .wm = 4, .pipe = true, .dilv = true}},
+    {147, {.bm = 128, .bn = 192, .wm = 4, .dilv = true}},
+    {148, {.bm = 128, .bn = 192, .wm = 4, .pipe = true, .dilv = true}},
+    {149, {.bm = 128, .bn = 256, .wm = 4, .ns = 2, .dilv = true}},
+    {150, {.bm = 64, .bn = 64, .ns = 2, .occ = 3, .dilv = true}},
+    {151, {.bm = 64, .bn = 64, .occ = 2, .dilv = true}},
+    {152, {.bm = 128, .bn = 64, .wm = 4, .dilv = true}},                      // 8 waves 32x32
+    {153, {.bm = 64, .bn = 128, .wn = 4, .dilv = true}},                      // 8 waves 32x32
+    {155, {.bm = 64, .bn = 192, .wm = 4, .ns = 4, .dilv = true}},
+    {156, {.bm = 128, .bn = 128, .wn = 4, .dilv = true}},                     // 8 waves 64x32
+    // round 4: FEWER waves with larger wave tiles (LDS fragment bytes per MFMA fall with the wave tile: a 32x32 wave tile reads 8 KB per
+    // 12 MFMAs, a 64x48 one 14 KB per 36), several blocks per CU
+    {160, {.bm = 64, .bn = 96, .wm = 1, .occ = 2}, GROUP},                    // 2 waves 64x48, two blocks per CU
+    {161, {.bm = 64, .bn = 96, .wm = 1, .pipe = true, .occ = 2}, GROUP},
+    {162, {.bm = 64, .bn = 64, .wm = 1, .occ = 3}, GROUP},                    // 2 waves 64x32, three blocks per CU
+    {163, {.bm = 64, .bn = 64, .wn = 1, .occ = 3}, GROUP},                    // 2 waves 32x64
+    {164, {.bm = 64, .bn = 64, .wm = 1, .wn = 1, .pipe = true, .occ = 3}, GROUP},// 1 wave 64x64, pipelined
+    {165, {.bm = 64, .bn = 64, .wm = 1, .wn = 1, .occ = 3}},
+    {166, {.bm = 128, .bn = 96}},                                             // 4 waves 64x48, one block per CU
+    {167, {.bm = 128, .bn = 96, .pipe = true}},
+    {168, {.bm = 64, .bn = 192, .wm = 1, .wn = 4}},                           // 4 waves 64x48 side by side
+    {169, {.bm = 64, .bn = 192, .wm = 1, .wn = 4, .pipe = true}},
+    {171, {.bm = 128, .bn = 256, .wn = 4, .ns = 2}},                          // 8 waves 64x64
+    // round 5: one fat block per CU for grids of many tiles per CU (the K / V projections of all cross-attention layers): MFMA issue per K-tile
+    // 3-4x the operand delivery (64 B/clk per CU)
+    {172, {.bm = 256, .bn = 256, .wn = 4, .ns = 2}},                          // 8 waves 128x64
+    {173, {.bm = 256, .bn = 192, .wn = 4, .ns = 2}},                          // 8 waves 128x48
+    {174, {.bm = 256, .bn = 192, .wm = 4, .ns = 2}},                          // 8 waves 64x96
+    {175, {.bm = 256, .bn = 128, .wm = 4, .ns = 2}},                          // 8 waves 64x64
+    {187, {.bm = 64, .bn = 64, .pre = true, .occ = 2}},                       // 120 with the residual fetched ahead of the K-loop
+    // round 5 (VERDICT next #1b, "BK = 64"): TWO K-tiles per ring slot and barrier (KPB = 2), otherwise the shipped configurations
+    {180, {.bm = 64, .bn = 192, .wm = 4, .ns = 2, .kpb = 2}},                 // 100 with 128 KB of LDS: one block per CU
+    {181, {.bm = 128, .bn = 192, .wn = 4, .ns = 2, .kpb = 2}},                // 170 with 160 KB: one block per CU instead of two
+    {183, {.bm = 64, .bn = 64, .ns = 2, .occ = 2, .kpb = 2}},                 // 120 with a ring of 2 x 32 KB: two blocks per CU
+    {184, {.bm = 128, .bn = 128, .wm = 4, .ns = 2, .kpb = 2}},                // 113 with a ring of 2 x 64 KB
+    {185, {.bm = 64, .bn = 128, .wn = 4, .ns = 2, .kpb = 2}},                 // 8 waves 32x32, 96 KB
+    {186, {.bm = 64, .bn = 64, .kpb = 2}},                                    // 120's ring of 3, 96 KB: one block per CU
+    // instrumented twins (TRACE) of 101 / 103 / 105 / 141
+    {201, {.bm = 64, .bn = 192, .wm = 4, .trace = true}},
+    {203, {.bm = 64, .bn = 192, .pipe = true, .trace = true}},
+    {205, {.bm = 64, .bn = 192, .nlw = 4, .pipe = true, .trace = true}},
+    {241, {.bm = 64, .bn = 192, .wm = 4, .dilv = true, .trace = true}},
+#endif
+};
+static_assert(unique_config_ids<H2_CONFIGS>(), "one row per id");
+constexpr bool h2_rows_consistent() {
+    for (const H2Row& r : H2_CONFIGS) {
+        if ((r.flags & (GROUP | FIXUP)) && (r.t.kpb != 1 || r.t.trace)) return false;      // launch_h2_group / launch_h2_skf check no K-tile parity and pass no trace buffer
+        if ((r.flags & FIXUP) && (r.t.bm != 64 || r.t.bn != 64)) return false;            // h2_skf_slices plans 64 x 64 tiles
+    }
+    return true;
+}
+static_assert(h2_rows_consistent(), "a GROUP / FIXUP row the grouped or fix-up launch cannot run");
+static const H2Row* h2_row(int id) {
+    for (const H2Row& r : H2_CONFIGS) if (r.id == id) return &r;
+    return nullptr;
+}
+
+template <H2Tile C, bool SKF>
+__global__ __launch_bounds__(C.waves() * 64, C.occ * C.waves() / 4) void gemm_h2_kernel(GemmArgs p) {
+    __shared__ __attribute__((aligned(128))) unsigned char smem[h2_smem_bytes<C.bm, C.bn, C.ns, C.kpb>()];
+    // XCD-aware tile order (gemm_tile.h): each XCD walks a contiguous run of tiles; split-K: slice s = blockIdx / tiles
     const int nblk = p.tiles_m * p.tiles_n;
     const int split = p.ksplit > 1 ? (int)blockIdx.x / nblk : 0;
     int bid = (int)blockIdx.x - split * nblk;
-    if (p.tile_order == 0 && !EMAGE_DBG(p, 32)) {     // (tools: emage_set_tuning key 1 bit 32, tools/prof_traffic_calib.py: dispatch order for every launch)
-        const int q = nblk >> 3, r = nblk & 7, xcd = bid & 7, idx = bid >> 3;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
+    if (p.tile_order == 0 && !EMAGE_DBG(p, 32)) bid = xcd_run_order(bid, nblk);     // (tools: emage_set_tuning key 1 bit 32, tools/prof_traffic_calib.py: dispatch order for every launch)
     int tile_n = bid % p.tiles_n, tile_m = bid / p.tiles_n;
     if (EMAGE_DBG(p, 64)) { tile_m = bid % p.tiles_m; tile_n = bid / p.tiles_m; }      // tools: an XCD's run walks M first (it owns a slice of N: A re-fetched per XCD, W once)
-    gemm_h2_tile<BM, BN, WM, WN, NS, NLW, PIPE, PRE, DILV, TRACE, KPB, LNF, SKF>(p, tile_m * BM, tile_n * BN, smem, split);
+    gemm_h2_tile<C.bm, C.bn, C.wm, C.wn, C.ns, C.nlw, C.pipe, C.pre, C.dilv, C.trace, C.kpb, C.lnf, SKF>(p, tile_m * C.bm, tile_n * C.bn, smem, split);
 }
+
 
 // most tiles a split-K launch may have: 100.  Measured on the captured training step (A/Bs on one box each, tools library variants):
 //   * 384 instead of 191 (the 768 x 1536 FFN weight gradients: 288 tiles -> two slices of 576 blocks): 105.2 -> 109.6 ms
@@ -87,22 +214,20 @@ static inline int h2_cus() { const int c = device_cus(); return c > 0 ? c : 256;
 
 // block slots of the chip for a tile configuration (LDS-bound residency x CUs of the current device): what a split-K launch should fill.
 // The count only steers how many K-slices are cut, never correctness
-template <int BM, int BN, int NS, int THREADS, int KPB = 1>
+template <H2Tile C>
 int h2_block_slots() {
-    constexpr int by_lds = (160 * 1024) / h2_smem_bytes<BM, BN, NS, KPB>();
-    constexpr int by_waves = 32 / (THREADS / 64);
+    constexpr int by_lds = (160 * 1024) / h2_smem_bytes<C.bm, C.bn, C.ns, C.kpb>();
+    constexpr int by_waves = 32 / C.waves();
     return h2_cus() * (by_lds < by_waves ? (by_lds < 1 ? 1 : by_lds) : by_waves);
 }
 
-template <int BM, int BN, int WM, int WN, int NS, int NLW, bool PIPE, bool PRE = false, int OCC = 1, bool DILV = false, bool TRACE = false, int KPB = 1, bool LNF = false>
+template <H2Tile C>
 int launch_h2(GemmArgs& a, hipStream_t s) {
-    if (!LNF && (a.ln_stats || a.rs_stats || a.st_out)) return EMAGE_EINVAL;      // only the LNF instantiations know the LayerNorm-fold fields
-    if (a.out_t && a.t_col0 % BN != 0) return EMAGE_EINVAL;      // a tile is either row-major or transposed
-    if (KPB > 1 && (a.K / 32) % KPB != 0) return EMAGE_EINVAL;   // a ring slot holds KPB whole K-tiles: an odd count would drop the last one
-    a.tiles_m = (a.M + BM - 1) / BM;
-    const int ncols = a.n_store > a.N ? a.n_store : a.N;
-    a.tiles_n = (ncols + BN - 1) / BN;
-    a.trace = TRACE ? g_h2_trace : nullptr;
+    if (!C.lnf && (a.ln_stats || a.rs_stats || a.st_out)) return EMAGE_EINVAL;      // only the LNF rows know the LayerNorm-fold fields
+    if (a.out_t && a.t_col0 % C.bn != 0) return EMAGE_EINVAL;      // a tile is either row-major or transposed
+    if (C.kpb > 1 && (a.K / 32) % C.kpb != 0) return EMAGE_EINVAL;   // a ring slot holds KPB whole K-tiles: an odd count would drop the last one
+    set_tile_grid(a, C.bm, C.bn);
+    a.trace = C.trace ? g_h2_trace : nullptr;
     // Tile order (round 5, profiles/r05_traffic_calibration.txt, r05_gemm_h2_tile_order_ab.txt).  XCD-aware runs keep an XCD's W panels in ITS L2 — as long
     // as W fits the eight 4 MB L2s next to the A panels.  The K / V projection of all cross-attention layers (W = 12 288 x 768 x 4 B = 37.7 MB) does not:
     // a strip-shaped run shares an A panel among its 64 concurrent blocks and a W panel among none (1 233 MB over the fabric, 3.9x the model); in
@@ -126,7 +251,7 @@ int launch_h2(GemmArgs& a, hipStream_t s) {
     if (bare && ws && !(g_h2_variant & 16384)) {      // tools A/B: bit 16384 = ignore the workspace (the atomic form)
         // two-pass split-K (emage_gemm_ws): as many K-slices as fill the chip's block slots ONCE, each slice >= 16 K-tiles, partial tiles as
         // planes of the workspace.  Cheap enough (plain stores + one streaming pass) to use up to twice the tile count of the atomic form
-        const int SLOTS = h2_block_slots<BM, BN, NS, (WM * WN + NLW) * 64, KPB>();
+        const int SLOTS = h2_block_slots<C>();
         const int ldws = (a.N + 3) & ~3;
         const long plane = ((long)a.M * ldws + 3) & ~3L;
         int want = (int)(SLOTS / tiles);
@@ -167,16 +292,13 @@ int launch_h2(GemmArgs& a, hipStream_t s) {
             }
         }
     }
-    if (reduce) {
-        hipLaunchKernelGGL((gemm_h2_kernel<BM, BN, WM, WN, NS, NLW, PIPE, PRE, OCC, DILV, TRACE, KPB, LNF>), dim3(a.tiles_m * a.tiles_n * a.ksplit), dim3((WM * WN + NLW) * 64), 0, s, a);
-        const int rc = launch_status();
-        if (rc) return rc;
-        const long quads = (long)a.M * ((a.N + 3) >> 2);
-        hipLaunchKernelGGL(h2_splitk_reduce_kernel, dim3((unsigned)((quads + 255) / 256)), dim3(256), 0, s, (const float*)a.ws, a.ws_plane, a.ldws, a.ksplit,
-                           a.out_f32, a.ldf, a.M, a.N, accumulate ? 1 : 0);
-        return launch_status();
-    }
-    hipLaunchKernelGGL((gemm_h2_kernel<BM, BN, WM, WN, NS, NLW, PIPE, PRE, OCC, DILV, TRACE, KPB, LNF>), dim3(a.tiles_m * a.tiles_n * a.ksplit), dim3((WM * WN + NLW) * 64), 0, s, a);
+    hipLaunchKernelGGL((gemm_h2_kernel<C, false>), dim3(a.tiles_m * a.tiles_n * a.ksplit), dim3(C.threads()), 0, s, a);
+    if (!reduce) return launch_status();
+    const int rc = launch_status();
+    if (rc) return rc;
+    const long quads = (long)a.M * ((a.N + 3) >> 2);
+    hipLaunchKernelGGL(h2_splitk_reduce_kernel, dim3((unsigned)((quads + 255) / 256)), dim3(256), 0, s, (const float*)a.ws, a.ws_plane, a.ldws, a.ksplit,
+                       a.out_f32, a.ldf, a.M, a.N, accumulate ? 1 : 0);
     return launch_status();
 }
 
@@ -186,8 +308,7 @@ int launch_h2(GemmArgs& a, hipStream_t s) {
 // output form, the LayerNorm fold).  The 64 x 64 tile only.  Returns < 0: not applicable (the caller launches the plain form).
 static int h2_skf_slices(const GemmArgs& a, int* per_out) {
     if (!a.sk_ws || !a.sk_count) return -1;
-    const int ncols = a.n_store > a.N ? a.n_store : a.N;
-    const long tiles = (long)((a.M + 63) / 64) * ((ncols + 63) / 64);
+    const long tiles = tile_count(a, 64, 64);
     const int nk_all = a.K / 32;
     if (tiles > 128 || tiles > a.sk_tiles || nk_all < 8) return -1;
     int want = (int)((h2_cus() + tiles - 1) / tiles);          // ~one block per CU
@@ -200,37 +321,33 @@ static int h2_skf_slices(const GemmArgs& a, int* per_out) {
     *per_out = per;
     return ksplit;
 }
-
-template <bool LNF>
+template <H2Tile C>
 int launch_h2_skf(GemmArgs& a, int ksplit, int per, hipStream_t s) {
-    if (a.out_t && a.t_col0 % 64 != 0) return EMAGE_EINVAL;
-    a.tiles_m = (a.M + 63) / 64;
-    const int ncols = a.n_store > a.N ? a.n_store : a.N;
-    a.tiles_n = (ncols + 63) / 64;
+    if (a.out_t && a.t_col0 % C.bn != 0) return EMAGE_EINVAL;
+    set_tile_grid(a, C.bm, C.bn);
     a.trace = nullptr;
     a.tile_order = 0;
     a.ws = nullptr; a.ws_plane = 0; a.ldws = 0;
     a.ksplit = ksplit; a.nk_split = per;
-    hipLaunchKernelGGL((gemm_h2_kernel<64, 64, 2, 2, 3, 0, false, false, 2, false, false, 1, LNF, true>), dim3(a.tiles_m * a.tiles_n * ksplit), dim3(256), 0, s, a);
+    hipLaunchKernelGGL((gemm_h2_kernel<C, true>), dim3(a.tiles_m * a.tiles_n * ksplit), dim3(C.threads()), 0, s, a);
     return launch_status();
 }
+
 
 // ---- grouped launch: several independent problems of ONE tile configuration in one grid (emage_gemm_grouped) ----
 // The argument block carries the problems by value (kernarg segment: no device table to allocate); a block finds its problem by
 // comparing its (XCD-remapped) id with the running tile counts — scalar work — and then runs the unchanged tile routine on that
 // problem's arguments: the result is bit for bit that of the single-problem launch.
 
-template <int BM, int BN, int WM, int WN, int NS, int NLW, bool PIPE, bool PRE, int OCC, bool DILV, bool LNF = false>
-__global__ __launch_bounds__((WM * WN + NLW) * 64, OCC * (WM * WN + NLW) / 4) void gemm_h2_group_kernel(GroupArgs g) {
-    __shared__ __attribute__((aligned(128))) unsigned char smem[h2_smem_bytes<BM, BN, NS>()];
+
+template <H2Tile C>
+__global__ __launch_bounds__(C.waves() * 64, C.occ * C.waves() / 4) void gemm_h2_group_kernel(GroupArgs g) {
+    __shared__ __attribute__((aligned(128))) unsigned char smem[h2_smem_bytes<C.bm, C.bn, C.ns, C.kpb>()];
     // XCD-aware order over the WHOLE grid: each XCD walks a contiguous run of the concatenated tile list, i.e. mostly one problem
     // (its W panel stays in that XCD's L2)
-    int bid = (int)blockIdx.x;
-    {
-        const int nblk = g.total;
-        const int q = nblk >> 3, r = nblk & 7, xcd = bid & 7, idx = bid >> 3;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
+    const int bid = xcd_run_order((int)blockIdx.x, g.total);
+    // which problem is this block in (written out here, in gemm_h2_pp.hip and in qkv_attention.hip: moved into a shared function, the same scan
+    // makes the compiler number these kernels' scalar registers differently)
     int pi = 0;
 #pragma unroll
     for (int i = 0; i < MAXG - 1; ++i) pi += (i + 1 < g.n && bid >= g.tile_end[i]) ? 1 : 0;
@@ -238,148 +355,23 @@ __global__ __launch_bounds__((WM * WN + NLW) * 64, OCC * (WM * WN + NLW) / 4) vo
     const int t = bid - (pi ? g.tile_end[pi - 1] : 0);
     const GemmArgs& p = g.p[pi];
     const int tile_n = t % p.tiles_n, tile_m = t / p.tiles_n;
-    gemm_h2_tile<BM, BN, WM, WN, NS, NLW, PIPE, PRE, DILV, false, 1, LNF>(p, tile_m * BM, tile_n * BN, smem, 0);
-}
-
-template <int BM, int BN>
-void h2_tiles(GemmArgs& a) {
-    a.tiles_m = (a.M + BM - 1) / BM;
-    const int ncols = a.n_store > a.N ? a.n_store : a.N;
-    a.tiles_n = (ncols + BN - 1) / BN;
+    gemm_h2_tile<C.bm, C.bn, C.wm, C.wn, C.ns, C.nlw, C.pipe, C.pre, C.dilv, C.trace, C.kpb, C.lnf>(p, tile_m * C.bm, tile_n * C.bn, smem, 0);
 }
 
 // the split-K condition of launch_h2 (bare contractions with few tiles and a long K: the weight gradients of a training step)
-template <int BM, int BN>
-bool h2_wants_split_k(const GemmArgs& a) {
-    const long tiles = (long)((a.M + BM - 1) / BM) * (((a.n_store > a.N ? a.n_store : a.N) + BN - 1) / BN);
-    return h2_bare(a) && tiles <= h2_split_k_tiles();
-}
+static bool h2_wants_split_k(const GemmArgs& a, const H2Tile& c) { return h2_bare(a) && tile_count(a, c.bm, c.bn) <= h2_split_k_tiles(); }
 
-template <int BM, int BN, int WM, int WN, int NS, int NLW, bool PIPE, bool PRE = false, int OCC = 1, bool DILV = false, bool LNF = false>
+template <H2Tile C>
 int launch_h2_group(GemmArgs** a, int n, hipStream_t s) {
     GroupArgs g;
-    int total = 0;
-    for (int i = 0; i < n; ++i) {
-        GemmArgs& q = *a[i];
-        if (q.out_t && q.t_col0 % BN != 0) return EMAGE_EINVAL;
-        h2_tiles<BM, BN>(q);
-        q.trace = nullptr;
-        q.ksplit = 1;
-        total += q.tiles_m * q.tiles_n;
-        g.p[i] = q;
-        g.tile_end[i] = total;
-    }
-    for (int i = n; i < MAXG; ++i) { g.p[i] = *a[0]; g.tile_end[i] = total; }
-    g.n = n;
-    g.total = total;
-    hipLaunchKernelGGL((gemm_h2_group_kernel<BM, BN, WM, WN, NS, NLW, PIPE, PRE, OCC, DILV, LNF>), dim3(total), dim3((WM * WN + NLW) * 64), 0, s, g);
+    const int rc = fill_group(g, a, n, C.bm, C.bn);
+    if (rc) return rc;
+    hipLaunchKernelGGL((gemm_h2_group_kernel<C>), dim3(g.total), dim3(C.threads()), 0, s, g);
     return launch_status();
 }
 
-// Tile configurations (id: block tile, compute-wave grid [wave tile], ring depth, loader waves, register-pipelined K-loop)
-int run_config(int cfg, GemmArgs& a, hipStream_t s) {
-    switch (cfg) {
-        //                       BM   BN  WM WN NS NLW PIPE  PRE  OCC
-        case 100: return launch_h2<64, 192, 4, 2, 2, 0, false>(a, s);              // 8 waves 16x96 (the F16X3 shape)
-        case 170: return launch_h2<128, 192, 2, 4, 2, 0, false>(a, s);             // 8 waves 64x48: grids of many tiles per CU (round 4)
-#ifdef EMAGE_TOOLS
-        case 101: return launch_h2<64, 192, 4, 2, 3, 0, false>(a, s);
-        case 102: return launch_h2<64, 192, 2, 4, 3, 0, false>(a, s);              // 8 waves 32x48
-        case 103: return launch_h2<64, 192, 2, 2, 3, 0, true>(a, s);               // 4 waves 32x96, pipelined
-        case 104: return launch_h2<64, 192, 2, 2, 4, 0, true>(a, s);
-        case 105: return launch_h2<64, 192, 2, 2, 3, 4, true>(a, s);               // 4 compute + 4 loader waves
-        case 106: return launch_h2<64, 192, 2, 2, 3, 4, false>(a, s);
-        case 107: return launch_h2<64, 192, 2, 4, 3, 4, false>(a, s);              // 8 compute (32x48) + 4 loaders
-        case 108: return launch_h2<128, 96, 4, 1, 3, 0, true>(a, s);               // 4 waves 32x96
-        case 109: return launch_h2<128, 96, 4, 1, 3, 4, true>(a, s);
-        case 110: return launch_h2<128, 96, 4, 2, 3, 4, false>(a, s);              // 8 compute 32x48 + 4 loaders
-        case 111: return launch_h2<128, 128, 2, 2, 3, 0, true>(a, s);              // 4 waves 64x64
-        case 112: return launch_h2<128, 128, 4, 2, 2, 0, false>(a, s);             // 8 waves 32x64
-#endif
-        case 113: return launch_h2<128, 128, 4, 2, 3, 0, false>(a, s);
-#ifdef EMAGE_TOOLS
-        case 115: return launch_h2<128, 192, 2, 2, 3, 0, true>(a, s);              // 4 waves 64x96
-        case 116: return launch_h2<128, 192, 4, 2, 3, 0, false>(a, s);             // 8 waves 32x96
-        case 118: return launch_h2<128, 256, 2, 2, 3, 0, true>(a, s);              // 4 waves 64x128
-#endif
-        case 119: return launch_h2<128, 256, 4, 2, 2, 0, false>(a, s);             // 8 waves 32x128
-        case 120: return launch_h2<64, 64, 2, 2, 3, 0, false, false, 2>(a, s);     // 768-wide / small outputs: 4 waves 32x32, three blocks per CU
-        // the same two tiles WITH the LayerNorm-fold paths (GemmArgs::ln_stats / rs_stats / st_out; round 6): taken only by launches that fold
-        case 1100: return launch_h2<64, 192, 4, 2, 2, 0, false, false, 1, false, false, 1, true>(a, s);
-        case 1120: return launch_h2<64, 64, 2, 2, 3, 0, false, false, 2, false, false, 1, true>(a, s);
-#ifdef EMAGE_TOOLS
-        case 188: return launch_h2<64, 64, 2, 2, 8, 0, false, false, 1>(a, s);     // round 5 (negative): a LONE block per CU with a ring of 8 for grids of at most one tile per CU
-        case 189: return launch_h2<64, 64, 2, 4, 3, 0, false, false, 1>(a, s);     // round 5: the same tile on 8 waves of 32 x 16 (2 DMA instructions per wave and K-tile instead of 4)
-#endif
-#ifdef EMAGE_TOOLS
-        case 121: return launch_h2<64, 64, 2, 2, 3, 0, true, false, 2>(a, s);
-        case 122: return launch_h2<64, 128, 2, 2, 3, 0, true>(a, s);               // 4 waves 32x64
-        case 123: return launch_h2<128, 64, 4, 1, 3, 0, true>(a, s);               // 4 waves 32x64
-        case 124: return launch_h2<64, 96, 2, 2, 3, 0, true, false, 2>(a, s);      // 4 waves 32x48
-        case 125: return launch_h2<64, 192, 2, 2, 3, 0, true, true>(a, s);         // 103 + residual prefetch
-        case 126: return launch_h2<64, 192, 2, 2, 3, 4, false, true>(a, s);        // 106 + residual prefetch
-        case 127: return launch_h2<128, 96, 4, 1, 3, 0, true, true>(a, s);         // 108 + residual prefetch
-        case 128: return launch_h2<64, 192, 4, 2, 3, 0, false, true>(a, s);        // 101 + residual prefetch
-        case 129: return launch_h2<128, 96, 4, 1, 4, 0, true, true>(a, s);
-        case 130: return launch_h2<64, 64, 2, 2, 2, 0, false, false, 3>(a, s);
-        case 131: return launch_h2<128, 128, 4, 2, 3, 4, false>(a, s);             // 8 compute 32x64 + 4 loaders
-        case 132: return launch_h2<128, 192, 4, 2, 3, 4, false>(a, s);             // 8 compute 32x96 + 4 loaders
-        // DMA issue interleaved with the MFMAs (DILV)
-        case 140: return launch_h2<64, 192, 4, 2, 2, 0, false, false, 1, true>(a, s);
-        case 141: return launch_h2<64, 192, 4, 2, 3, 0, false, false, 1, true>(a, s);
-        case 142: return launch_h2<64, 192, 2, 4, 3, 0, false, false, 1, true>(a, s);
-        case 143: return launch_h2<64, 192, 2, 2, 3, 0, true, false, 1, true>(a, s);
-        case 144: return launch_h2<64, 192, 4, 2, 3, 0, true, false, 1, true>(a, s);      // 8 waves, pipelined fragments + interleaved DMA
-        case 145: return launch_h2<128, 128, 4, 2, 3, 0, false, false, 1, true>(a, s);
-        case 146: return launch_h2<128, 128, 4, 2, 3, 0, true, false, 1, true>(a, s);
-        case 147: return launch_h2<128, 192, 4, 2, 3, 0, false, false, 1, true>(a, s);
-        case 148: return launch_h2<128, 192, 4, 2, 3, 0, true, false, 1, true>(a, s);
-        case 149: return launch_h2<128, 256, 4, 2, 2, 0, false, false, 1, true>(a, s);
-        case 150: return launch_h2<64, 64, 2, 2, 2, 0, false, false, 3, true>(a, s);
-        case 151: return launch_h2<64, 64, 2, 2, 3, 0, false, false, 2, true>(a, s);
-        case 152: return launch_h2<128, 64, 4, 2, 3, 0, false, false, 1, true>(a, s);     // 8 waves 32x32
-        case 153: return launch_h2<64, 128, 2, 4, 3, 0, false, false, 1, true>(a, s);     // 8 waves 32x32
-        case 155: return launch_h2<64, 192, 4, 2, 4, 0, false, false, 1, true>(a, s);
-        case 156: return launch_h2<128, 128, 2, 4, 3, 0, false, false, 1, true>(a, s);    // 8 waves 64x32
-        // round 4: FEWER waves with larger wave tiles (LDS fragment bytes per MFMA fall with the wave tile: a 32x32 wave tile reads 8 KB per
-        // 12 MFMAs, a 64x48 one 14 KB per 36), several blocks per CU
-        case 160: return launch_h2<64, 96, 1, 2, 3, 0, false, false, 2>(a, s);            // 2 waves 64x48, two blocks per CU
-        case 161: return launch_h2<64, 96, 1, 2, 3, 0, true, false, 2>(a, s);
-        case 162: return launch_h2<64, 64, 1, 2, 3, 0, false, false, 3>(a, s);            // 2 waves 64x32, three blocks per CU
-        case 163: return launch_h2<64, 64, 2, 1, 3, 0, false, false, 3>(a, s);            // 2 waves 32x64
-        case 164: return launch_h2<64, 64, 1, 1, 3, 0, true, false, 3>(a, s);             // 1 wave 64x64, pipelined
-        case 165: return launch_h2<64, 64, 1, 1, 3, 0, false, false, 3>(a, s);
-        case 166: return launch_h2<128, 96, 2, 2, 3, 0, false>(a, s);                     // 4 waves 64x48, one block per CU
-        case 167: return launch_h2<128, 96, 2, 2, 3, 0, true>(a, s);
-        case 168: return launch_h2<64, 192, 1, 4, 3, 0, false>(a, s);                     // 4 waves 64x48 side by side
-        case 169: return launch_h2<64, 192, 1, 4, 3, 0, true>(a, s);
-        case 171: return launch_h2<128, 256, 2, 4, 2, 0, false>(a, s);                    // 8 waves 64x64
-        // round 5: one fat block per CU for grids of many tiles per CU (the K / V projections of all cross-attention layers): MFMA issue per K-tile
-        // 3-4x the operand delivery (64 B/clk per CU)
-        case 172: return launch_h2<256, 256, 2, 4, 2, 0, false>(a, s);                    // 8 waves 128x64
-        case 173: return launch_h2<256, 192, 2, 4, 2, 0, false>(a, s);                    // 8 waves 128x48
-        case 174: return launch_h2<256, 192, 4, 2, 2, 0, false>(a, s);                    // 8 waves 64x96
-        case 175: return launch_h2<256, 128, 4, 2, 2, 0, false>(a, s);                    // 8 waves 64x64
-        case 187: return launch_h2<64, 64, 2, 2, 3, 0, false, true, 2>(a, s);             // 120 with the residual fetched ahead of the K-loop
-        // round 5 (VERDICT next #1b, "BK = 64"): TWO K-tiles per ring slot and barrier (KPB = 2), otherwise the shipped configurations
-        case 180: return launch_h2<64, 192, 4, 2, 2, 0, false, false, 1, false, false, 2>(a, s);    // 100 with 128 KB of LDS: one block per CU
-        case 181: return launch_h2<128, 192, 2, 4, 2, 0, false, false, 1, false, false, 2>(a, s);   // 170 with 160 KB: one block per CU instead of two
-        case 183: return launch_h2<64, 64, 2, 2, 2, 0, false, false, 2, false, false, 2>(a, s);     // 120 with a ring of 2 x 32 KB: two blocks per CU
-        case 184: return launch_h2<128, 128, 4, 2, 2, 0, false, false, 1, false, false, 2>(a, s);   // 113 with a ring of 2 x 64 KB
-        case 185: return launch_h2<64, 128, 2, 4, 2, 0, false, false, 1, false, false, 2>(a, s);    // 8 waves 32x32, 96 KB
-        case 186: return launch_h2<64, 64, 2, 2, 3, 0, false, false, 1, false, false, 2>(a, s);     // 120's ring of 3, 96 KB: one block per CU
-        // instrumented twins (TRACE) of 101 / 103 / 105 / 141
-        case 201: return launch_h2<64, 192, 4, 2, 3, 0, false, false, 1, false, true>(a, s);
-        case 203: return launch_h2<64, 192, 2, 2, 3, 0, true, false, 1, false, true>(a, s);
-        case 205: return launch_h2<64, 192, 2, 2, 3, 4, true, false, 1, false, true>(a, s);
-        case 241: return launch_h2<64, 192, 4, 2, 3, 0, false, false, 1, true, true>(a, s);
-#endif
-        default: break;
-    }
-    return EMAGE_EINVAL;
-}
-
 }  // namespace
+
 
 #ifdef EMAGE_TOOLS
 extern "C" int emage_h2_set_trace(void* buf) { emage_dev::g_h2_trace = (unsigned long long*)buf; return 0; }
@@ -389,13 +381,14 @@ namespace emage_dev {
 
 int run_pp_config(int cfg, GemmArgs& a, hipStream_t s);       // gemm_h2_pp.hip
 int run_pp_group(int cfg, GemmArgs** a, int n, hipStream_t s);
+__attribute__((visibility("hidden"))) bool pp_groupable(int cfg);     // (hidden: the library's dynamic symbols stay what they were)
 
 // the tile configuration of one problem.  Measured on MI355X (tools/bench_gemm_h2.py, profiles/r03_h2_sweep*.txt).  Wide outputs: 8-wave
 // 64x192 / 128x256 tiles; everything else: 64x64 tiles, three resident blocks per CU (their barriers de-synchronise, which hides each
 // block's DMA / LDS phases behind the others' MFMAs better than one fat block per CU does at M = 4096).  < 0: unsupported argument
 static int h2_config_for(const GemmArgs& a) {
     if (g_h2_force_config >= 0) return g_h2_force_config;
-    const int ncols = a.n_store > a.N ? a.n_store : a.N;
+    const int ncols = store_cols(a);
     const int v = g_h2_variant;
     if ((v & 1) && ncols < 1024 && ncols % 192 == 0 && a.M >= 2048 && !a.out_t) return 101;       // one 8-wave block per CU
     if ((v & 4) && ncols < 1024 && ncols % 192 == 0 && a.M >= 2048 && !a.out_t) return 124;       // 64x96, two 4-wave blocks per CU
@@ -405,10 +398,10 @@ static int h2_config_for(const GemmArgs& a) {
     if ((v & 128) && ncols < 1024 && !a.out_t) return 163;
     if ((v & 256) && ncols < 1024 && !a.out_t) return 164;
     if (ncols >= 1024 && a.M >= 1024) {
-        const long t128x256 = (long)((a.M + 127) / 128) * ((ncols + 255) / 256);
+        const long t128x256 = tile_count(a, 128, 256);
         // many tiles per CU (the K/V projections of all cross-attention layers, N = 12288): 64x48 wave tiles read 14 KB of fragments per 36
         // MFMAs (the 32x128 ones of 119: 20 KB per 48) and two 80 KB blocks fit a CU: 239 vs 270 us (profiles/r04_gemm_h2_sweep_fewer_waves_wide.txt)
-        const long t128x192 = (long)((a.M + 127) / 128) * ((ncols + 191) / 192);
+        const long t128x192 = tile_count(a, 128, 192);
         const long cus = h2_cus();                     // the thresholds were measured on 256 CUs: 4 / 2 tiles per CU
         if (!(v & 512) && t128x192 >= 4 * cus && ncols % 192 == 0 && (!a.out_t || a.t_col0 % 192 == 0)) return 170;
         if (!(v & 2) && t128x256 >= 2 * cus && ncols % 256 == 0 && (!a.out_t || a.t_col0 % 256 == 0)) return 119;
@@ -435,12 +428,25 @@ static int h2_config_for(const GemmArgs& a) {
 // a launch that folds a LayerNorm (operand statistics, a folded residual, statistics out) takes the LNF twin of its configuration — 100 / 120 only
 static int h2_fold_config(const GemmArgs& a, int cfg) {
     if (!(a.ln_stats || a.rs_stats || a.st_out) || cfg < 0) return cfg;
-    const int ncols = a.n_store > a.N ? a.n_store : a.N;
+    const int ncols = store_cols(a);
     if (a.st_out) return (a.out_t || ncols >= 1024) ? EMAGE_EINVAL : 1120;      // row statistics come out of the 64 x 64 tile's 32 x 32 wave tiles only
     if (cfg == 120 || cfg == 100) return cfg + 1000;
     // batches whose plain launch would take another tile (119 / 170 / 113 beyond ~7 000 rows): the fold exists in two tiles only
     if (ncols >= 1024 && ncols % 192 == 0 && (!a.out_t || a.t_col0 % 192 == 0)) return 1100;
     return (a.out_t && a.t_col0 % 64 != 0) ? EMAGE_EINVAL : 1120;
+}
+
+// one problem on configuration `cfg`, alone in its launch.  A FIXUP row with few rows and a fix-up workspace: split-K inside the launch
+static int h2_launch_one(int cfg, GemmArgs& a, hipStream_t s) {
+    if (cfg >= 300 && cfg < 400) return run_pp_config(cfg, a, s);       // antiphase tiles: gemm_h2_pp.hip
+    return with_config<H2_CONFIGS>(cfg, [&]<H2Row R>() {
+        if constexpr (R.flags & FIXUP) {
+            int per = 0;
+            const int ksplit = h2_skf_slices(a, &per);
+            if (ksplit > 1) return launch_h2_skf<R.t>(a, ksplit, per, s);
+        }
+        return launch_h2<R.t>(a, s);
+    });
 }
 
 // called by emage_gemm (gemm.hip) for dtype EMAGE_H2 after the common argument checks
@@ -452,23 +458,13 @@ int gemm_h2_dispatch(GemmArgs& a, hipStream_t s) {
     // of 3 — are SLOWER: one clip 4.38-4.45 vs 4.33-4.34 ms, 28 s 29.2-29.4 vs 28.6-28.7, the 64-clip step 13.25-13.31 vs 13.14-13.19 (same bits).
     // Kept behind emage_set_tuning key 5 bit 524288 for A/B only
     if (cfg == 120 && g_h2_force_config < 0 && (g_h2_variant & 524288)) {
-        const long t64 = (long)((a.M + 63) / 64) * ((((a.n_store > a.N ? a.n_store : a.N)) + 63) / 64);
-        const bool bare = h2_bare(a);
-        if (t64 <= 256 && !bare) cfg = 188;
+        if (tile_count(a, 64, 64) <= 256 && !h2_bare(a)) cfg = 188;
     }
     if (cfg == 120 && g_h2_force_config < 0 && ((g_h2_variant & 1048576) || g_h2_small_cfg > 0)) {       // tools A/B: lone-block grids on 8 waves / on any 64 x 64 configuration
-        const long t64 = (long)((a.M + 63) / 64) * ((((a.n_store > a.N ? a.n_store : a.N)) + 63) / 64);
-        const bool bare = h2_bare(a);
-        if (t64 <= 256 && !bare) cfg = g_h2_small_cfg > 0 ? g_h2_small_cfg : 189;
+        if (tile_count(a, 64, 64) <= 256 && !h2_bare(a)) cfg = g_h2_small_cfg > 0 ? g_h2_small_cfg : 189;
     }
 #endif
-    if (cfg == 120 || cfg == 1120) {                                    // few rows + a fix-up workspace: split-K inside the launch
-        int per = 0;
-        const int ksplit = h2_skf_slices(a, &per);
-        if (ksplit > 1) return cfg == 120 ? launch_h2_skf<false>(a, ksplit, per, s) : launch_h2_skf<true>(a, ksplit, per, s);
-    }
-    if (cfg >= 300 && cfg < 400) return run_pp_config(cfg, a, s);       // antiphase tiles: gemm_h2_pp.hip
-    return cfg < 0 ? cfg : run_config(cfg, a, s);
+    return cfg < 0 ? cfg : h2_launch_one(cfg, a, s);
 }
 
 // called by emage_gemm_grouped: problems that take the same (groupable) configuration share launches of up to MAXG problems; the rest —
@@ -483,21 +479,12 @@ int gemm_h2_dispatch_group(GemmArgs* a, int n, hipStream_t s, bool count_only) {
         if (cfg[i] < 0) return cfg[i];
         done[i] = false;
     }
+    // a problem may share a launch when its row has a grouped kernel and it would run neither split-K form alone
     auto groupable = [&](int i) {
-        switch (cfg[i]) {
-            case 100: case 1100: return !h2_wants_split_k<64, 192>(a[i]);
-            case 1120: { int per = 0; return !h2_wants_split_k<64, 64>(a[i]) && h2_skf_slices(a[i], &per) < 2; }
-            case 113: return !h2_wants_split_k<128, 128>(a[i]);
-            case 119: return !h2_wants_split_k<128, 256>(a[i]);
-            case 120: { int per = 0; return !h2_wants_split_k<64, 64>(a[i]) && h2_skf_slices(a[i], &per) < 2; }
-            case 170: return !h2_wants_split_k<128, 192>(a[i]);
-#ifdef EMAGE_TOOLS
-            case 300: case 301: case 302: case 303: return true;
-            case 160: case 161: return !h2_wants_split_k<64, 96>(a[i]);
-            case 162: case 163: case 164: return !h2_wants_split_k<64, 64>(a[i]);
-#endif
-            default: return false;
-        }
+        if (cfg[i] >= 300 && cfg[i] < 400) return pp_groupable(cfg[i]);
+        const H2Row* r = h2_row(cfg[i]);
+        int per = 0;
+        return r && (r->flags & GROUP) && !h2_wants_split_k(a[i], r->t) && !((r->flags & FIXUP) && h2_skf_slices(a[i], &per) >= 2);
     };
     for (int i = 0; i < n; ++i) {
         if (done[i]) continue;
@@ -515,28 +502,13 @@ int gemm_h2_dispatch_group(GemmArgs* a, int n, hipStream_t s, bool count_only) {
         if (m >= 2 && cfg[i] >= 300 && cfg[i] < 400) {
             rc = run_pp_group(cfg[i], grp, m, s);
         } else if (m >= 2) {
-            switch (cfg[i]) {
-                case 100: rc = launch_h2_group<64, 192, 4, 2, 2, 0, false>(grp, m, s); break;
-                case 1100: rc = launch_h2_group<64, 192, 4, 2, 2, 0, false, false, 1, false, true>(grp, m, s); break;
-                case 1120: rc = launch_h2_group<64, 64, 2, 2, 3, 0, false, false, 2, false, true>(grp, m, s); break;
-                case 113: rc = launch_h2_group<128, 128, 4, 2, 3, 0, false>(grp, m, s); break;
-                case 119: rc = launch_h2_group<128, 256, 4, 2, 2, 0, false>(grp, m, s); break;
-                case 170: rc = launch_h2_group<128, 192, 2, 4, 2, 0, false>(grp, m, s); break;
-#ifdef EMAGE_TOOLS
-                case 160: rc = launch_h2_group<64, 96, 1, 2, 3, 0, false, false, 2>(grp, m, s); break;
-                case 161: rc = launch_h2_group<64, 96, 1, 2, 3, 0, true, false, 2>(grp, m, s); break;
-                case 162: rc = launch_h2_group<64, 64, 1, 2, 3, 0, false, false, 3>(grp, m, s); break;
-                case 163: rc = launch_h2_group<64, 64, 2, 1, 3, 0, false, false, 3>(grp, m, s); break;
-                case 164: rc = launch_h2_group<64, 64, 1, 1, 3, 0, true, false, 3>(grp, m, s); break;
-#endif
-                default: rc = launch_h2_group<64, 64, 2, 2, 3, 0, false, false, 2>(grp, m, s); break;
-            }
+            rc = with_config<H2_CONFIGS>(cfg[i], [&]<H2Row R>() {
+                if constexpr (R.flags & GROUP) return launch_h2_group<R.t>(grp, m, s);
+                else return (int)EMAGE_EINVAL;
+            });
         } else {
             done[i] = true;
-            int per = 0;
-            const int ksplit = (cfg[i] == 120 || cfg[i] == 1120) ? h2_skf_slices(a[i], &per) : -1;
-            if (ksplit > 1) rc = cfg[i] == 120 ? launch_h2_skf<false>(a[i], ksplit, per, s) : launch_h2_skf<true>(a[i], ksplit, per, s);
-            else rc = run_config(cfg[i], a[i], s);
+            rc = h2_launch_one(cfg[i], a[i], s);
         }
         if (rc) return rc;
     }

@@ -45,6 +45,20 @@ struct GemmArgs {
     unsigned long long* trace;   // tools builds: per-wave s_memtime stamps of one block (h2_tile.h TRACE), else NULL
 };
 
+// XCD-aware block order: consecutive block ids round-robin over the 8 XCDs, so block `bid` of `nblk` takes the position that gives each
+// XCD a contiguous run of the grid (neighbouring tiles share A rows / W columns in that XCD's L2)
+__device__ __forceinline__ int xcd_run_order(const int bid, const int nblk) {
+    const int q = nblk >> 3, r = nblk & 7, xcd = bid & 7, idx = bid >> 3;
+    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
+}
+// host: the columns a launch covers (the zero-filled pad columns up to n_store included), its tile count, and its grid of bm x bn tiles
+static inline int store_cols(const GemmArgs& a) { return a.n_store > a.N ? a.n_store : a.N; }
+static inline long tile_count(const GemmArgs& a, int bm, int bn) { return (long)((a.M + bm - 1) / bm) * ((store_cols(a) + bn - 1) / bn); }
+static inline void set_tile_grid(GemmArgs& a, int bm, int bn) {
+    a.tiles_m = (a.M + bm - 1) / bm;
+    a.tiles_n = (store_cols(a) + bn - 1) / bn;
+}
+
 // Epilogue kinds of gemm_pipe_tile.  EPI_LSTM (emage_lstm_step): the contraction is h_{t-1} W_hh^T with the gate rows of
 // W_hh interleaved per hidden unit (column 4u + g, g = input / forget / cell / output), `res` holds the step's input
 // projection x_t W_ih^T + b_ih + b_hh in the same layout, and the epilogue applies the LSTM cell (torch.nn.LSTM:

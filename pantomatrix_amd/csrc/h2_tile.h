@@ -33,6 +33,24 @@ struct GroupArgs {
     int tile_end[MAXG];          // running sum of tiles_m * tiles_n
     int n, total;
 };
+// host: the argument block of one grouped launch of bm x bn tiles over problems a[0..n) (whose tile grids it sets); the unused entries repeat a[0]
+static inline int fill_group(GroupArgs& g, GemmArgs** a, int n, int bm, int bn) {
+    g.total = 0;
+    for (int i = 0; i < n; ++i) {
+        GemmArgs& q = *a[i];
+        if (q.out_t && q.t_col0 % bn != 0) return EMAGE_EINVAL;
+        set_tile_grid(q, bm, bn);
+        q.trace = nullptr;
+        q.ksplit = 1;
+        q.ws = nullptr; q.ws_plane = 0; q.ldws = 0;
+        g.total += q.tiles_m * q.tiles_n;
+        g.p[i] = q;
+        g.tile_end[i] = g.total;
+    }
+    for (int i = n; i < MAXG; ++i) { g.p[i] = *a[0]; g.tile_end[i] = g.total; }
+    g.n = n;
+    return 0;
+}
 
 template <int BM, int BN, int NS, int KPB = 1> constexpr int h2_smem_bytes() { return NS * KPB * (BM + BN) * 128; }
 

@@ -44,12 +44,7 @@ static_assert(h2_smem_bytes<QA_BM, QA_BN, QA_NS>() <= 160 * 1024, "one block per
 __global__ __launch_bounds__(QA_THREADS, 1) void qkv_attn_kernel(QkvAttnGroup g) {
     __shared__ __attribute__((aligned(128))) unsigned char smem[h2_smem_bytes<QA_BM, QA_BN, QA_NS>()];
     // XCD-aware order over the whole grid (gemm_h2_group_kernel): each XCD walks a contiguous run of (clip, head) blocks, heads fastest
-    int bid = (int)blockIdx.x;
-    {
-        const int nblk = g.total;
-        const int q = nblk >> 3, r = nblk & 7, xcd = bid & 7, idx = bid >> 3;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
+    const int bid = xcd_run_order((int)blockIdx.x, g.total);
     int pi = 0;
 #pragma unroll
     for (int i = 0; i < QA_MAXG - 1; ++i) pi += (i + 1 < g.n && bid >= g.blk_end[i]) ? 1 : 0;

@@ -99,6 +99,28 @@ int emage_gather_rows(const float* table, const int64_t* idx, int idx_rows, long
                       void* out, int ldo, int n_store, int N, int K, int D, int dtype, void* stream);
 
 /*
+ * Quantizer.forward in TRAINING mode (P:144-156) behind emage_vq_argmin_f32, which stays the one place the codes are chosen.
+ * z: (N, ldz) fp32 encoder output; codebook: (K, D) fp32 contiguous; idx: (N,) int64 contiguous (clamped to [0, K)).
+ *   emage_vq_quantize_train writes zq (N, ldo) fp32 = codebook[idx[n]] and, when zq_image is non-NULL, the same rows as the decoder's
+ *   operand image ((N, ld_image) in `dtype`: EMAGE_F32 / EMAGE_BF16 / EMAGE_H2, columns [D, n_store) zero, like emage_gather_rows);
+ *   hist (K int32) = bincount(idx) (cleared by the call; integer atomics); scalars[0] = embedding_loss = (1 + beta) * mean((zq - z)^2),
+ *   scalars[1] = perplexity = exp(-sum_k p_k log(p_k + 1e-10)), p = hist / N: float64 partial sums per 16-row block in `workspace`
+ *   (emage_vq_quantize_train_workspace_bytes(N) bytes, 8-byte aligned), added in block order by a second one-block launch — no host
+ *   read-back, no floating-point atomics.
+ *   emage_vq_quantize_backward, with s = 2 / (N D) and g_loss ONE fp32 on the device (the gradient arriving at embedding_loss):
+ *     dz[n] = g_zq[n] + g_loss * beta * s * (z[n] - e[idx[n]])      (g_zq (N, ldg): the straight-through gradient, may be NULL)
+ *     d_codebook[k] = g_loss * s * sum_{n : idx[n] = k} (e[k] - z[n])  (K, D) contiguous, zero for unused codes; g_zq does not reach it
+ *   One block per code scans idx and adds its rows in ascending n in float64: bit-reproducible run to run.
+ */
+long emage_vq_quantize_train_workspace_bytes(int N);
+int emage_vq_quantize_train(const float* z, int ldz, const float* codebook, const int64_t* idx, float* zq, int ldo,
+                            void* zq_image, int ld_image, int n_store, int dtype, int* hist, float* scalars, float beta,
+                            void* workspace, long workspace_bytes, int N, int K, int D, void* stream);
+int emage_vq_quantize_backward(const float* z, int ldz, const float* codebook, const int64_t* idx, const float* g_zq, int ldg,
+                               const float* g_loss, float beta, float* dz, int ld_dz, float* d_codebook, int N, int K, int D,
+                               void* stream);
+
+/*
  * K1/K2/K3 — the one contraction kernel: Linear and Conv1d as (implicit) GEMM with a fused epilogue.
  * Replaces nn.Linear (M:232-263 call sites, MLP P:316-326), nn.Conv1d k=3 of VQEncoderV5/V6,
  * VQDecoderV5, ResBlock (P:178-261) and nn.Conv1d k=15 (+ folded eval BatchNorm1d + LeakyReLU +

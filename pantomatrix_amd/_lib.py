@@ -10,7 +10,7 @@ LIB_PATH = os.path.join(_HERE, "csrc", "libemage_hip.so")
 TOOLS_LIB_PATH = os.path.join(_HERE, "csrc", "libemage_hip_tools.so")   # -DEMAGE_TOOLS twin: every tile configuration + emage_set_tuning
 
 F32, BF16, F16X3, H2 = 0, 1, 2, 3
-ABI_VERSION = 18
+ABI_VERSION = 19
 
 _p, _i, _f, _l = C.c_void_p, C.c_int, C.c_float, C.c_long
 
@@ -43,6 +43,9 @@ SIGNATURES = {
     "emage_vq_argmin_f32": [_p, _i, _p, _p, _i, _l, _i, _i, _i, _p],
     "emage_argmax_logsoftmax_f32": [_p, _i, _p, _i, _l, _i, _i, _p],
     "emage_gather_rows": [_p, _p, _i, _l, _i, _p, _i, _i, _i, _i, _i, _i, _p],
+    "emage_vq_quantize_train_workspace_bytes": [_i],
+    "emage_vq_quantize_train": [_p, _i, _p, _p, _p, _i, _p, _i, _i, _i, _p, _p, _f, _p, _l, _i, _i, _i, _p],
+    "emage_vq_quantize_backward": [_p, _i, _p, _p, _p, _i, _p, _f, _p, _i, _p, _i, _i, _i, _p],
     "emage_gemm": [_i, _p, _i, _p, _p, _p, _p, _i, _i, _i, _p, _i, _i, _p, _i, _p, _i, _i, _i,
                    _i, _i, _i, _i, _i, _i, _i, _i, _f, _f, _p],
     "emage_gemm_ws": [_i, _p, _i, _p, _p, _p, _p, _i, _i, _i, _p, _i, _i, _p, _i, _p, _i, _i, _i,
@@ -109,7 +112,7 @@ SIGNATURES = {
     "emage_lstm_inputs": [_p, _p, _i, _p, _l, _i, _i, _p, _p, _i, _i, _i, _i, _p],
     "emage_rot6d_scatter": [_p, _i, _p, _p, _i, _i, _p],
 }
-RESTYPES = {"emage_bn_stats_workspace_bytes": _l, "emage_wav_conv_in_backward_workspace_bytes": _l, "emage_layernorm_backward_affine_workspace_bytes": _l}
+RESTYPES = {"emage_bn_stats_workspace_bytes": _l, "emage_vq_quantize_train_workspace_bytes": _l, "emage_wav_conv_in_backward_workspace_bytes": _l, "emage_layernorm_backward_affine_workspace_bytes": _l}
 
 _lib = None
 _tools = None

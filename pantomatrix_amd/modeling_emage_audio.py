@@ -678,7 +678,30 @@ def _pack_conv_decoder(pk, prefix, n_layer):
 # ======================================================================================
 # EmageVAEConv / EmageVQVAEConv  (M:19-70)
 # ======================================================================================
-class EmageVAEConv(_EmageModule):
+class _Tokenizer(_EmageModule):
+    """The motion tokenizers are frozen unless asked otherwise: the EMAGE trainer relies on it (T:233-245), so `.train()` on a fresh
+    instance raises.  `unfreeze()` makes THIS instance trainable — `.train()` then switches `forward` to the differentiable train-mode
+    forward (pantomatrix_amd/training_vq.py); `freeze()` puts it back into eval mode and restores the raise.  The eval-mode entry points
+    (`forward`, `map2index`, `map2latent`, `decode`, `decode_from_latent`) are the same code in both states."""
+
+    def train(self, mode=True):
+        if mode and not self._trainable:
+            raise NotImplementedError(f"{type(self).__name__} is frozen (the reference keeps its VQ-VAEs frozen while EMAGE trains, "
+                                      "train_emage_audio.py:233-245): call .unfreeze() first to train this tokenizer")
+        return super().train(mode)
+
+    def unfreeze(self):
+        self.__dict__["_trainable"] = True
+        return self
+
+    def freeze(self):
+        self.eval()
+        self.__dict__.pop("_trainable", None)
+        self.__dict__.pop("_train_fwd", None)
+        return self
+
+
+class EmageVAEConv(_Tokenizer):
     config_class = EmageVAEConvConfig
     base_model_prefix = "emage_vaeconv"
     _spec_fn = staticmethod(spec.vae_spec)
@@ -688,6 +711,9 @@ class EmageVAEConv(_EmageModule):
         _pack_conv_decoder(pk, "decoder", self.config.vae_layer)
 
     def forward(self, inputs):
+        if self.training:
+            from . import training_vq
+            return training_vq.train_forward(self, inputs)
         c = self.config
         cx = _Ctx(self._engine())
         b, t, d = inputs.shape
@@ -698,7 +724,7 @@ class EmageVAEConv(_EmageModule):
 
 
 
-class EmageVQVAEConv(_EmageModule):
+class EmageVQVAEConv(_Tokenizer):
     config_class = EmageVQVAEConvConfig
     base_model_prefix = "emage_vqvaeconv"
     _spec_fn = staticmethod(spec.vqvae_spec)
@@ -747,7 +773,10 @@ class EmageVQVAEConv(_EmageModule):
         idx = self._nearest(cx, latent.reshape(b * t, d).float().contiguous())
         return self._decode_idx(cx, idx, b, t).view(b, t, -1)
 
-    def forward(self, inputs):                                       # M:42-46 (values; eval mode)
+    def forward(self, inputs):                                       # M:42-46 (values in eval mode; differentiable after unfreeze().train())
+        if self.training:
+            from . import training_vq
+            return training_vq.train_forward(self, inputs)
         cx = _Ctx(self._engine())
         b, t, _ = inputs.shape
         pre = self._encode(cx, inputs)

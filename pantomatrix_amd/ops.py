@@ -413,6 +413,64 @@ def gather_rows(table, idx, dtype, n_store=None):
     return out
 
 
+@_op("vq_quantize_train", "(Tensor z, Tensor codebook, Tensor idx, Tensor(a!) zq, Tensor(b!)? image, int dtype, Tensor(c!) hist, Tensor(d!) scalars, "
+                          "float beta, Tensor(e!) workspace) -> ()")
+def _vq_quantize_train(z, codebook, idx, zq, image, dtype, hist, scalars, beta, workspace):
+    n, d = z.shape
+    check(_lib.load().emage_vq_quantize_train(_ptr(z), _ld(z), _ptr(codebook), _ptr(idx), _ptr(zq), _ld(zq), _ptr(image),
+                                              _ld(image) if image is not None else 0, image.shape[1] if image is not None else 0, dtype,
+                                              _ptr(hist), _ptr(scalars), beta, _ptr(workspace), workspace.numel() * 8, n, codebook.shape[0], d,
+                                              _stream()), "vq_quantize_train")
+
+
+def vq_quantize_train(z2d, codebook, idx, beta, zq=None, image_dtype=None, n_store=None):
+    """Quantizer.forward's training arithmetic behind `vq_argmin` (include/emage_hip.h: emage_vq_quantize_train): z2d (N, D) fp32 view,
+    codebook (K, D) fp32 contiguous, idx (N,) int64 -> (zq (N, D) fp32, image | None, hist (K,) int32, scalars (2,) fp32 =
+    [embedding_loss, perplexity]), everything on the device.  image_dtype: also write the rows as an (N, n_store) operand image of that
+    dtype (columns [D, n_store) zero)."""
+    _dev(z2d)
+    n, d = z2d.shape
+    k = codebook.shape[0]
+    assert z2d.dtype == torch.float32 and codebook.dtype == torch.float32 and codebook.is_contiguous() and codebook.shape[1] == d
+    assert idx.dtype == torch.int64 and idx.shape == (n,) and idx.is_contiguous()
+    dev = z2d.device
+    zq = torch.empty(n, d, dtype=torch.float32, device=dev) if zq is None else zq
+    assert zq.shape == (n, d) and zq.dtype == torch.float32
+    image = None
+    if image_dtype is not None:
+        image = torch.empty(n, d if n_store is None else n_store, dtype=TORCH_DTYPE[image_dtype], device=dev)
+    hist = torch.empty(k, dtype=torch.int32, device=dev)
+    scalars = torch.empty(2, dtype=torch.float32, device=dev)
+    ws = torch.empty(max(1, _lib.load().emage_vq_quantize_train_workspace_bytes(n) // 8), dtype=torch.float64, device=dev)
+    _vq_quantize_train(z2d, codebook, idx, zq, image, F32 if image_dtype is None else image_dtype, hist, scalars, float(beta), ws)
+    return zq, image, hist, scalars
+
+
+@_op("vq_quantize_backward", "(Tensor z, Tensor codebook, Tensor idx, Tensor? g_zq, Tensor g_loss, float beta, Tensor(a!) dz, Tensor(b!) d_codebook) -> ()")
+def _vq_quantize_backward(z, codebook, idx, g_zq, g_loss, beta, dz, d_codebook):
+    n, d = z.shape
+    check(_lib.load().emage_vq_quantize_backward(_ptr(z), _ld(z), _ptr(codebook), _ptr(idx), _ptr(g_zq), _ld(g_zq) if g_zq is not None else 0,
+                                                 _ptr(g_loss), beta, _ptr(dz), _ld(dz), _ptr(d_codebook), n, codebook.shape[0], d, _stream()),
+          "vq_quantize_backward")
+
+
+def vq_quantize_backward(z2d, codebook, idx, g_zq, g_loss, beta, dz=None, d_codebook=None):
+    """Backward of the quantiser (include/emage_hip.h: emage_vq_quantize_backward): g_zq (N, D) fp32 view or None (the gradient at the
+    straight-through output), g_loss a one-element fp32 DEVICE tensor (the gradient at embedding_loss) -> (dz (N, D), d_codebook (K, D)),
+    the latter bit-reproducible (fixed summation order)."""
+    _dev(z2d)
+    n, d = z2d.shape
+    assert z2d.dtype == torch.float32 and codebook.dtype == torch.float32 and codebook.is_contiguous() and codebook.shape[1] == d
+    assert idx.dtype == torch.int64 and idx.shape == (n,) and idx.is_contiguous()
+    assert g_loss.dtype == torch.float32 and g_loss.numel() == 1 and g_loss.is_cuda
+    assert g_zq is None or (g_zq.shape == (n, d) and g_zq.dtype == torch.float32)
+    dz = torch.empty(n, d, dtype=torch.float32, device=z2d.device) if dz is None else dz
+    d_codebook = torch.empty_like(codebook) if d_codebook is None else d_codebook
+    assert dz.shape == (n, d) and d_codebook.shape == codebook.shape and d_codebook.is_contiguous()
+    _vq_quantize_backward(z2d, codebook, idx, g_zq, g_loss, float(beta), dz, d_codebook)
+    return dz, d_codebook
+
+
 class SplitKScratch:
     """Scratch memory a caller lends to `gemm` launches of few rows so that they may split their K range inside the launch (include/emage_hip.h:
     emage_gemm_problem sk_ws / sk_count): one (workspace, zeroed tile counters) pair per (device, stream) — launches on one stream are ordered, so

@@ -477,11 +477,13 @@ class TrainForward:
             r0 += rows
         if not need_dx:
             return None
-        if n % 64:
-            raise RuntimeError(f"convolution backward: {n} output channels (not a multiple of 64)")
         wflat = torch.cat([w.permute(0, 2, 1).reshape(w.shape[0], taps * cin) for w in ws], 0).contiguous()        # (N, taps*cin), taps major
+        np_ = _rup(n)
+        if np_ != n:                           # the contraction length is a multiple of 64: zero channels (the tokenizers' 106 / 78 / 180 / 61 / 240-wide layers)
+            dy = torch.nn.functional.pad(dy, (0, np_ - n))
+            wflat = torch.nn.functional.pad(wflat, (0, 0, 0, np_ - n))
         dcol = torch.empty(m, _rup(kc, 4), dtype=torch.float32, device=cx.dev)[:, :kc]
-        ops.gemm(F32, dy, ops.transpose(wflat), None, None, None, dcol, None, None, n=kc, cp=n)
+        ops.gemm(F32, dy, ops.transpose(wflat), None, None, None, dcol, None, None, n=kc, cp=np_)
         return ops.col2im(dcol, cin, taps, stride, pad, lin, lout, nseq)
 
     def _conv_backward_h2(self, cx, x, cin, origins, ws, dy, n, m, mp, taps, stride, pad, lin, lout, nseq, need_dx):
@@ -643,9 +645,11 @@ class TrainForward:
         else:
             tape.add(sv["x_prev"], self._conv_backward(cx, sv["x_prev"], cin, origins, dys, k, stride, pad, lin, lout, b, True), cols=cin)
 
-    # ---- motion pre-encoder (VQEncoderV6, P:213-235), tape-aware ----------------------------------------------------------------------
-    def _conv3(self, cx, x, key, t, b, cin, slope=None, res=None):
-        y, _ = cx.conv3(x, key, t, slope=slope, res=res, n_store=_rup(cx.pk.w[key]["n"]))
+    # ---- Conv1d(k=3) + LeakyReLU + ResBlock stacks (VQEncoderV5 / V6, VQDecoderV5: P:178-261), tape-aware --------------------------------
+    def _conv3(self, cx, x, key, t, b, cin, slope=None, res=None, need_dx=True):
+        """y (M, rup64(n)) = act(conv3(x) + bias) (+ res); columns [n, rup64(n)) are zero.  need_dx False: x is the network's input."""
+        n = cx.pk.w[key]["n"]
+        y, _ = cx.conv3(x, key, t, slope=slope, res=res, n_store=_rup(n))
         if self.tape is not None:
             def bw():
                 g = self.tape.get(y)
@@ -653,21 +657,41 @@ class TrainForward:
                     return
                 if res is not None:
                     self.tape.add(res, g)
-                dpre = g if slope is None else ops.act_backward(g, y, slope)
-                dx = self._conv_backward(cx, x, cin, [(key + ".weight", key + ".bias")], dpre, 3, 1, 1, t, t, b, True)
-                self.tape.add(x, dx, cols=cin)
+                yv = y
+                if g.shape[1] != n:                      # a width that is not a multiple of 64: the padding columns carry no gradient
+                    g, yv = g[:, :n].contiguous(), y[:, :n]
+                dpre = g if slope is None else ops.act_backward(g, yv, slope)
+                dx = self._conv_backward(cx, x, cin, [(key + ".weight", key + ".bias")], dpre, 3, 1, 1, t, t, b, need_dx)
+                if need_dx:
+                    self.tape.add(x, dx, cols=cin)
             self.tape.node(bw)
         return y
 
-    def _motion_encoder(self, cx, x0, t, b, cin0):
+    def _conv_encoder(self, cx, prefix, x0, t, b, cin0, n_layer, need_dx=True):
+        """VQEncoderV5 / V6 (P:189-235): n_layer x [conv + LeakyReLU(0.2) + ResBlock].  need_dx False: no gradient for x0."""
         h, cin = x0, cin0
-        for i in range(spec.MOTION_ENC_LAYERS):
-            p = f"motion_encoder.main.{3 * i}"
-            h = self._conv3(cx, h, p, t, b, cin, slope=0.2)
+        for i in range(n_layer):
+            p = f"{prefix}.main.{3 * i}"
+            h = self._conv3(cx, h, p, t, b, cin, slope=0.2, need_dx=need_dx or i > 0)
             cin = cx.pk.w[p]["n"]
-            r = self._conv3(cx, h, f"motion_encoder.main.{3 * i + 2}.model.0", t, b, cin, slope=0.2)
-            h = self._conv3(cx, r, f"motion_encoder.main.{3 * i + 2}.model.2", t, b, cin, res=h)
+            r = self._conv3(cx, h, f"{prefix}.main.{3 * i + 2}.model.0", t, b, cin, slope=0.2)
+            h = self._conv3(cx, r, f"{prefix}.main.{3 * i + 2}.model.2", t, b, cin, res=h)
         return h
+
+    def _conv_decoder(self, cx, prefix, z, t, b, length, n_layer):
+        """VQDecoderV5 (P:237-261): two ResBlocks, n_layer x [conv + LeakyReLU(0.2)], a bare conv -> (M, rup64(out_dim))."""
+        h, cin = z, length
+        for i in range(2):
+            r = self._conv3(cx, h, f"{prefix}.main.{i}.model.0", t, b, cin, slope=0.2)
+            h = self._conv3(cx, r, f"{prefix}.main.{i}.model.2", t, b, cin, res=h)
+        for i in range(n_layer):
+            key = f"{prefix}.main.{2 + 2 * i}"
+            h = self._conv3(cx, h, key, t, b, cin, slope=0.2)
+            cin = cx.pk.w[key]["n"]
+        return self._conv3(cx, h, f"{prefix}.main.{2 + 2 * n_layer}", t, b, cin)
+
+    def _motion_encoder(self, cx, x0, t, b, cin0):
+        return self._conv_encoder(cx, "motion_encoder", x0, t, b, cin0, spec.MOTION_ENC_LAYERS)
 
     # ---- differentiable pieces: each wrapper launches the forward op and, when a tape is attached, records its backward -----------
     def _image(self, x, e):

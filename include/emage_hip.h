@@ -236,6 +236,39 @@ int emage_wav_conv_in(int dtype, const float* wav, long ldw, int L, int nwin, lo
                       void* out, int ldo, int B, int Lout, int C, int taps, int stride, int pad, void* stream);
 
 /*
+ * The audio front end in one launch (what `librosa.load(path, sr=16000)` does for PCM input, test_emage_audio.py:17-18): decode, channel
+ * mean and rational-rate polyphase low-pass resampling, out = scipy.signal.resample_poly(mean(decode(pcm)), up, down) in fp32.
+ *   pcm:  n_clips clips of n_in interleaved frames of `channels` (1..8) samples, clip b at (char*)pcm + b * clip_pitch_bytes
+ *         (>= one clip).  fmt: EMAGE_PCM_S16 (/ 32768), EMAGE_PCM_S24 (packed 3-byte little endian, sign-extended, / 8388608),
+ *         EMAGE_PCM_S32 (int32 -> float32 round-to-nearest, / 2^31), EMAGE_PCM_F32.  16- and 32-bit samples at their natural alignment;
+ *         16-bit mono / stereo with a 16-byte aligned base and pitch is read with 16-byte loads.
+ *   mono: the fp32 sum of a frame's samples in channel order, divided by `channels` (one channel: the sample itself).
+ *   out:  (n_clips, ldo >= n_out) fp32, n_out == ceil(n_in * up / down):
+ *           out[b][m] = sum_k h[m * down + half - k * up] * mono[b][k],   half = 10 * max(up, down),  0 <= k < n_in,
+ *         fp32 taps, fp32 accumulation with fused multiply-add, k descending.  One writer per output: bit-reproducible.
+ *   taps: the n_taps == 2 * half + 1 filter taps h as PHASE ROWS, 16-byte aligned: `up` rows of pitch (rpp | 1) floats, rpp = ceil(n_taps / up);
+ *         row p holds h[p], h[p + up], h[p + 2 up], ... and zeros up to the pitch (odd: with 32 | up and down odd, the rows 32 neighbouring
+ *         lanes read start on 32 different LDS banks).  up == down == 1: decode and down-mix only, taps / n_taps are ignored.
+ *   The padded taps of a short row are multiplied too (0 * x): with EMAGE_PCM_F32 an Inf / NaN sample within one row length of an output's
+ *   window makes that output NaN where the exact sum would skip it; integer PCM cannot produce one.
+ * LDS budget: the phase rows (up * (rpp | 1) * 4 bytes) must fit EMAGE_AUDIO_TAPS_LDS_BYTES, and the decoded input span of one tile of
+ * EMAGE_AUDIO_TILE outputs (ceil((TILE - 1) * down / up) + rpp + 17 floats) EMAGE_AUDIO_SPAN_LDS_BYTES: together the 160 KiB of a CU.
+ * 44 100 -> 16 000 Hz (8 821 taps) takes 36 KiB + 12 KiB, 11 025 -> 16 000 Hz (12 801 taps) 53 KiB + 3 KiB; down / up beyond about 15 is refused.
+ * EMAGE_EINVAL: null pointers, unknown fmt, channels outside 1..8, n_out != ceil(n_in up / down), ldo < n_out, clip_pitch_bytes smaller
+ * than a clip, n_taps != 20 max(up, down) + 1, a table or span beyond the budget, misaligned samples / taps, n_clips > 65535.
+ */
+#define EMAGE_PCM_S16 0
+#define EMAGE_PCM_S24 1
+#define EMAGE_PCM_S32 2
+#define EMAGE_PCM_F32 3
+#define EMAGE_AUDIO_TILE 1024
+#define EMAGE_AUDIO_TAPS_LDS_BYTES (96 * 1024)
+#define EMAGE_AUDIO_SPAN_LDS_BYTES (64 * 1024)
+int emage_audio_resample(int fmt, const void* pcm, long clip_pitch_bytes, int channels, long n_in,
+                         const float* taps, int n_taps, int up, int down,
+                         float* out, long ldo, long n_out, int n_clips, void* stream);
+
+/*
  * K1, LDS-resident input slab — the stride-1, k <= 16 convolutions with C == N in {64, 128} channels (BasicBlock conv2 of every
  * WavEncoder block and conv1 of the stride-1 blocks, P:263-306), same arithmetic as emage_gemm with taps = k, stride 1:
  *   out[s][l][n] = leaky( sum_{tap,c} A[s][l + tap - pad][c] * W[n][tap*C + c] + bias[n] + res[s][l][n], slope[n] )

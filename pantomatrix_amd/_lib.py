@@ -10,7 +10,9 @@ LIB_PATH = os.path.join(_HERE, "csrc", "libemage_hip.so")
 TOOLS_LIB_PATH = os.path.join(_HERE, "csrc", "libemage_hip_tools.so")   # -DEMAGE_TOOLS twin: every tile configuration + emage_set_tuning
 
 F32, BF16, F16X3, H2 = 0, 1, 2, 3
-ABI_VERSION = 19
+PCM_S16, PCM_S24, PCM_S32, PCM_F32 = 0, 1, 2, 3       # EMAGE_PCM_*: the sample formats of emage_audio_resample
+AUDIO_TILE = 1024                                     # EMAGE_AUDIO_TILE: outputs per tile of emage_audio_resample
+ABI_VERSION = 20
 
 _p, _i, _f, _l = C.c_void_p, C.c_int, C.c_float, C.c_long
 
@@ -53,6 +55,7 @@ SIGNATURES = {
     "emage_gemm_grouped": [_i, C.POINTER(GemmProblem), _i, _p],
     "emage_gemm_grouped_launches": [_i, C.POINTER(GemmProblem), _i],
     "emage_wav_conv_in": [_i, _p, _l, _i, _i, _l, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p],
+    "emage_audio_resample": [_i, _p, _l, _i, _l, _p, _i, _i, _i, _p, _l, _l, _i, _p],
     "emage_conv_slab": [_i, _p, _i, _p, _p, _p, _p, _i, _p, _i, _i, _i, _i, _i, _i, _f, _f, _p],
     "emage_wav_block0": [_i, _p, _l, _i, _i, _l, _i, _p, _p, _f, _p, _p, _i, _i, _i, _p, _p, _p, _i, _i, _p, _i, _i, _i, _f, _f, _p],
     "emage_attention": [_i, _p, _i, _p, _i, _p, _i, _i, _p, _i, _i, _i, _i, _i, _i, _p],

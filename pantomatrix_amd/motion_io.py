@@ -85,8 +85,8 @@ def beat_format_load(load_path, mask=None):
 
 
 # --------------------------------------------------------------------------------------------------------------
-def _read_wav(path):
-    """Minimal RIFF/WAVE reader: PCM 8/16/24/32-bit and IEEE float 32/64, any channel count -> (float32 (n, ch), sr)."""
+def _wav_chunks(path):
+    """The chunk walk of a RIFF/WAVE file -> ((format tag, channels, sample rate, _, _, bits per sample), the `data` chunk's bytes)."""
     with open(path, "rb") as f:
         raw = f.read()
     if raw[:4] != b"RIFF" or raw[8:12] != b"WAVE":
@@ -105,6 +105,12 @@ def _read_wav(path):
         pos += 8 + size + (size & 1)
     if fmt is None or data is None:
         raise ValueError(f"{path}: missing fmt/data chunk")
+    return fmt, data
+
+
+def _read_wav(path):
+    """Minimal RIFF/WAVE reader: PCM 8/16/24/32-bit and IEEE float 32/64, any channel count -> (float32 (n, ch), sr)."""
+    fmt, data = _wav_chunks(path)
     tag, ch, sr, _, _, bits = fmt
     if tag == 1:
         if bits == 8:

@@ -744,6 +744,38 @@ def wav_conv_in(dtype, wav, w, bias, slope, out, lout, stride, pad, nwin=1, hop=
     _wav_conv_in(dtype, wav, w, bias, slope, out, lout, stride, pad, nwin, hop, win_len)
 
 
+@_op("audio_resample", "(int fmt, Tensor pcm, int channels, Tensor? taps, int n_taps, int up, int down, Tensor(a!) out) -> ()")
+def _audio_resample(fmt, pcm, channels, taps, n_taps, up, down, out):
+    check(_lib.load().emage_audio_resample(fmt, _ptr(pcm), pcm.stride(0) * pcm.element_size(), channels, pcm.shape[1], _ptr(taps), n_taps, up, down,
+                                           _ptr(out), out.stride(0), out.shape[1], pcm.shape[0], _stream()), "audio_resample")
+
+
+_PCM_CODES = {torch.int16: _lib.PCM_S16, torch.uint8: _lib.PCM_S24, torch.int32: _lib.PCM_S32, torch.float32: _lib.PCM_F32}
+
+
+def audio_resample(pcm, channels, in_rate, out_rate=16000, out=None):
+    """The audio front end in one launch (`emage_audio_resample`): interleaved PCM -> mono float32 at `out_rate`.
+    pcm: device tensor (B, n_in, channels) int16 / int32 / float32, or (B, n_in, channels * 3) uint8 for packed 24-bit; the frames of a
+    clip are contiguous, the clips may be strided.  out: (B, n_out) float32 with unit sample stride, n_out = ceil(n_in * out_rate /
+    in_rate) (allocated when None).  Recordable, with one condition: the first use of a rate pair on a device uploads its tap table
+    (`audio.packed_taps`) — call that before capturing.  What the kernel does not support (a wrong n_out, channels outside 1..8, a row pitch shorter than
+    n_out, a rate pair beyond its LDS budget) raises EmageKernelError before any launch."""
+    from . import audio
+    _dev(pcm)
+    if pcm.dtype not in _PCM_CODES:
+        raise TypeError(f"audio_resample: pcm must be int16, int32, float32 or uint8 (packed 24-bit), not {pcm.dtype}")
+    assert pcm.dim() == 3 and pcm[0].is_contiguous(), (pcm.shape, pcm.stride())
+    if channels >= 1 and pcm.shape[2] != channels * (3 if pcm.dtype == torch.uint8 else 1):      # the library sees a pointer and a pitch, not this shape
+        raise ValueError(f"audio_resample: pcm of shape {tuple(pcm.shape)} ({pcm.dtype}) does not hold {channels} channels per frame")
+    up, down = audio.rate_ratio(in_rate, out_rate)
+    if out is None:
+        out = torch.empty(pcm.shape[0], audio.out_length(pcm.shape[1], up, down), dtype=torch.float32, device=pcm.device)
+    assert out.dtype == torch.float32 and out.dim() == 2 and out.stride(1) == 1 and out.shape[0] == pcm.shape[0]
+    taps = None if up == down else audio.packed_taps(up, down, pcm.device)
+    _audio_resample(_PCM_CODES[pcm.dtype], pcm, channels, taps, 2 * audio.half_length(up, down) + 1, up, down, out)
+    return out
+
+
 @_op("conv_slab", "(int dtype, Tensor a, Tensor w, Tensor bias, Tensor slope, Tensor? res, Tensor(a!) out, int nseq, int l, int taps, int pad, "
                   "float w_scale, float a_scale) -> ()")
 def _conv_slab(dtype, a, w, bias, slope, res, out, nseq, l, taps, pad, w_scale, a_scale):

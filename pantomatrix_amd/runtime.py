@@ -46,7 +46,7 @@ def calibrate_activation_shift(model, vq_model, audio, speaker_id=None, margin: 
 class ClipRunner:
     def __init__(self, model, vq_model, batch: int, n_samples: int, use_graph: bool = True, warmup: int = 2,
                  sub_batches: int = 1, main_priority: bool = False, on_overflow: str = "raise", split_k: bool = False,
-                 activation_shift: int | None = None):
+                 activation_shift: int | None = None, audio_input=None):
         """main_priority (experiment): capture on a HIGH-priority stream, so the launch chain issued on lane 0 (the critical
         path: motion encoder -> body stack -> decode) outranks the side lanes (face decoder, WavEncoders) when both have
         ready kernels — if the runtime's graph kernel nodes inherit the capturing stream's priority.
@@ -56,7 +56,10 @@ class ClipRunner:
         or "rescale" (f16x3): run that batch again on the SAME split-fp16 path with the activation images scaled down by 2^RESCALE_STEP
         (`activation_shift` + 4: |x| < 65 504 instead of 4 094; a twin runner built on first use, `rescales` counts them) and only a batch
         that overflows there too goes to the fp32 twin — a checkpoint with large pre-norm sums stays on the fast path.
-        activation_shift: the EMAGE_H2 activation shift THIS runner's launches use (None: the model's current `activation_shift`)."""
+        activation_shift: the EMAGE_H2 activation shift THIS runner's launches use (None: the model's current `activation_shift`).
+        audio_input: an `audio.AudioInput` (rate, channels, sample format): the runner takes raw interleaved PCM `(batch, n_in, channels)` of
+        that format in place of 16 kHz float audio — `n_in` (attribute) is the smallest frame count that resamples to `n_samples`, which stays
+        the 16 kHz length — and decodes, down-mixes and resamples it as the FIRST launch of every step, inside the captured graph."""
         if on_overflow not in ("raise", "fp32", "rescale"):
             raise ValueError("on_overflow must be 'raise', 'fp32' or 'rescale'")
         self.model, self.vq = model, vq_model
@@ -65,12 +68,15 @@ class ClipRunner:
         self.shift = int(model.activation_shift if activation_shift is None else activation_shift)
         ops.h2_shifted(self.shift)
         self.precision = model.precision             # what THIS runner's launches compute in (the models may be re-packed later)
-        self._args = dict(batch=batch, n_samples=n_samples, use_graph=use_graph, warmup=warmup, split_k=split_k)
+        self._args = dict(batch=batch, n_samples=n_samples, use_graph=use_graph, warmup=warmup, split_k=split_k, audio_input=audio_input)
+        self.audio_input = audio_input
         dev = model.device
         if dev.type != "cuda":
             raise RuntimeError("ClipRunner needs the models on an MI355X device")
         if batch % sub_batches:
             raise ValueError("batch must be divisible by sub_batches")
+        if sub_batches > 1 and audio_input is not None:
+            raise ValueError("audio_input needs sub_batches=1")
         if sub_batches > 1 and on_overflow != "raise":
             raise ValueError("on_overflow='fp32' needs sub_batches=1 (the exact-fp32 re-run is built per single-graph runner)")
         self.device, self.batch, self.sub = dev, batch, sub_batches
@@ -83,7 +89,17 @@ class ClipRunner:
             self.host = tuple(torch.empty((batch,) + tuple(h.shape[1:]), dtype=h.dtype, pin_memory=True)
                               for h in self.children[0].host)
             return
-        self.audio = torch.zeros(batch, n_samples, dtype=torch.float32, device=dev)
+        if audio_input is None:
+            self.audio = torch.zeros(batch, n_samples, dtype=torch.float32, device=dev)
+        else:                                        # PCM staging -> the resampled clips; the models read their first n_samples samples in place
+            from . import audio as _audio
+            self.n_in = audio_input.frames_for(n_samples)
+            up, down = _audio.rate_ratio(audio_input.rate, 16000)
+            if up != down:
+                _audio.packed_taps(up, down, dev)        # the upload happens here, never inside a capture
+            self.pcm = audio_input.staging(batch, self.n_in, dev)
+            self._resampled = torch.zeros(batch, _audio.out_length(self.n_in, up, down), dtype=torch.float32, device=dev)
+            self.audio = self._resampled[:, :n_samples]
         self.speaker_id = torch.zeros(batch, 1, dtype=torch.long, device=dev)
         self.ref_trans = torch.zeros(1, 3, device=dev)
         self.nonfinite = torch.zeros(1, dtype=torch.int32, device=dev)
@@ -112,6 +128,8 @@ class ClipRunner:
         self._checked_replays = 0
 
     def _step(self):
+        if self.audio_input is not None:
+            ops.audio_resample(self.pcm, self.audio_input.channels, self.audio_input.rate, 16000, out=self._resampled)
         # health check: inf / NaN among the network outputs the codes are taken from (the quantiser would launder them into valid
         # codes) and among the results — e.g. an activation beyond the f16x3 range
         self.nonfinite.zero_()
@@ -135,10 +153,10 @@ class ClipRunner:
 
     def run_device(self, audio=None, speaker_id=None):
         """Launch one batch on the current stream; returns device tensors (poses (B,T,165), expressions (B,T,100),
-        trans (B,T,3)) that are overwritten by the next call."""
+        trans (B,T,3)) that are overwritten by the next call.  With `audio_input`, `audio` is the batch's PCM."""
         assert self.sub == 1
         if audio is not None:
-            self.audio.copy_(audio, non_blocking=True)
+            self._input().copy_(audio, non_blocking=True)
         if speaker_id is not None:
             self.speaker_id.copy_(speaker_id, non_blocking=True)
         if self.graph is not None:
@@ -146,6 +164,10 @@ class ClipRunner:
         else:
             self.out = self._step()
         return self.out
+
+    def _input(self):
+        """The buffer a batch is fed through: the 16 kHz float audio, or with `audio_input` the PCM staging tensor."""
+        return self.audio if self.audio_input is None else self.pcm
 
     def _to_host(self, host_views):
         for h, d in zip(host_views, self.out):
@@ -188,7 +210,7 @@ class ClipRunner:
         self.rescales += 1
         if self._rescaled_twin is None:
             self._rescaled_twin = ClipRunner(self.model, self.vq, on_overflow="fp32", activation_shift=self.shift + RESCALE_STEP, **self._args)
-        out = self._rescaled_twin(self.audio, self.speaker_id)
+        out = self._rescaled_twin(self._input(), self.speaker_id)
         self.fallbacks += self._rescaled_twin.fallbacks - getattr(self, "_twin_fallbacks_seen", 0)
         self._twin_fallbacks_seen = self._rescaled_twin.fallbacks
         return out
@@ -206,7 +228,7 @@ class ClipRunner:
             finally:
                 self.model.set_precision(was[0])
                 self.vq.set_precision(was[1])
-        return self._fp32_twin(self.audio, self.speaker_id)
+        return self._fp32_twin(self._input(), self.speaker_id)
 
     def _raise_if_nonfinite(self):
         n = int(self.nonfinite_host[0])

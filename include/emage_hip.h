@@ -298,7 +298,9 @@ int emage_wav_block0(int dtype, const float* wav, long ldw, int Lw, int nwin, lo
  * q:  (B*Tq, ldq) `dtype`, head h at columns [h*hd, (h+1)*hd).
  * k:  (B*Tk, ldk) `dtype`, same head layout.
  * vt: V transposed, (B, vt_rows, ldvt) `dtype`: vt[(b*vt_rows + h*hd + d)*ldvt + t], vt_rows >= H*hd (several
- *     layers' V^T may share one buffer); ldvt % 32 == 0, ldvt >= Tk, columns [Tk, ldvt) must be finite (zero).
+ *     layers' V^T may share one buffer); ldvt % 32 == 0, ldvt >= Tk, columns [Tk, ldvt) must be finite (any finite value:
+ *     their probabilities are exactly 0).  Nothing past the ldvt columns of a row is read: with Tk in 65..96 and ldvt = 96 the
+ *     key slots [96, 128) of the 128-key path are zero operands, so what follows a V^T row in the buffer may be anything.
  * out:(B*Tq, ldo) `dtype`, head-concatenated like nn.MultiheadAttention before out_proj.
  * hd == 192 (768 / 4 heads, the only head size on this path), Tk <= 128.
  */

@@ -222,9 +222,16 @@ __device__ __forceinline__ void attn_tile(const AttnArgs& p, const int b, const 
     constexpr int NDW = NDT / DSP;            // d tiles per wave
     constexpr int VT_ = PRE ? NDW : 1;
     uint4 vf[VT_][NPC];
+    // NT = 8 with ldvt = 96 (Tk in 65..96): the chunks of keys [96, 128) lie past the V^T row, in the next row of the buffer.  Their
+    // probabilities are 0, but 0 * Inf / NaN is not: such a chunk (wave-uniform) is a zero operand instead of a load.  96 = 16 NT - 32 is the
+    // one ldvt below 16 NT that the argument check admits (ldvt % 32 == 0, ldvt >= Tk > 64), so only chunks from column 96 on can be past a row
+    constexpr int KPC = (EPC == 8) ? 32 : 16;             // keys per V^T chunk
     auto load_v = [&](int dt, uint4 (&dst)[NPC]) {
 #pragma unroll
         for (int c = 0; c < NPC; ++c) {
+            if constexpr (NT == 8) {
+                if (c * KPC >= 96 && c * KPC >= p.ldvt) { dst[c] = make_uint4(0u, 0u, 0u, 0u); continue; }
+            }
             if constexpr (EPC == 8) {
                 const uint2 lo = bload64(rv, voff, vsoff(dt) + c * 64);
                 const uint2 hi = bload64(rv, voff, vsoff(dt) + c * 64 + 32);

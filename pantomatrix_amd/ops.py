@@ -827,7 +827,8 @@ def _attention(dtype, q, k, vt, vt_rows, out, b, h, tq, tk, hd):
 
 def attention(dtype, q, k, vt, vt_rows, out, b, h, tq, tk, hd):
     """q (B*Tq, ldq), k (B*Tk, ldk) 2-D views; vt a view into a (B, vt_rows, ldvt) buffer starting at this
-    layer's first row; out (B*Tq, ldo)."""
+    layer's first row; out (B*Tq, ldo).  Columns [Tk, ldvt) of the V^T rows must be finite (they meet zero probabilities);
+    nothing outside the H*hd rows x ldvt columns of each batch is read, so the rest of the buffer may hold anything."""
     _dev(q)
     _attention(dtype, q, k, vt, vt_rows, out, b, h, tq, tk, hd)
 

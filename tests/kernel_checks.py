@@ -1,4 +1,4 @@
-"""Comparison helpers shared by the float64 kernel tests (test_backward_kernels_gpu.py, test_forward_kernels_*.py)."""
+"""Comparison helpers shared by the float64 kernel tests (test_backward_kernels_gpu.py, test_forward_kernels_*.py, test_attention_lstm_*.py)."""
 import math
 
 import torch

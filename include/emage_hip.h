@@ -131,6 +131,9 @@ int emage_vq_quantize_backward(const float* z, int ldz, const float* codebook, c
  *               BasicBlock's "x += shortcut; act2(x)", P:291-293)
  *   m = b*Lout + l,  row(m,tap) = b*Lin + l*stride + tap - pad, taken as zeros when
  *   l*stride + tap - pad is outside [0, Lin)   (taps=1,stride=1,pad=0,Lin=Lout => plain Linear).
+ *   The formula holds for taps == 1 too: taps=1 with stride != 1, pad != 0 or Lin != Lout is a 1 x 1 convolution with that geometry, not a Linear.
+ *   EMAGE_EINVAL: pad < 0, stride <= 0, Lin <= 0, Lout <= 0, M % Lout != 0 (checked before any launch); the LayerNorm fold of
+ *   emage_gemm_problem needs the plain Linear geometry.
  *
  * A:     (rows_in, lda) `dtype`; channels [C, Cp) must hold finite values (they meet zero weights).
  * W:     (N, taps*Cp) `dtype`, Cp % 64 == 0, zero in the padded channels; K = taps*Cp.

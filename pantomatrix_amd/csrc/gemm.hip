@@ -312,6 +312,7 @@ namespace {
 int apply_fold(int dtype, GemmArgs& a, const emage_gemm_problem& q) {
     if (!q.ln_stats && !q.rs_stats && !q.st_out) return 0;
     if (dtype != EMAGE_H2 || a.taps != 1) return EMAGE_EINVAL;
+    if (a.stride != 1 || a.pad != 0 || a.Lin != a.Lout) return EMAGE_EINVAL;       // the statistics are indexed by the output row: a plain Linear only
     if (q.ln_stats) {
         if (!q.ln_c || q.ln_np != 24 || q.ln_np * 32 != a.Cp || !(q.ln_eps > 0.f)) return EMAGE_EINVAL;     // the operand's rows ARE the normalised rows
         if (((uintptr_t)q.ln_stats & 15) || ((uintptr_t)q.ln_c & 15)) return EMAGE_EINVAL;
@@ -342,7 +343,7 @@ int make_args(GemmArgs& a, int dtype, const emage_dev::H2Scale& hs, const emage_
     }
     if (lda % epc != 0 || lda < Cp) return EMAGE_EINVAL;                 // 16-byte aligned operand rows
     if (((uintptr_t)q.A | (uintptr_t)q.W) & 15) return EMAGE_EINVAL;
-    if (q.Lout <= 0 || q.Lin <= 0 || M % q.Lout != 0 || q.stride <= 0) return EMAGE_EINVAL;
+    if (q.Lout <= 0 || q.Lin <= 0 || M % q.Lout != 0 || q.stride <= 0 || q.pad < 0) return EMAGE_EINVAL;    // pad < 0 would wrap A's descriptor base
     if (!q.out && !q.out_f32 && !q.out_t) return EMAGE_EINVAL;
     if (q.out_t && (q.t_rows <= 0 || M % q.t_rows != 0 || q.t_ld < q.t_rows || q.t_col0 < 0 || q.t_col0 > N)) return EMAGE_EINVAL;
     if ((dtype == EMAGE_F16X3 || dtype == EMAGE_H2) && !(q.a_scale > 0.f && q.w_scale > 0.f)) return EMAGE_EINVAL;
@@ -357,7 +358,8 @@ int make_args(GemmArgs& a, int dtype, const emage_dev::H2Scale& hs, const emage_
     a.t_col0 = q.out_t ? q.t_col0 : N; a.t_rows = q.t_rows > 0 ? q.t_rows : 1; a.t_ld = q.t_ld;
     a.dbg = g_debug_skip;
     a.ksplit = 1;
-    a.M = M; a.N = N; a.K = taps * Cp; a.Cp = Cp; a.taps = taps; a.stride = q.stride; a.pad = q.pad; a.Lin = q.Lin; a.Lout = q.Lout;
+    a.M = M; a.N = N; a.K = taps * Cp; a.Cp = Cp;
+    set_geometry(a, taps, q.stride, q.pad, q.Lin, q.Lout);
     const bool split = dtype == EMAGE_F16X3 || dtype == EMAGE_H2;
     a.a_scale = split ? q.a_scale : 1.f;
     a.o_scale = split ? 1.f / (q.a_scale * q.w_scale) : 1.f;

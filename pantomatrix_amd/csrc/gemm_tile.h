@@ -25,6 +25,9 @@ struct GemmArgs {
     float h2s, h2i;           // EMAGE_H2: the scale of the activation IMAGES this launch writes (`out`) and reads as its residual, and its inverse (csrc/h2.h: 16 unless the dtype code carries a shift)
     float* cstate; int ldc;   // EPI_LSTM: the (M, N/4) cell state, updated in place
     int ksplit, nk_split;        // EMAGE_H2 split-K (gemm_h2.hip): > 1 K-slices of nk_split K-tiles each; partial tiles atomically added into out_f32,
+    int conv;                 // 0 = the identity geometry (taps = 1, stride = 1, pad = 0, Lin = Lout): the plain row mapping; else row(m, tap) of include/emage_hip.h,
+                              // ALSO for taps = 1 (a strided / padded 1 x 1 convolution).  Written by `set_geometry` below, together with the five numbers it
+                              // stands for, and by nothing else.  (Sits in what was alignment padding in front of `ws`: no other field moves.)
     float* ws; long ws_plane; int ldws;   // ... or (ws != NULL, emage_gemm_ws) stored as plane `slice` of the workspace — (M, ldws) fp32 each, ws_plane
                                  // elements apart — and summed in slice order by a second launch (deterministic)
     int tile_order;              // EMAGE_H2 single launches: 0 = XCD-aware runs (each XCD walks a contiguous run of tiles), 1 = dispatch order (gemm_h2.hip)
@@ -44,6 +47,12 @@ struct GemmArgs {
     long sk_ws_bytes; int sk_tiles;      // capacities the caller provides (bytes of sk_ws, counters behind sk_count): the dispatch splits only within them
     unsigned long long* trace;   // tools builds: per-wave s_memtime stamps of one block (h2_tile.h TRACE), else NULL
 };
+
+// The one place a builder of GemmArgs sets the geometry: the five numbers and the flag the tile routines read in their place, so the two cannot drift
+inline void set_geometry(GemmArgs& a, const int taps, const int stride, const int pad, const int Lin, const int Lout) {
+    a.taps = taps; a.stride = stride; a.pad = pad; a.Lin = Lin; a.Lout = Lout;
+    a.conv = (taps > 1 || stride != 1 || pad != 0 || Lin != Lout) ? 1 : 0;
+}
 
 // XCD-aware block order: consecutive block ids round-robin over the 8 XCDs, so block `bid` of `nblk` takes the position that gives each
 // XCD a contiguous run of the grid (neighbouring tiles share A rows / W columns in that XCD's L2)
@@ -310,7 +319,7 @@ __device__ __forceinline__ void gemm_pipe_tile(const GemmArgs& p, const int m0, 
     // DMA slots of this lane: instruction j of this wave fills rows (wave + 4j)*RPI .. +RPI-1 of the A (or W)
     // tile; lane -> row offset lane / KC, LDS slot lane % KC, source chunk slot ^ swz(row)
     const int lrow = lane / KC, lslot = lane % KC;
-    const bool is_conv = p.taps > 1;
+    const bool is_conv = p.conv != 0;          // host flag (gemm.hip: make_args): 0 only for the identity geometry, where A row m feeds output row m
     unsigned a_voff[GA]; int a_lpos[GA];
 #pragma unroll
     for (int j = 0; j < GA; ++j) {

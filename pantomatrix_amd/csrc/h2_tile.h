@@ -411,7 +411,7 @@ __device__ __forceinline__ void gemm_h2_tile(const GemmArgs& p, const int m0, co
     const __amdgpu_buffer_rsrc_t a_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)((const char*)p.A - a_shift), 0, a_bytes, 0x00020000);
     const __amdgpu_buffer_rsrc_t w_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)p.W, 0, w_bytes, 0x00020000);
     const int lrow = lane >> 3, lslot = lane & 7;
-    const bool is_conv = p.taps > 1;
+    const bool is_conv = p.conv != 0;          // host flag (gemm.hip: make_args): 0 only for the identity geometry, where A row m feeds output row m
     // LDS slot s of row r holds logical chunk lc = s ^ swz(r): lc 0..3 = hi of k-group lc, 4..7 = lo of k-group lc - 4;
     // in memory (h2.h) k-group g is the 32 bytes [hi | lo] at g*32: source chunk = 2*(lc & 3) + (lc >> 2)
     unsigned a_voff[GA]; int a_lpos[GA];

@@ -104,7 +104,8 @@ static int lstm_args(GemmArgs& a, int dtype, const float* h_prev, int ld_hprev, 
     a = GemmArgs{};
     a.A = h_prev; a.W = w_hh; a.res = gates_x; a.out_f32 = h_out; a.cstate = cstate;
     a.lda = ld_hprev; a.ldr = ld_gx; a.ldf = ld_hout; a.ldc = ldc; a.res_is_f32 = 1;
-    a.M = B; a.N = 4 * H; a.K = H; a.Cp = H; a.taps = 1; a.stride = 1; a.pad = 0; a.Lin = B; a.Lout = B;
+    a.M = B; a.N = 4 * H; a.K = H; a.Cp = H;
+    set_geometry(a, 1, 1, 0, B, B);
     a.t_col0 = a.N; a.t_rows = 1;
     a.a_scale = dtype == EMAGE_F16X3 ? a_scale : 1.f;
     a.o_scale = dtype == EMAGE_F16X3 ? 1.f / (a_scale * w_scale) : 1.f;
@@ -140,7 +141,8 @@ extern "C" int emage_lstm_step(int dtype, const float* h_prev, int ld_hprev, con
     GemmArgs a{};
     a.A = h_prev; a.W = w_hh; a.res = gates_x; a.out_f32 = h_out; a.cstate = cstate;
     a.lda = ld_hprev; a.ldr = ld_gx; a.ldf = ld_hout; a.ldc = ldc; a.res_is_f32 = 1;
-    a.M = B; a.N = 4 * H; a.K = H; a.Cp = H; a.taps = 1; a.stride = 1; a.pad = 0; a.Lin = B; a.Lout = B;
+    a.M = B; a.N = 4 * H; a.K = H; a.Cp = H;
+    set_geometry(a, 1, 1, 0, B, B);
     a.t_col0 = a.N; a.t_rows = 1;
     a.a_scale = dtype == EMAGE_F16X3 ? a_scale : 1.f;
     a.o_scale = dtype == EMAGE_F16X3 ? 1.f / (a_scale * w_scale) : 1.f;

@@ -132,7 +132,8 @@ int make_problem(int dtype, const emage_qkv_attention_problem& q, int T, int d, 
     GemmArgs a = {};
     a.A = q.A; a.W = q.W; a.bias = q.bias;
     a.lda = q.lda;
-    a.M = (int)rows; a.N = 3 * d; a.K = d; a.Cp = d; a.taps = 1; a.stride = 1; a.pad = 0; a.Lin = a.Lout = a.M;
+    a.M = (int)rows; a.N = 3 * d; a.K = d; a.Cp = d;
+    set_geometry(a, 1, 1, 0, a.M, a.M);
     a.t_col0 = a.N; a.t_rows = 1;
     a.ksplit = 1;
     a.a_scale = q.a_scale;

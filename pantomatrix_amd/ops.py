@@ -628,7 +628,10 @@ def gemm(dtype, a, w, bias=None, slope=None, res=None, out=None, out_f32=None, o
     dtype F16X3: `a` is float32, `w` / `w_scale` come from `split_f16_weights`.  dtype H2: `a` / `out` are H2 images
     (float32-typed), `w` / `w_scale` from `split_f16_weights_h2`, `res` fp32 or (res_h2) an H2 image, `out_f32` / `out_t` fp32.
     workspace (a contiguous device tensor, scratch): emage_gemm_ws — split-K contractions store their K-slices as planes of it and add
-    them in slice order (deterministic) instead of meeting through fp32 atomics."""
+    them in slice order (deterministic) instead of meeting through fp32 atomics.
+    Geometry: output row m = b * lout + l contracts the rows b * lin + l * stride + tap - pad of `a` (zeros outside [0, lin)) for EVERY `taps`:
+    taps = 1 with stride != 1, pad != 0 or lin != lout is a 1 x 1 convolution with that geometry, and only taps = 1, stride = 1, pad = 0,
+    lin = lout is the plain Linear.  pad >= 0 is required (pad < 0 raises EmageKernelError before any launch)."""
     _dev(a)
     m = a.shape[0] if m is None else m
     lin = m if lin is None else lin

@@ -27,13 +27,11 @@ import torch
 
 import fake_ops as F
 from forward_cases import dev_of, far, gen, nans
-from kernel_checks import EPS32, _cmp, _nan_outside
+from kernel_checks import EPS32, SPLIT_FLOOR, SPLIT_REL, _cmp, _nan_outside
 from pantomatrix_amd import ops
 from pantomatrix_amd._lib import BF16, F32, F16X3, H2
 from pantomatrix_amd.modeling_lstm_audio import _LstmAudioModel
 
-SPLIT_REL = 3 * 2.0 ** -22          # per product of two split operands
-SPLIT_FLOOR = 2.0 ** -25            # of an operand times its scale: the fp16-subnormal floor of the low plane
 BF16_HALF_ULP = 2.0 ** -8           # unit roundoff of 8 significant bits (round to nearest): half an ulp, relative
 
 # ---------------------------------------------------------------------------------------------------------------------------------

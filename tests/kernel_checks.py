@@ -1,4 +1,4 @@
-"""Comparison helpers shared by the float64 kernel tests (test_backward_kernels_gpu.py, test_forward_kernels_*.py, test_attention_lstm_*.py)."""
+"""Comparison helpers shared by the float64 kernel tests (test_backward_kernels_gpu.py, test_forward_kernels_*.py, test_attention_lstm_*.py, test_gemm_float64_*.py)."""
 import math
 
 import torch
@@ -6,6 +6,8 @@ import torch
 DEV = "cuda"
 EPS32 = 2.0 ** -24          # unit roundoff of fp32
 FAR = 8.0                   # a wrong reference must miss by more than FAR x the tolerance
+SPLIT_REL = 3 * 2.0 ** -22          # per product of two split-f16 operands (EMAGE_F16X3 / EMAGE_H2)
+SPLIT_FLOOR = 2.0 ** -25            # of an operand times its scale: the fp16-subnormal floor of the low plane
 
 
 def _scale(ref):

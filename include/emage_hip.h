@@ -648,6 +648,33 @@ int emage_adam_multi(const long long* table, const int* block_tensor, const int*
                      float lr, float beta1, float beta2, float eps, float weight_decay, float grad_scale, int zero_grad, const int* skip,
                      void* stream);
 
+/* emage_adam_multi with one more gradient factor read from DEVICE memory: grad_scale_dev (one fp32, may be NULL).  Every block forms
+ * s = grad_scale * *grad_scale_dev once, in fp32, and uses g[i] * s — the clip coefficient of emage_grad_sumsq_multi reaches Adam without a
+ * pass over the gradients and without the host.  NULL is emage_adam_multi itself (the same kernel; emage_adam_multi passes NULL). */
+int emage_adam_multi_scaled(const long long* table, const int* block_tensor, const int* block_chunk, int n_blocks, const int* step_dev, int step,
+                            float lr, float beta1, float beta2, float eps, float weight_decay, float grad_scale, const float* grad_scale_dev,
+                            int zero_grad, const int* skip, void* stream);
+
+/* Global gradient norm and clip coefficient (torch.nn.utils.clip_grad_norm_, norm_type 2; train_emage_audio.py:179-180 with
+ * configs/emage_audio.yaml:67 max_grad_norm) over the gradients of an emage_adam_multi table (word 1 of a tensor's five is its gradient, word 4
+ * its n; block_tensor / block_chunk / n_blocks as there, the blocks of a tensor consecutive with ascending chunks; n_tensors rows).  In float64:
+ *   tensor_sumsq[t] = sum of g^2 over tensor t (n_tensors doubles), total_sumsq = their sum (one double);
+ * every g is squared as a double (exact), per-block partial sums go to `workspace` and a finalize launch adds each tensor's partials and then
+ * the tensors in table order with a fixed tree: no atomics, the same input gives the same bits.  Two fp32 device scalars follow:
+ *   norm = pre_scale * sqrt(total_sumsq)            (pre_scale: the 1 / world_size of a data-parallel SUM of gradients; 1 otherwise)
+ *   coef = min(1, max_norm / (norm + 1e-6))         (evaluated in double from the unrounded norm, rounded to fp32 once)
+ * max_norm <= 0 or +inf: coef = 1.0f exactly (the norm is still reported).  Non-finite gradients: norm is inf / NaN and coef what the formula
+ * gives (0 or NaN), as in torch.  Gradients need 4-byte alignment only.  workspace: 8-byte aligned, emage_grad_norm_workspace_bytes(n_blocks,
+ * n_tensors) bytes (0 for invalid counts), no initialisation needed.  Two launches. */
+long emage_grad_norm_workspace_bytes(int n_blocks, int n_tensors);
+int emage_grad_sumsq_multi(const long long* table, const int* block_tensor, const int* block_chunk, int n_blocks, int n_tensors,
+                           double pre_scale, double max_norm, double* tensor_sumsq, double* total_sumsq, float* norm, float* coef,
+                           void* workspace, long workspace_bytes, void* stream);
+
+/* g[i] *= *coef (one fp32 on the device) over every gradient of an emage_adam_multi table, one launch: the second half of a stand-alone
+ * clip_grad_norm_ (the trainers fold coef into Adam instead: emage_adam_multi_scaled). */
+int emage_scale_multi(const long long* table, const int* block_tensor, const int* block_chunk, int n_blocks, const float* coef, void* stream);
+
 /* nn.Dropout's keep mask drawn on the device (T:241-250 dropout = 0.1 in every transformer layer, P:331,343): out[i] = bernoulli(1 - p) / (1 - p)
  * from Philox4x32-10 with key = seed, counter = (i / 4, mask_id, step): a pure function of its arguments (no generator state; step_dev, one
  * int32 on the device, overrides `step` when non-NULL so a captured training step draws fresh masks on every replay).  The stream is this

@@ -12,9 +12,9 @@ TOOLS_LIB_PATH = os.path.join(_HERE, "csrc", "libemage_hip_tools.so")   # -DEMAG
 F32, BF16, F16X3, H2 = 0, 1, 2, 3
 PCM_S16, PCM_S24, PCM_S32, PCM_F32 = 0, 1, 2, 3       # EMAGE_PCM_*: the sample formats of emage_audio_resample
 AUDIO_TILE = 1024                                     # EMAGE_AUDIO_TILE: outputs per tile of emage_audio_resample
-ABI_VERSION = 20
+ABI_VERSION = 20                                      # unchanged by the gradient-norm entry points: they were ADDED, no existing prototype moved
 
-_p, _i, _f, _l = C.c_void_p, C.c_int, C.c_float, C.c_long
+_p, _i, _f, _l, _d = C.c_void_p, C.c_int, C.c_float, C.c_long, C.c_double
 
 class GemmProblem(C.Structure):
     """`emage_gemm_problem` of include/emage_hip.h: one emage_gemm call's arguments (emage_gemm_grouped takes an array of them)."""
@@ -93,6 +93,10 @@ SIGNATURES = {
     "emage_adam_step": [_p, _p, _p, _p, _l, _i, _f, _f, _f, _f, _f, _p],
     "emage_adam_multi_chunk": [],
     "emage_adam_multi": [_p, _p, _p, _i, _p, _i, _f, _f, _f, _f, _f, _f, _i, _p, _p],
+    "emage_adam_multi_scaled": [_p, _p, _p, _i, _p, _i, _f, _f, _f, _f, _f, _f, _p, _i, _p, _p],
+    "emage_grad_norm_workspace_bytes": [_i, _i],
+    "emage_grad_sumsq_multi": [_p, _p, _p, _i, _i, _d, _d, _p, _p, _p, _p, _p, _l, _p],
+    "emage_scale_multi": [_p, _p, _p, _i, _p, _p],
     "emage_dropout_mask": [_p, _l, _f, C.c_ulonglong, C.c_uint, _p, _i, _p],
     "emage_mul_add": [_p, _i, _p, _i, _i, _p, _i, _p, _i, _i, _i, _p],
     "emage_mul_add_philox": [_p, _i, _f, C.c_ulonglong, C.c_uint, _p, _i, _i, _p, _i, _p, _i, _i, _i, _p],
@@ -115,7 +119,8 @@ SIGNATURES = {
     "emage_lstm_inputs": [_p, _p, _i, _p, _l, _i, _i, _p, _p, _i, _i, _i, _i, _p],
     "emage_rot6d_scatter": [_p, _i, _p, _p, _i, _i, _p],
 }
-RESTYPES = {"emage_bn_stats_workspace_bytes": _l, "emage_vq_quantize_train_workspace_bytes": _l, "emage_wav_conv_in_backward_workspace_bytes": _l, "emage_layernorm_backward_affine_workspace_bytes": _l}
+RESTYPES = {"emage_bn_stats_workspace_bytes": _l, "emage_vq_quantize_train_workspace_bytes": _l, "emage_wav_conv_in_backward_workspace_bytes": _l, "emage_layernorm_backward_affine_workspace_bytes": _l,
+            "emage_grad_norm_workspace_bytes": _l}
 
 _lib = None
 _tools = None

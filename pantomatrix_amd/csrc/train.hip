@@ -1249,7 +1249,9 @@ namespace {
 constexpr int ADAM_CHUNK = 4096;
 __global__ __launch_bounds__(256) void adam_multi_kernel(const long long* __restrict__ table, const int* __restrict__ block_tensor, const int* __restrict__ block_chunk,
                                                          const int* __restrict__ step_dev, int step, float lr, float b1, float b2, float eps, float weight_decay,
-                                                         float grad_scale, int zero_grad, const int* __restrict__ skip) {
+                                                         float grad_scale, int zero_grad, const int* __restrict__ skip,
+                                                         const float* __restrict__ grad_scale_dev) {
+    if (grad_scale_dev) grad_scale = grad_scale * *grad_scale_dev;      // the clip coefficient of emage_grad_sumsq_multi: one fp32 product per block
     const bool skipped = skip && *skip != 0;             // a non-finite gradient was counted: parameters and moments stay as they are
     const int t = step_dev ? *step_dev : step;
     const double bias1 = 1.0 - pow((double)b1, t), bias2 = 1.0 - pow((double)b2, t);
@@ -1287,7 +1289,141 @@ extern "C" int emage_adam_multi(const long long* table, const int* block_tensor,
                                 void* stream) {
     if (!table || !block_tensor || !block_chunk || n_blocks <= 0 || (!step_dev && step <= 0)) return EMAGE_EINVAL;
     if (!(beta1 >= 0.f && beta1 < 1.f) || !(beta2 >= 0.f && beta2 < 1.f)) return EMAGE_EINVAL;
+    return emage_adam_multi_scaled(table, block_tensor, block_chunk, n_blocks, step_dev, step, lr, beta1, beta2, eps, weight_decay, grad_scale, nullptr,
+                                   zero_grad, skip, stream);
+}
+
+extern "C" int emage_adam_multi_scaled(const long long* table, const int* block_tensor, const int* block_chunk, int n_blocks, const int* step_dev, int step,
+                                       float lr, float beta1, float beta2, float eps, float weight_decay, float grad_scale, const float* grad_scale_dev,
+                                       int zero_grad, const int* skip, void* stream) {
+    if (!table || !block_tensor || !block_chunk || n_blocks <= 0 || (!step_dev && step <= 0)) return EMAGE_EINVAL;
+    if (!(beta1 >= 0.f && beta1 < 1.f) || !(beta2 >= 0.f && beta2 < 1.f)) return EMAGE_EINVAL;
     hipLaunchKernelGGL(adam_multi_kernel, dim3(n_blocks), dim3(256), 0, (hipStream_t)stream, table, block_tensor, block_chunk, step_dev, step,
-                       lr, beta1, beta2, eps, weight_decay, grad_scale, zero_grad, skip);
+                       lr, beta1, beta2, eps, weight_decay, grad_scale, zero_grad, skip, grad_scale_dev);
+    return launch_status();
+}
+
+// ---- global gradient norm and clipping -----------------------------------------------------------------------------------------------
+// torch.nn.utils.clip_grad_norm_ (norm_type 2) over the gradients of an Adam table (the layout of emage_adam_multi), INSIDE the step: the
+// norm is needed between the gradient exchange and Adam, a window a captured step only has on the device.  Two launches, every sum in
+// float64 with a fixed order (no atomics: the same input gives the same bits):
+//   sumsq_partial_kernel   block b -> partial[b] = sum of g^2 over its ADAM_CHUNK elements.  Each g is squared as a double (the product of
+//                          two 24-bit significands is exact; an fp32 square would flush below 1e-19 and overflow above 1e19).  Thread j adds
+//                          elements j, j + 256, ... in order; 64 lanes by a shuffle tree; the 4 wave sums in order.  Plain dword loads: the
+//                          gradients are bucket views with 4-byte alignment only, a wave reads 256 contiguous bytes per instruction, and the
+//                          order of the sum does not depend on where the view starts.
+//   sumsq_finalize_kernel  ONE block of 1024 threads.  Wave w adds the partials of tensors w, w + 16, ... (lane l: partials l, l + 64, ...
+//                          of the tensor in order, then the shuffle tree) -> tensor_sumsq[t]; then thread j adds its contiguous range of
+//                          tensors in table order, a shared-memory tree adds the 1024 thread sums -> total, norm and the clip coefficient.
+// The blocks of a tensor are consecutive in block_tensor with ascending chunks (as every table of this library is built): the block of
+// chunk 0 records where the tensor's partials start.
+namespace {
+constexpr int NORM_FIN_THREADS = 1024;
+__device__ __forceinline__ double wave_sum(double s) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
+    return s;                                             // lane 0 holds the sum
+}
+__global__ __launch_bounds__(256) void sumsq_partial_kernel(const long long* __restrict__ table, const int* __restrict__ block_tensor,
+                                                            const int* __restrict__ block_chunk, double* __restrict__ partial, int* __restrict__ first_block) {
+    __shared__ double red[4];
+    const int t = block_tensor[blockIdx.x], c = block_chunk[blockIdx.x];
+    const long long* e = table + 5 * (long)t;
+    const float* __restrict__ g = (const float*)e[1];
+    const long n = (long)e[4];
+    const long i0 = (long)c * ADAM_CHUNK;
+    const long i1 = i0 + ADAM_CHUNK < n ? i0 + ADAM_CHUNK : n;
+    double s = 0.0;
+#pragma unroll 4
+    for (long i = i0 + threadIdx.x; i < i1; i += 256) {
+        const double v = (double)g[i];
+        s += v * v;
+    }
+    s = wave_sum(s);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        partial[blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
+        if (c == 0) first_block[t] = (int)blockIdx.x;
+    }
+}
+__global__ __launch_bounds__(NORM_FIN_THREADS) void sumsq_finalize_kernel(const long long* __restrict__ table, const double* __restrict__ partial,
+                                                                          const int* __restrict__ first_block, int n_blocks, int n_tensors, double pre_scale,
+                                                                          double max_norm, double* __restrict__ tensor_sumsq, double* __restrict__ total_sumsq,
+                                                                          float* __restrict__ norm, float* __restrict__ coef) {
+    __shared__ double red[NORM_FIN_THREADS];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int t = wave; t < n_tensors; t += NORM_FIN_THREADS / 64) {
+        const long n = (long)table[5 * (long)t + 4];
+        const long nb = n > 0 ? (n + ADAM_CHUNK - 1) / ADAM_CHUNK : 0;
+        double s = 0.0;
+        if (nb > 0) {
+            const long first = first_block[t];
+            if (first < 0 || first + nb > n_blocks) s = NAN;          // a table whose blocks are not laid out as described above
+            else
+                for (long k = lane; k < nb; k += 64) s += partial[first + k];
+        }
+        s = wave_sum(s);
+        if (lane == 0) tensor_sumsq[t] = s;
+    }
+    __syncthreads();                                      // tensor_sumsq was written by this block: visible to all of its threads from here on
+    const int per = (n_tensors + NORM_FIN_THREADS - 1) / NORM_FIN_THREADS;
+    const int t0 = threadIdx.x * per, t1 = t0 + per < n_tensors ? t0 + per : n_tensors;
+    double a = 0.0;
+    for (int t = t0; t < t1; ++t) a += tensor_sumsq[t];
+    red[threadIdx.x] = a;
+    __syncthreads();
+    for (int w = NORM_FIN_THREADS / 2; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        const double total = red[0];
+        const double nrm = pre_scale * sqrt(total);
+        *total_sumsq = total;
+        *norm = (float)nrm;
+        double cf = 1.0;
+        if (max_norm > 0.0 && !isinf(max_norm)) {
+            cf = max_norm / (nrm + 1e-6);                 // torch: clip_coef = max_norm / (total_norm + 1e-6), clamped to at most 1 (a NaN stays a NaN)
+            if (cf > 1.0) cf = 1.0;
+        }
+        *coef = (float)cf;
+    }
+}
+__global__ __launch_bounds__(256) void scale_multi_kernel(const long long* __restrict__ table, const int* __restrict__ block_tensor,
+                                                          const int* __restrict__ block_chunk, const float* __restrict__ coef) {
+    const float c = *coef;
+    const long long* e = table + 5 * (long)block_tensor[blockIdx.x];
+    float* __restrict__ g = (float*)e[1];
+    const long n = (long)e[4];
+    const long i0 = (long)block_chunk[blockIdx.x] * ADAM_CHUNK;
+    const long i1 = i0 + ADAM_CHUNK < n ? i0 + ADAM_CHUNK : n;
+    for (long i = i0 + threadIdx.x; i < i1; i += 256) g[i] *= c;
+}
+static inline long norm_workspace_bytes(long n_blocks, long n_tensors) { return 8 * n_blocks + 4 * ((n_tensors + 1) & ~1L); }
+}  // namespace
+
+extern "C" long emage_grad_norm_workspace_bytes(int n_blocks, int n_tensors) {
+    if (n_blocks <= 0 || n_tensors <= 0) return 0;
+    return norm_workspace_bytes(n_blocks, n_tensors);
+}
+
+extern "C" int emage_grad_sumsq_multi(const long long* table, const int* block_tensor, const int* block_chunk, int n_blocks, int n_tensors,
+                                      double pre_scale, double max_norm, double* tensor_sumsq, double* total_sumsq, float* norm, float* coef,
+                                      void* workspace, long workspace_bytes, void* stream) {
+    if (!table || !block_tensor || !block_chunk || n_blocks <= 0 || n_tensors <= 0 || !tensor_sumsq || !total_sumsq || !norm || !coef) return EMAGE_EINVAL;
+    if (!workspace || ((uintptr_t)workspace & 7) || workspace_bytes < norm_workspace_bytes(n_blocks, n_tensors)) return EMAGE_EINVAL;
+    if (!(pre_scale >= 0.0) || isinf(pre_scale) || max_norm != max_norm) return EMAGE_EINVAL;
+    double* partial = (double*)workspace;
+    int* first_block = (int*)(partial + n_blocks);
+    hipLaunchKernelGGL(sumsq_partial_kernel, dim3(n_blocks), dim3(256), 0, (hipStream_t)stream, table, block_tensor, block_chunk, partial, first_block);
+    hipLaunchKernelGGL(sumsq_finalize_kernel, dim3(1), dim3(NORM_FIN_THREADS), 0, (hipStream_t)stream, table, partial, first_block, n_blocks, n_tensors,
+                       pre_scale, max_norm, tensor_sumsq, total_sumsq, norm, coef);
+    return launch_status();
+}
+
+extern "C" int emage_scale_multi(const long long* table, const int* block_tensor, const int* block_chunk, int n_blocks, const float* coef, void* stream) {
+    if (!table || !block_tensor || !block_chunk || n_blocks <= 0 || !coef) return EMAGE_EINVAL;
+    hipLaunchKernelGGL(scale_multi_kernel, dim3(n_blocks), dim3(256), 0, (hipStream_t)stream, table, block_tensor, block_chunk, coef);
     return launch_status();
 }

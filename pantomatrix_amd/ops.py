@@ -1431,7 +1431,29 @@ class AdamTable:
         self.block_tensor = torch.tensor(bt, dtype=torch.int32).to(device)
         self.block_chunk = torch.tensor(bc, dtype=torch.int32).to(device)
         self.n_blocks = len(bt)
+        self.n_tensors = len(rows)
         self.keep = quads                      # the tensors the table points at stay alive with it
+        self._norm = None
+
+    def norm_buffers(self):
+        """The persistent outputs of `grad_norm` over this table, allocated once (a captured step writes them at every replay)."""
+        if self._norm is None:
+            self._norm = GradNorm(self)
+        return self._norm
+
+
+class GradNorm:
+    """Outputs and scratch of `grad_norm` for one table: `tensor_sumsq` (n_tensors float64), `total_sumsq` (one float64) and the two fp32
+    device scalars `norm` and `coef` (views of one two-element tensor, so one copy brings both to the host)."""
+
+    def __init__(self, tab):
+        dev = tab.table.device
+        self.tensor_sumsq = torch.zeros(tab.n_tensors, dtype=torch.float64, device=dev)
+        self.total_sumsq = torch.zeros(1, dtype=torch.float64, device=dev)
+        self.scalars = torch.zeros(2, dtype=torch.float32, device=dev)
+        self.norm, self.coef = self.scalars[0:1], self.scalars[1:2]
+        nbytes = _lib.load().emage_grad_norm_workspace_bytes(tab.n_blocks, tab.n_tensors)
+        self.workspace = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=dev)
 
 
 @_op("adam_multi", "(Tensor table, Tensor block_tensor, Tensor block_chunk, int n_blocks, Tensor? step_dev, int step, float lr, float beta1, float beta2, "
@@ -1441,13 +1463,61 @@ def _adam_multi(table, block_tensor, block_chunk, n_blocks, step_dev, step, lr, 
                                        weight_decay, grad_scale, int(zero_grad), _ptr(skip), _stream()), "adam_multi")
 
 
-def adam_multi(tab: "AdamTable", step, lr=1.5e-4, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0, grad_scale=1.0, zero_grad=False, skip=None):
+@_op("adam_multi_scaled", "(Tensor table, Tensor block_tensor, Tensor block_chunk, int n_blocks, Tensor? step_dev, int step, float lr, float beta1, "
+                          "float beta2, float eps, float weight_decay, float grad_scale, Tensor grad_scale_dev, bool zero_grad, Tensor? skip) -> ()")
+def _adam_multi_scaled(table, block_tensor, block_chunk, n_blocks, step_dev, step, lr, beta1, beta2, eps, weight_decay, grad_scale, grad_scale_dev,
+                       zero_grad, skip):
+    check(_lib.load().emage_adam_multi_scaled(_ptr(table), _ptr(block_tensor), _ptr(block_chunk), n_blocks, _ptr(step_dev), step, lr, beta1, beta2, eps,
+                                              weight_decay, grad_scale, _ptr(grad_scale_dev), int(zero_grad), _ptr(skip), _stream()), "adam_multi_scaled")
+
+
+@_op("grad_sumsq_multi", "(Tensor table, Tensor block_tensor, Tensor block_chunk, int n_blocks, int n_tensors, float pre_scale, float max_norm, "
+                         "Tensor(a!) tensor_sumsq, Tensor(b!) total_sumsq, Tensor(c!) norm, Tensor(d!) coef, Tensor(e!) workspace) -> ()")
+def _grad_sumsq_multi(table, block_tensor, block_chunk, n_blocks, n_tensors, pre_scale, max_norm, tensor_sumsq, total_sumsq, norm, coef, workspace):
+    check(_lib.load().emage_grad_sumsq_multi(_ptr(table), _ptr(block_tensor), _ptr(block_chunk), n_blocks, n_tensors, pre_scale, max_norm,
+                                             _ptr(tensor_sumsq), _ptr(total_sumsq), _ptr(norm), _ptr(coef), _ptr(workspace), workspace.numel() * 8,
+                                             _stream()), "grad_sumsq_multi")
+
+
+@_op("scale_multi", "(Tensor table, Tensor block_tensor, Tensor block_chunk, int n_blocks, Tensor coef) -> ()")
+def _scale_multi(table, block_tensor, block_chunk, n_blocks, coef):
+    check(_lib.load().emage_scale_multi(_ptr(table), _ptr(block_tensor), _ptr(block_chunk), n_blocks, _ptr(coef), _stream()), "scale_multi")
+
+
+def grad_norm(tab: "AdamTable", pre_scale=1.0, max_norm=None, out=None):
+    """Global 2-norm of the gradients of `tab` and torch's clip coefficient, on the device (include/emage_hip.h: emage_grad_sumsq_multi):
+    -> `GradNorm` with norm = pre_scale * sqrt(sum g^2) and coef = min(1, max_norm / (norm + 1e-6)) as one-element fp32 device tensors and
+    the per-tensor float64 sums of squares.  max_norm None / <= 0 / inf: coef = 1.  `out`: the table's own buffers unless given."""
+    _dev(tab.table)
+    out = tab.norm_buffers() if out is None else out
+    assert out.tensor_sumsq.numel() == tab.n_tensors and out.tensor_sumsq.dtype == torch.float64 and out.norm.dtype == torch.float32
+    _grad_sumsq_multi(tab.table, tab.block_tensor, tab.block_chunk, tab.n_blocks, tab.n_tensors, float(pre_scale),
+                      0.0 if max_norm is None else float(max_norm), out.tensor_sumsq, out.total_sumsq, out.norm, out.coef, out.workspace)
+    return out
+
+
+def scale_multi(tab: "AdamTable", coef):
+    """g *= coef (a one-element fp32 device tensor) for every gradient of `tab`, one launch."""
+    _dev(tab.table)
+    assert coef.dtype == torch.float32 and coef.numel() == 1 and coef.is_cuda
+    _scale_multi(tab.table, tab.block_tensor, tab.block_chunk, tab.n_blocks, coef)
+
+
+def adam_multi(tab: "AdamTable", step, lr=1.5e-4, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0, grad_scale=1.0, zero_grad=False, skip=None,
+               grad_scale_dev=None):
     """torch.optim.Adam's update of every tensor of `tab` in ONE launch (include/emage_hip.h: emage_adam_multi); `step` an int or a one-element
     int32 device tensor.  skip: one int32 on the device — non-zero (a count of non-finite gradient words) leaves parameters and moments
-    untouched (the gradients are still cleared when zero_grad)."""
+    untouched (the gradients are still cleared when zero_grad).  grad_scale_dev: one fp32 on the device (the clip coefficient of
+    `grad_norm`) multiplied into grad_scale by the kernel (emage_adam_multi_scaled); None is the launch without it."""
     _dev(tab.table)
     if skip is not None:
         assert skip.dtype == torch.int32 and skip.numel() == 1 and skip.is_cuda
+    if grad_scale_dev is not None:
+        assert grad_scale_dev.dtype == torch.float32 and grad_scale_dev.numel() == 1 and grad_scale_dev.is_cuda
+        dev_step = torch.is_tensor(step)
+        _adam_multi_scaled(tab.table, tab.block_tensor, tab.block_chunk, tab.n_blocks, step if dev_step else None, 0 if dev_step else int(step),
+                           float(lr), float(beta1), float(beta2), float(eps), float(weight_decay), float(grad_scale), grad_scale_dev, bool(zero_grad), skip)
+        return
     if torch.is_tensor(step):
         _adam_multi(tab.table, tab.block_tensor, tab.block_chunk, tab.n_blocks, step, 0, float(lr), float(beta1), float(beta2), float(eps),
                     float(weight_decay), float(grad_scale), bool(zero_grad), skip)

@@ -1357,6 +1357,56 @@ def step_losses(fwd: TrainForward, vq, batch, iteration, dropout_masks, random_m
     return res, stats
 
 
+def _check_max_norm(value):
+    if value is None:
+        return None
+    value = float(value)
+    if not value > 0:
+        raise ValueError("max_grad_norm must be positive (None: no clipping)")
+    return value
+
+
+def _param_grad_norms(gn, names, pre_scale):
+    if gn is None:
+        raise RuntimeError("param_grad_norms: no step has run with max_grad_norm / track_grad_norm set")
+    return {n: pre_scale * v ** 0.5 for n, v in zip(names, gn.tensor_sumsq.tolist())}
+
+
+_CLIP_TABLES = {}                                         # ((gradient pointer, n), ...) -> ops.AdamTable: valid exactly as long as the key matches
+
+
+def _clip_table(grads):
+    """The pointer table over `grads` for `clip_grad_norm_`, cached per set of (pointer, n): a table stays right for as long as the
+    gradients sit where they sat (an optimizer.zero_grad() that frees them usually hands the same blocks back).  It holds no reference to
+    the gradients; a handful of sets are kept."""
+    key = tuple((g.data_ptr(), g.numel()) for g in grads)
+    tab = _CLIP_TABLES.get(key)
+    if tab is None:
+        while len(_CLIP_TABLES) >= 8:
+            _CLIP_TABLES.pop(next(iter(_CLIP_TABLES)))
+        tab = _CLIP_TABLES[key] = ops.AdamTable([(g, g, g, g) for g in grads], grads[0].device)      # only the gradient word and n are read
+        tab.keep = None
+    return tab
+
+
+def clip_grad_norm_(parameters, max_norm):
+    """torch.nn.utils.clip_grad_norm_(parameters, max_norm) (norm_type 2) on the device for the reference-style loop — `loss.backward();
+    clip_grad_norm_(model.parameters(), cfg.max_grad_norm); optimizer.step()`: one sum-of-squares launch (float64, fixed order) and one
+    scaling launch over the `.grad` of the given parameters (contiguous fp32 on the device; parameters without a gradient are skipped).
+    Returns the total norm as a 0-dim fp32 DEVICE tensor — no host synchronisation."""
+    params = [parameters] if torch.is_tensor(parameters) else list(parameters)
+    grads = [p.grad for p in params if p.grad is not None and p.grad.numel()]
+    if not grads:
+        return torch.zeros((), dtype=torch.float32, device=params[0].device if params else None)
+    for g in grads:
+        if not (g.is_cuda and g.dtype == torch.float32 and g.is_contiguous()):
+            raise RuntimeError("clip_grad_norm_: gradients must be contiguous fp32 tensors on the device (no CPU fallback)")
+    tab = _clip_table(grads)
+    out = ops.grad_norm(tab, 1.0, max_norm)
+    ops.scale_multi(tab, out.coef)
+    return out.norm.clone().reshape(())
+
+
 class Trainer:
     """One optimisation step of train_emage_audio.py:132-180 on the device: the three train-mode forwards with their backward
     passes (gradients accumulate like `loss_all.backward()`), torch.optim.Adam with the reference's settings (lr 1.5e-4 constant,
@@ -1373,7 +1423,7 @@ class Trainer:
     `grad_hook(param_grads)` still runs between backward and the update (tests spy on it)."""
 
     def __init__(self, model, vq, lr=1.5e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, sync_bn=False, group=None, seed=0, exchange=True,
-                 on_nonfinite="raise", share_encoders=True, exchange_dtype=torch.float32):
+                 on_nonfinite="raise", share_encoders=True, exchange_dtype=torch.float32, max_grad_norm=None, track_grad_norm=False):
         """exchange=False: no built-in gradient all-reduce even in a multi-process run (a `grad_hook` may do it: `dist.gradient_allreduce_hook`).
 
         Health of a step (the f16x3 backward runs on fp16 planes of `grad_scale` x dY and of scaled weights: an overflow turns into
@@ -1383,7 +1433,13 @@ class Trainer:
         "skip": the step is dropped (`skipped_steps`), `grad_scale` is halved and training goes on (a captured step is re-captured with
         the new scale: it is a launch argument) — the step-skip of loss-scaled mixed-precision training.  Weight operand scales are
         power-of-two constants chosen once; every re-packing checks on the device that max |w| x scale is still in [2^10, 2^14) and the
-        trainer re-derives the scales behind the step that reports a miss (two doublings before an fp16 plane could overflow)."""
+        trainer re-derives the scales behind the step that reports a miss (two doublings before an fp16 plane could overflow).
+
+        max_grad_norm: clip the gradient by its global 2-norm (torch.nn.utils.clip_grad_norm_; configs/emage_audio.yaml:67) INSIDE the step,
+        between the exchange and Adam — `ops.grad_norm` over the Adam table (float64 sums in a fixed order, pre_scale = 1 / world: the norm of
+        the AVERAGED gradient, what DDP followed by clip_grad_norm_ sees) and the coefficient as Adam's device-side gradient factor; eager
+        and captured.  track_grad_norm: the same launch without clipping.  Either adds "grad_norm" to the loss dict and fills
+        `param_grad_norms()`; a skipped step reports its inf / NaN norm.  Both off (the default): no launch, the step is unchanged."""
         from . import dist as pdist
         if on_nonfinite not in ("raise", "skip"):
             raise ValueError("on_nonfinite must be 'raise' or 'skip'")
@@ -1408,6 +1464,24 @@ class Trainer:
         self._adam = None
         self._graph, self._recapture_pending = None, False
         self.health = torch.zeros(1, dtype=torch.int32, device=model.device)       # non-finite gradient words of the last step (Adam's skip word)
+        self._max_grad_norm = _check_max_norm(max_grad_norm)
+        self.track_grad_norm = bool(track_grad_norm)
+        self._grad_norm, self._adam_names = None, []      # `ops.GradNorm` of the last step (buffers of the Adam table), the table's parameter names
+
+    @property
+    def max_grad_norm(self):
+        return self._max_grad_norm
+
+    @max_grad_norm.setter
+    def max_grad_norm(self, value):
+        value = _check_max_norm(value)
+        if value != self._max_grad_norm and self._graph is not None:      # a launch argument of the captured step, like the loss scale
+            self._recapture_pending = True
+        self._max_grad_norm = value
+
+    def param_grad_norms(self):
+        """{parameter name: 2-norm of its (averaged) gradient} of the last step — one device-to-host copy of the float64 sums of squares."""
+        return _param_grad_norms(self._grad_norm, self._adam_names, 1.0 / self._world())
 
     def _world(self):
         import torch.distributed as tdist
@@ -1520,11 +1594,18 @@ class Trainer:
                 st = self.state[name] = dict(step=0, exp_avg=torch.zeros_like(p), exp_avg_sq=torch.zeros_like(p))
                 quads.append((p, g, st["exp_avg"], st["exp_avg_sq"]))
             self._adam = ops.AdamTable(quads, model.device)
+            self._adam_names = list(buckets.grads)
+        clip = {}
+        if self._max_grad_norm is not None or self.track_grad_norm:
+            # global norm of the exchanged gradient SUM times 1 / world = the norm of the average; the coefficient rides into Adam on the device
+            self._grad_norm = ops.grad_norm(self._adam, pre_scale=1.0 / world, max_norm=self._max_grad_norm)
+            if self._max_grad_norm is not None:
+                clip = dict(grad_scale_dev=self._grad_norm.coef)
         self.steps_done += 1
         for st in self.state.values():
             st["step"] = self.steps_done
         ops.adam_multi(self._adam, self.steps_done if step_counter is None else step_counter, self.lr, self.betas[0], self.betas[1], self.eps,
-                       self.weight_decay, grad_scale=1.0 / world, zero_grad=True, skip=self.health)
+                       self.weight_decay, grad_scale=1.0 / world, zero_grad=True, skip=self.health, **clip)
         skipped = self.health[0] > 0                      # device scalar: the buffers below keep their values in a skipped step
         by_dtype = {}
         for name, v in stats.items():                     # BatchNorm running statistics after the three forwards
@@ -1566,6 +1647,7 @@ class Trainer:
         stale = any(int(f) != 0 for f in self._range_flags())
         ops.loss_check(ws)
         res["all"] = sum(res.values())
+        grad_norm = float(self._grad_norm.norm) if (self._max_grad_norm is not None or self.track_grad_norm) else None
         recapture = False
         if stale:                                         # results of this step are fine (margin of 4x); the NEXT packing takes fresh scales
             self.rescaled += 1
@@ -1577,6 +1659,8 @@ class Trainer:
             finite = False
         if bad:                                           # the DEVICE skipped the update (Adam's skip word, the same on every rank: it is counted
             self.steps_done -= 1                          # behind the gradient exchange) — the host only follows that decision
+            if grad_norm is not None:                     # how far off the step was: inf / NaN
+                res["grad_norm"] = grad_norm
             for st in self.state.values():
                 st["step"] = self.steps_done
             msg = (f"training step {self.steps_done + 1}: {bad} non-finite gradient words (losses {res}) — the update was skipped on the device, "
@@ -1596,6 +1680,8 @@ class Trainer:
             if self.on_nonfinite == "raise":
                 raise FloatingPointError(f"training step {self.steps_done}: non-finite loss {res} with finite gradients — the update WAS applied "
                                          "(the device's health word counts gradient words only); optimiser state and step counts are consistent")
+        if grad_norm is not None:                         # no loss: it joins the dict behind the decisions above (a skipped step reports inf / NaN)
+            res["grad_norm"] = grad_norm
         return res, recapture
 
     def step(self, batch, iteration=0, dropout_masks=None, random_mask=None, grad_hook=None):

@@ -18,7 +18,7 @@ import torch
 
 from . import ops
 from .modeling_emage_audio import _Ctx, _rup
-from .training import TrainForward, _Tape
+from .training import TrainForward, _Tape, _check_max_norm, _param_grad_norms
 
 CODEBOOK = "quantizer.embedding.weight"
 
@@ -160,9 +160,11 @@ def train_forward(model, inputs):
 class TokenizerTrainer:
     """`step(x)`: train-mode forward, `emage_mse_loss` of rec_pose against the input (+ embedding_loss for the VQ class), backward,
     `emage_adam_multi` over every parameter with the step count on the device.  No torch autograd; the only host read-back is the
-    returned losses.  Every sum of the step has a fixed order: two steps from the same state and input give the same bits."""
+    returned losses.  Every sum of the step has a fixed order: two steps from the same state and input give the same bits.
+    max_grad_norm / track_grad_norm: as for `training.Trainer` — `ops.grad_norm` over the Adam table in front of Adam, the clip
+    coefficient as Adam's device-side gradient factor, "grad_norm" in the returned dict, `param_grad_norms()`."""
 
-    def __init__(self, model, lr=1.5e-4, betas=(0.9, 0.999), eps=1e-8):
+    def __init__(self, model, lr=1.5e-4, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=None, track_grad_norm=False):
         model.unfreeze()
         self.model, self.fwd = model, TokenizerForward(model)
         self.lr, self.betas, self.eps = lr, betas, eps
@@ -177,10 +179,16 @@ class TokenizerTrainer:
         self._one = torch.ones(1, dtype=torch.float32, device=dev)
         self.health = torch.zeros(1, dtype=torch.int32, device=dev)       # non-finite gradient words of the last step (Adam's skip word)
         self.steps_done = 0
+        self.max_grad_norm, self.track_grad_norm = _check_max_norm(max_grad_norm), bool(track_grad_norm)
+        self._grad_norm = None
 
-    def step(self, x):
+    def param_grad_norms(self):
+        """{parameter name: 2-norm of its gradient} of the last step — one device-to-host copy of the float64 sums of squares."""
+        return _param_grad_norms(self._grad_norm, self.names, 1.0)
+
+    def step(self, x, grad_hook=None):
         """One optimisation step on x (B, T, vae_test_dim) -> dict of the losses as Python floats ("rec", "all"; the VQ class adds
-        "embedding_loss" and "perplexity")."""
+        "embedding_loss" and "perplexity").  `grad_hook(grads)` runs between backward and the update, as `Trainer.step`'s does."""
         fwd = self.fwd
         dev = self.model.device
         fwd.grad_views, fwd.param_grads = self.grads, {}
@@ -196,15 +204,24 @@ class TokenizerTrainer:
         ops._mse_loss_grad(rec2d, x2d, 1.0, g if g.shape[1] == d else g[:, :d])
         fwd.tape.add(rec_full, g)
         fwd.backward(g_loss=self._one if fwd.quantized else None)
+        if grad_hook is not None:
+            grad_hook(self.grads)
         fwd.flush_range_checks(new_step=True)
         # inf / NaN among the gradients (an fp16 plane of the split-fp16 backward overflowed) -> Adam's skip word: such a step never reaches the weights
         self.health.zero_()
         ops.count_nonfinite_multi(list(self.grads.values()), self.health)
         self.step_counter.add_(1)
-        ops.adam_multi(self._adam, self.step_counter, self.lr, self.betas[0], self.betas[1], self.eps, 0.0, zero_grad=True, skip=self.health)
+        clip, max_norm = {}, _check_max_norm(self.max_grad_norm)
+        tracking = max_norm is not None or self.track_grad_norm
+        if tracking:
+            self._grad_norm = ops.grad_norm(self._adam, max_norm=max_norm)
+            if max_norm is not None:
+                clip = dict(grad_scale_dev=self._grad_norm.coef)
+        ops.adam_multi(self._adam, self.step_counter, self.lr, self.betas[0], self.betas[1], self.eps, 0.0, zero_grad=True, skip=self.health, **clip)
         self.step_counter.sub_((self.health > 0).to(torch.int32))       # a skipped step does not count
         self.model.bump_versions(self._params)                  # updated through raw pointers: the next `_engine()` re-packs
         res = {"rec": float(rec_loss)}
+        grad_norm = float(self._grad_norm.norm) if tracking else None
         bad = int(self.health[0])
         if fwd.range_flag is not None and int(fwd.range_flag) != 0:      # a weight left the band its cached operand scale was chosen for
             fwd.reset_scales()
@@ -216,4 +233,6 @@ class TokenizerTrainer:
         if fwd.quantized:
             res["embedding_loss"], res["perplexity"] = float(out["embedding_loss"]), float(out["perplexity"])
             res["all"] += res["embedding_loss"]
+        if grad_norm is not None:
+            res["grad_norm"] = grad_norm
         return res

@@ -38,6 +38,8 @@ def main():
     ap.add_argument("--precision", default="f16x3")
     ap.add_argument("--graph", action="store_true", help="with --full-step: the step captured as one hipGraph (Trainer.capture / replay; precision fp32)")
     ap.add_argument("--full-step", action="store_true", help="whole optimisation steps (training.Trainer.step: + backward, Adam) instead of the forward side")
+    ap.add_argument("--max-grad-norm", type=float, default=None, help="with --full-step: clip the gradient by its global norm inside the step "
+                    "(training.Trainer(max_grad_norm=...); the reference's configs/emage_audio.yaml has 0.99)")
     args = ap.parse_args()
     import common
     from pantomatrix_amd import training
@@ -54,7 +56,9 @@ def main():
     ta = model._wav_lengths(batch["audio"].shape[1])[-1]
     random_mask = (torch.rand(b, t, 337, device=dev) < 0.5).float()
 
-    trainer = training.Trainer(model, vq) if args.full_step else None
+    if args.max_grad_norm is not None and not args.full_step:
+        ap.error("--max-grad-norm needs --full-step")
+    trainer = training.Trainer(model, vq, max_grad_norm=args.max_grad_norm) if args.full_step else None
     if args.graph:
         trainer.capture(batch, random_mask)                          # dropout masks are drawn inside the graph (ops.dropout_mask)
 
@@ -82,7 +86,7 @@ def main():
             "contractions forward and backward, fp32: exact-fp32 MFMA" if args.full_step else
             "forward side of one EMAGE training step (targets + 3 train-mode forwards + 6 losses), eager, one stream")
     print(json.dumps({"what": what, "config": {"workload": "BASELINE config 3", "clips_per_gpu": b, "frames_per_clip": t}, "dtype": args.precision,
-                      "ms_per_step": ms, "clip_windows_per_s": b / (ms * 1e-3), "peak_memory_gb": torch.cuda.max_memory_allocated() / 2 ** 30,
+                      "max_grad_norm": args.max_grad_norm, "ms_per_step": ms, "clip_windows_per_s": b / (ms * 1e-3), "peak_memory_gb": torch.cuda.max_memory_allocated() / 2 ** 30,
                       "losses": {k: round(v, 4) for k, v in losses.items()}}))
 
 

@@ -60,7 +60,9 @@ const char* emage_target_arch(void);
  *          8 / 16: write-through / non-temporal result stores, a recorded negative experiment);
  *   key 2: tile-heuristic variant for A/B runs;   key 3: timing ablations of emage_lstm_layer;
  *   key 4: force the EMAGE_H2 tile configuration id;   key 5: EMAGE_H2 tile-heuristic variant;   key 6: attention variant;
- *   key 7: EMAGE_H2 tile configuration for grids of at most one 64 x 64 tile per CU (0 = the shipped one).
+ *   key 7: EMAGE_H2 tile configuration for grids of at most one 64 x 64 tile per CU (0 = the shipped one);
+ *   key 8: retired (it selected an antiphase EMAGE_H2 configuration).  Value 0 ("off") returns 0 so that callers which always set it
+ *          keep working; any other value returns EMAGE_EINVAL.
  * Returns EMAGE_EINVAL for unknown keys.  emage_h2_set_trace: device buffer (waves x 512 uint64) for the phase tracer of the
  * instrumented EMAGE_H2 configurations (tools/trace_gemm_h2.py).
  */

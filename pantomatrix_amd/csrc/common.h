@@ -65,7 +65,7 @@ static inline int launch_status() {
     return (int)e;
 }
 
-// Tile-configuration tables (gemm.hip, gemm_h2.hip, gemm_h2_pp.hip): a constexpr array of rows, each with an `id`.  with_config calls
+// Tile-configuration tables (gemm.hip, gemm_h2.hip): a constexpr array of rows, each with an `id`.  with_config calls
 // f.template operator()<row>() for the row of that id — the row arrives as a template argument, so f can name the kernel it describes —
 // and returns its result; an id without a row is EMAGE_EINVAL.  (The id is compared as an integral_constant: reading ROWS[I].id through the
 // reference parameter crashes this compiler's code generation.)

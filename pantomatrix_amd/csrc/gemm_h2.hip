@@ -10,10 +10,9 @@ namespace emage_dev {
 int g_h2_force_config = -1;      // tools build (emage_set_tuning key 4): fixed tile configuration for sweeps
 int g_h2_variant = 0;            // tools build: dispatch-heuristic variant for A/B runs (emage_set_tuning key 5)
 int g_h2_small_cfg = 0;          // tools build: tile configuration for grids of at most one 64 x 64 tile per CU (emage_set_tuning key 7; 0 = the shipped 120)
-int g_h2_pp_cfg = 0;             // tools build: antiphase configuration for the 768-wide launches (emage_set_tuning key 8; 0 = the shipped 120)
 unsigned long long* g_h2_trace = nullptr;   // tools build: device buffer of (waves x 512) s_memtime stamps (emage_h2_set_trace)
 #else
-constexpr int g_h2_force_config = -1, g_h2_variant = 0, g_h2_small_cfg = 0, g_h2_pp_cfg = 0;
+constexpr int g_h2_force_config = -1, g_h2_variant = 0, g_h2_small_cfg = 0;
 constexpr unsigned long long* g_h2_trace = nullptr;
 #endif
 }
@@ -25,17 +24,14 @@ using namespace emage_dev;
 // One tile configuration: what gemm_h2_tile (h2_tile.h) takes as template arguments, by name
 struct H2Tile {
     int bm, bn;                  // block tile
-    int wm = 2, wn = 2;          // grid of compute waves (wave tile bm / wm x bn / wn)
-    int ns = 3;                  // ring depth in K-tiles
-    int nlw = 0;                 // loader waves
-    bool pipe = false;           // register-pipelined K-loop
-    bool pre = false;            // residual fetched ahead of the K-loop
+    int wm = 2, wn = 2;          // grid of waves (wave tile bm / wm x bn / wn)
+    int ns = 3;                  // ring depth in K-tiles (2..4)
     int occ = 1;                 // resident blocks per CU the launch bounds ask for, in blocks of 4 waves
     bool dilv = false;           // DMA issue interleaved with the MFMAs
     bool trace = false;          // phase tracer
     int kpb = 1;                 // K-tiles per ring slot and barrier
     bool lnf = false;            // the LayerNorm-fold paths (GemmArgs::ln_stats / rs_stats / st_out)
-    constexpr int waves() const { return wm * wn + nlw; }
+    constexpr int waves() const { return wm * wn; }
     constexpr int threads() const { return waves() * 64; }
 };
 enum : int { GROUP = 1, FIXUP = 2 };
@@ -45,7 +41,7 @@ struct H2Row {
     int flags = 0;               // GROUP: has a grouped kernel (emage_gemm_grouped); FIXUP: has the split-K form with the in-kernel fix-up (SKF)
 };
 
-// THE tile configurations (id: block tile, compute-wave grid [wave tile], ring depth, loader waves, K-loop form); every launcher, kernel and
+// THE tile configurations (id: block tile, wave grid [wave tile], ring depth, K-loop form); every launcher, kernel and
 // predicate below takes its row from here.  The product library carries the rows the heuristics select; the rest are the tools build's
 constexpr H2Row H2_CONFIGS[] = {
     {100, {.bm = 64, .bn = 192, .wm = 4, .ns = 2}, GROUP},                    // 8 waves 16x96 (the F16X3 shape)
@@ -59,43 +55,16 @@ constexpr H2Row H2_CONFIGS[] = {
 #ifdef EMAGE_TOOLS
     {101, {.bm = 64, .bn = 192, .wm = 4}},
     {102, {.bm = 64, .bn = 192, .wn = 4}},                                    // 8 waves 32x48
-    {103, {.bm = 64, .bn = 192, .pipe = true}},                               // 4 waves 32x96, pipelined
-    {104, {.bm = 64, .bn = 192, .ns = 4, .pipe = true}},
-    {105, {.bm = 64, .bn = 192, .nlw = 4, .pipe = true}},                     // 4 compute + 4 loader waves
-    {106, {.bm = 64, .bn = 192, .nlw = 4}},
-    {107, {.bm = 64, .bn = 192, .wn = 4, .nlw = 4}},                          // 8 compute (32x48) + 4 loaders
-    {108, {.bm = 128, .bn = 96, .wm = 4, .wn = 1, .pipe = true}},             // 4 waves 32x96
-    {109, {.bm = 128, .bn = 96, .wm = 4, .wn = 1, .nlw = 4, .pipe = true}},
-    {110, {.bm = 128, .bn = 96, .wm = 4, .nlw = 4}},                          // 8 compute 32x48 + 4 loaders
-    {111, {.bm = 128, .bn = 128, .pipe = true}},                              // 4 waves 64x64
     {112, {.bm = 128, .bn = 128, .wm = 4, .ns = 2}},                          // 8 waves 32x64
-    {115, {.bm = 128, .bn = 192, .pipe = true}},                              // 4 waves 64x96
     {116, {.bm = 128, .bn = 192, .wm = 4}},                                   // 8 waves 32x96
-    {118, {.bm = 128, .bn = 256, .pipe = true}},                              // 4 waves 64x128
-    {188, {.bm = 64, .bn = 64, .ns = 8}},                                     // round 5 (negative): a LONE block per CU with a ring of 8 for grids of at most one tile per CU
     {189, {.bm = 64, .bn = 64, .wn = 4}},                                     // round 5: the same tile on 8 waves of 32 x 16 (2 DMA instructions per wave and K-tile instead of 4)
-    {121, {.bm = 64, .bn = 64, .pipe = true, .occ = 2}},
-    {122, {.bm = 64, .bn = 128, .pipe = true}},                               // 4 waves 32x64
-    {123, {.bm = 128, .bn = 64, .wm = 4, .wn = 1, .pipe = true}},             // 4 waves 32x64
-    {124, {.bm = 64, .bn = 96, .pipe = true, .occ = 2}},                      // 4 waves 32x48
-    {125, {.bm = 64, .bn = 192, .pipe = true, .pre = true}},                  // 103 + residual prefetch
-    {126, {.bm = 64, .bn = 192, .nlw = 4, .pre = true}},                      // 106 + residual prefetch
-    {127, {.bm = 128, .bn = 96, .wm = 4, .wn = 1, .pipe = true, .pre = true}},// 108 + residual prefetch
-    {128, {.bm = 64, .bn = 192, .wm = 4, .pre = true}},                       // 101 + residual prefetch
-    {129, {.bm = 128, .bn = 96, .wm = 4, .wn = 1, .ns = 4, .pipe = true, .pre = true}},
     {130, {.bm = 64, .bn = 64, .ns = 2, .occ = 3}},
-    {131, {.bm = 128, .bn = 128, .wm = 4, .nlw = 4}},                         // 8 compute 32x64 + 4 loaders
-    {132, {.bm = 128, .bn = 192, .wm = 4, .nlw = 4}},                         // 8 compute 32x96 + 4 loaders
     // DMA issue interleaved with the MFMAs (DILV)
     {140, {.bm = 64, .bn = 192, .wm = 4, .ns = 2, .dilv = true}},
     {141, {.bm = 64, .bn = 192, .wm = 4, .dilv = true}},
     {142, {.bm = 64, .bn = 192, .wn = 4, .dilv = true}},
-    {143, {.bm = 64, .bn = 192, .pipe = true, .dilv = true}},
-    {144, {.bm = 64, .bn = 192, .wm = 4, .pipe = true, .dilv = true}},        // 8 waves, pipelined fragments + interleaved DMA
     {145, {.bm = 128, .bn = 128, .wm = 4, .dilv = true}},
-    {146, {.bm = 128, .bn = 128, .wm = 4, .pipe = true, .dilv = true}},
     {147, {.bm = 128, .bn = 192, .wm = 4, .dilv = true}},
-    {148, {.bm = 128, .bn = 192, .wm = 4, .pipe = true, .dilv = true}},
     {149, {.bm = 128, .bn = 256, .wm = 4, .ns = 2, .dilv = true}},
     {150, {.bm = 64, .bn = 64, .ns = 2, .occ = 3, .dilv = true}},
     {151, {.bm = 64, .bn = 64, .occ = 2, .dilv = true}},
@@ -106,15 +75,11 @@ constexpr H2Row H2_CONFIGS[] = {
     // round 4: FEWER waves with larger wave tiles (LDS fragment bytes per MFMA fall with the wave tile: a 32x32 wave tile reads 8 KB per
     // 12 MFMAs, a 64x48 one 14 KB per 36), several blocks per CU
     {160, {.bm = 64, .bn = 96, .wm = 1, .occ = 2}, GROUP},                    // 2 waves 64x48, two blocks per CU
-    {161, {.bm = 64, .bn = 96, .wm = 1, .pipe = true, .occ = 2}, GROUP},
     {162, {.bm = 64, .bn = 64, .wm = 1, .occ = 3}, GROUP},                    // 2 waves 64x32, three blocks per CU
     {163, {.bm = 64, .bn = 64, .wn = 1, .occ = 3}, GROUP},                    // 2 waves 32x64
-    {164, {.bm = 64, .bn = 64, .wm = 1, .wn = 1, .pipe = true, .occ = 3}, GROUP},// 1 wave 64x64, pipelined
     {165, {.bm = 64, .bn = 64, .wm = 1, .wn = 1, .occ = 3}},
     {166, {.bm = 128, .bn = 96}},                                             // 4 waves 64x48, one block per CU
-    {167, {.bm = 128, .bn = 96, .pipe = true}},
     {168, {.bm = 64, .bn = 192, .wm = 1, .wn = 4}},                           // 4 waves 64x48 side by side
-    {169, {.bm = 64, .bn = 192, .wm = 1, .wn = 4, .pipe = true}},
     {171, {.bm = 128, .bn = 256, .wn = 4, .ns = 2}},                          // 8 waves 64x64
     // round 5: one fat block per CU for grids of many tiles per CU (the K / V projections of all cross-attention layers): MFMA issue per K-tile
     // 3-4x the operand delivery (64 B/clk per CU)
@@ -122,7 +87,6 @@ constexpr H2Row H2_CONFIGS[] = {
     {173, {.bm = 256, .bn = 192, .wn = 4, .ns = 2}},                          // 8 waves 128x48
     {174, {.bm = 256, .bn = 192, .wm = 4, .ns = 2}},                          // 8 waves 64x96
     {175, {.bm = 256, .bn = 128, .wm = 4, .ns = 2}},                          // 8 waves 64x64
-    {187, {.bm = 64, .bn = 64, .pre = true, .occ = 2}},                       // 120 with the residual fetched ahead of the K-loop
     // round 5 (VERDICT next #1b, "BK = 64"): TWO K-tiles per ring slot and barrier (KPB = 2), otherwise the shipped configurations
     {180, {.bm = 64, .bn = 192, .wm = 4, .ns = 2, .kpb = 2}},                 // 100 with 128 KB of LDS: one block per CU
     {181, {.bm = 128, .bn = 192, .wn = 4, .ns = 2, .kpb = 2}},                // 170 with 160 KB: one block per CU instead of two
@@ -130,10 +94,8 @@ constexpr H2Row H2_CONFIGS[] = {
     {184, {.bm = 128, .bn = 128, .wm = 4, .ns = 2, .kpb = 2}},                // 113 with a ring of 2 x 64 KB
     {185, {.bm = 64, .bn = 128, .wn = 4, .ns = 2, .kpb = 2}},                 // 8 waves 32x32, 96 KB
     {186, {.bm = 64, .bn = 64, .kpb = 2}},                                    // 120's ring of 3, 96 KB: one block per CU
-    // instrumented twins (TRACE) of 101 / 103 / 105 / 141
+    // instrumented twins (TRACE) of 101 / 141
     {201, {.bm = 64, .bn = 192, .wm = 4, .trace = true}},
-    {203, {.bm = 64, .bn = 192, .pipe = true, .trace = true}},
-    {205, {.bm = 64, .bn = 192, .nlw = 4, .pipe = true, .trace = true}},
     {241, {.bm = 64, .bn = 192, .wm = 4, .dilv = true, .trace = true}},
 #endif
 };
@@ -161,7 +123,7 @@ __global__ __launch_bounds__(C.waves() * 64, C.occ * C.waves() / 4) void gemm_h2
     if (p.tile_order == 0 && !EMAGE_DBG(p, 32)) bid = xcd_run_order(bid, nblk);     // (tools: emage_set_tuning key 1 bit 32, tools/prof_traffic_calib.py: dispatch order for every launch)
     int tile_n = bid % p.tiles_n, tile_m = bid / p.tiles_n;
     if (EMAGE_DBG(p, 64)) { tile_m = bid % p.tiles_m; tile_n = bid / p.tiles_m; }      // tools: an XCD's run walks M first (it owns a slice of N: A re-fetched per XCD, W once)
-    gemm_h2_tile<C.bm, C.bn, C.wm, C.wn, C.ns, C.nlw, C.pipe, C.pre, C.dilv, C.trace, C.kpb, C.lnf, SKF>(p, tile_m * C.bm, tile_n * C.bn, smem, split);
+    gemm_h2_tile<C.bm, C.bn, C.wm, C.wn, C.ns, C.dilv, C.trace, C.kpb, C.lnf, SKF>(p, tile_m * C.bm, tile_n * C.bn, smem, split);
 }
 
 
@@ -281,7 +243,7 @@ int launch_h2(GemmArgs& a, hipStream_t s) {
         if (want > 64) want = 64;
         if (want > 1) {
             int per = (nk_all + want - 1) / want;
-            per = (per + 1) & ~1;                      // the register-pipelined loops take K-tiles in pairs
+            per = (per + 1) & ~1;                      // K-tiles in pairs (the two-K-tiles-per-slot rows need an even count)
             a.nk_split = per;
             a.ksplit = (nk_all + per - 1) / per;
             if (accumulate) {
@@ -346,7 +308,7 @@ __global__ __launch_bounds__(C.waves() * 64, C.occ * C.waves() / 4) void gemm_h2
     // XCD-aware order over the WHOLE grid: each XCD walks a contiguous run of the concatenated tile list, i.e. mostly one problem
     // (its W panel stays in that XCD's L2)
     const int bid = xcd_run_order((int)blockIdx.x, g.total);
-    // which problem is this block in (written out here, in gemm_h2_pp.hip and in qkv_attention.hip: moved into a shared function, the same scan
+    // which problem is this block in (written out here and in qkv_attention.hip: moved into a shared function, the same scan
     // makes the compiler number these kernels' scalar registers differently)
     int pi = 0;
 #pragma unroll
@@ -355,7 +317,7 @@ __global__ __launch_bounds__(C.waves() * 64, C.occ * C.waves() / 4) void gemm_h2
     const int t = bid - (pi ? g.tile_end[pi - 1] : 0);
     const GemmArgs& p = g.p[pi];
     const int tile_n = t % p.tiles_n, tile_m = t / p.tiles_n;
-    gemm_h2_tile<C.bm, C.bn, C.wm, C.wn, C.ns, C.nlw, C.pipe, C.pre, C.dilv, C.trace, C.kpb, C.lnf>(p, tile_m * C.bm, tile_n * C.bn, smem, 0);
+    gemm_h2_tile<C.bm, C.bn, C.wm, C.wn, C.ns, C.dilv, C.trace, C.kpb, C.lnf>(p, tile_m * C.bm, tile_n * C.bn, smem, 0);
 }
 
 // the split-K condition of launch_h2 (bare contractions with few tiles and a long K: the weight gradients of a training step)
@@ -379,10 +341,6 @@ extern "C" int emage_h2_set_trace(void* buf) { emage_dev::g_h2_trace = (unsigned
 
 namespace emage_dev {
 
-int run_pp_config(int cfg, GemmArgs& a, hipStream_t s);       // gemm_h2_pp.hip
-int run_pp_group(int cfg, GemmArgs** a, int n, hipStream_t s);
-__attribute__((visibility("hidden"))) bool pp_groupable(int cfg);     // (hidden: the library's dynamic symbols stay what they were)
-
 // the tile configuration of one problem.  Measured on MI355X (tools/bench_gemm_h2.py, profiles/r03_h2_sweep*.txt).  Wide outputs: 8-wave
 // 64x192 / 128x256 tiles; everything else: 64x64 tiles, three resident blocks per CU (their barriers de-synchronise, which hides each
 // block's DMA / LDS phases behind the others' MFMAs better than one fat block per CU does at M = 4096).  < 0: unsupported argument
@@ -391,12 +349,9 @@ static int h2_config_for(const GemmArgs& a) {
     const int ncols = store_cols(a);
     const int v = g_h2_variant;
     if ((v & 1) && ncols < 1024 && ncols % 192 == 0 && a.M >= 2048 && !a.out_t) return 101;       // one 8-wave block per CU
-    if ((v & 4) && ncols < 1024 && ncols % 192 == 0 && a.M >= 2048 && !a.out_t) return 124;       // 64x96, two 4-wave blocks per CU
     if ((v & 16) && ncols < 1024 && ncols % 96 == 0 && a.M >= 2048 && !a.out_t) return 160;      // 64x96, two 2-wave blocks per CU
-    if ((v & 32) && ncols < 1024 && ncols % 96 == 0 && a.M >= 2048 && !a.out_t) return 161;
     if ((v & 64) && ncols < 1024 && !a.out_t) return 162;
     if ((v & 128) && ncols < 1024 && !a.out_t) return 163;
-    if ((v & 256) && ncols < 1024 && !a.out_t) return 164;
     if (ncols >= 1024 && a.M >= 1024) {
         const long t128x256 = tile_count(a, 128, 256);
         // many tiles per CU (the K/V projections of all cross-attention layers, N = 12288): 64x48 wave tiles read 14 KB of fragments per 36
@@ -418,10 +373,6 @@ static int h2_config_for(const GemmArgs& a) {
         if (mk >= 20L * per_cu) return 100;
     }
     if (a.out_t && a.t_col0 % 64 != 0) return EMAGE_EINVAL;
-#ifdef EMAGE_TOOLS
-    // round 6 A/B (emage_set_tuning key 8 = g_h2_pp_cfg): 768-wide launches over many rows on an ANTIPHASE configuration (gemm_h2_pp.hip)
-    if (g_h2_pp_cfg > 0 && !a.out_t && ncols % 96 == 0 && ncols >= 768 && a.M >= 2048) return g_h2_pp_cfg;
-#endif
     return (v & 8) ? 130 : 120;
 }
 
@@ -438,7 +389,6 @@ static int h2_fold_config(const GemmArgs& a, int cfg) {
 
 // one problem on configuration `cfg`, alone in its launch.  A FIXUP row with few rows and a fix-up workspace: split-K inside the launch
 static int h2_launch_one(int cfg, GemmArgs& a, hipStream_t s) {
-    if (cfg >= 300 && cfg < 400) return run_pp_config(cfg, a, s);       // antiphase tiles: gemm_h2_pp.hip
     return with_config<H2_CONFIGS>(cfg, [&]<H2Row R>() {
         if constexpr (R.flags & FIXUP) {
             int per = 0;
@@ -453,13 +403,6 @@ static int h2_launch_one(int cfg, GemmArgs& a, hipStream_t s) {
 int gemm_h2_dispatch(GemmArgs& a, hipStream_t s) {
     int cfg = h2_fold_config(a, h2_config_for(a));
 #ifdef EMAGE_TOOLS
-    // round 5, measured NEGATIVE (profiles/r05_small_grids_ring_of_8_ab.txt): grids of at most one 64 x 64 tile per CU (ONE clip: M = 64 rows; the
-    // N = 256 heads / conv3 of the 64-clip batch) on config 188 — the same tile as a LONE block per CU with a ring of 8 K-tiles in flight instead
-    // of 3 — are SLOWER: one clip 4.38-4.45 vs 4.33-4.34 ms, 28 s 29.2-29.4 vs 28.6-28.7, the 64-clip step 13.25-13.31 vs 13.14-13.19 (same bits).
-    // Kept behind emage_set_tuning key 5 bit 524288 for A/B only
-    if (cfg == 120 && g_h2_force_config < 0 && (g_h2_variant & 524288)) {
-        if (tile_count(a, 64, 64) <= 256 && !h2_bare(a)) cfg = 188;
-    }
     if (cfg == 120 && g_h2_force_config < 0 && ((g_h2_variant & 1048576) || g_h2_small_cfg > 0)) {       // tools A/B: lone-block grids on 8 waves / on any 64 x 64 configuration
         if (tile_count(a, 64, 64) <= 256 && !h2_bare(a)) cfg = g_h2_small_cfg > 0 ? g_h2_small_cfg : 189;
     }
@@ -481,7 +424,6 @@ int gemm_h2_dispatch_group(GemmArgs* a, int n, hipStream_t s, bool count_only) {
     }
     // a problem may share a launch when its row has a grouped kernel and it would run neither split-K form alone
     auto groupable = [&](int i) {
-        if (cfg[i] >= 300 && cfg[i] < 400) return pp_groupable(cfg[i]);
         const H2Row* r = h2_row(cfg[i]);
         int per = 0;
         return r && (r->flags & GROUP) && !h2_wants_split_k(a[i], r->t) && !((r->flags & FIXUP) && h2_skf_slices(a[i], &per) >= 2);
@@ -499,9 +441,7 @@ int gemm_h2_dispatch_group(GemmArgs* a, int n, hipStream_t s, bool count_only) {
             done[i] = true;
             continue;
         }
-        if (m >= 2 && cfg[i] >= 300 && cfg[i] < 400) {
-            rc = run_pp_group(cfg[i], grp, m, s);
-        } else if (m >= 2) {
+        if (m >= 2) {
             rc = with_config<H2_CONFIGS>(cfg[i], [&]<H2Row R>() {
                 if constexpr (R.flags & GROUP) return launch_h2_group<R.t>(grp, m, s);
                 else return (int)EMAGE_EINVAL;

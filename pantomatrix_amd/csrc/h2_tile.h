@@ -2,13 +2,15 @@
 // v_mfma_f32_16x16x32_f16 only — no VALU.  Shared by gemm_h2.hip (one tile per block) and fused kernels.
 //
 // Structure (all template parameters):
-//   * BM x BN block tile, WM x WN COMPUTE waves (wave tile WTM x WTN = FM x FN fragments of 16 x 16); optionally NLW
-//     dedicated LOADER waves that only issue the operand DMA (the compute waves then never stall on the texture path:
-//     an LDS-DMA instruction costs its issuing wave 60-180 cycles, MI355X_MICROARCH.md);
-//   * NS-deep LDS ring of K-tiles (32 k = 128 bytes per row, image [4 hi chunks | 4 lo chunks] per row, XOR-swizzled slots
-//     as in gemm_tile.h), ONE raw s_barrier per K-tile, counted s_waitcnt vmcnt on the issuing waves;
-//   * PIPE: the fragments of K-tile k+1 are read from LDS while the MFMAs of K-tile k run (two register sets, reads
-//     interleaved between the MFMAs) — affordable here because no fp32 staging registers / split temporaries exist;
+//   * BM x BN block tile, WM x WN waves (wave tile WTM x WTN = FM x FN fragments of 16 x 16); every wave issues its share of
+//     the operand DMA and computes;
+//   * NS-deep LDS ring of K-tiles (NS = 2..4; 32 k = 128 bytes per row, image [4 hi chunks | 4 lo chunks] per row, XOR-swizzled
+//     slots as in gemm_tile.h);
+//   * ONE K-loop: per ring slot a counted s_waitcnt vmcnt (the slot has landed, up to NS - 2 newer ones stay in flight), one raw
+//     s_barrier, the DMA of the slot NS - 1 ahead, then per K-tile 2 FM + 2 FN ds_read_b128 and 3 FM FN MFMAs.  Two tools-only forms
+//     remain as template parameters: DILV (the DMA issue spread between the MFMAs) and KPB (two K-tiles per slot and barrier).
+//     (Loader waves, a register-pipelined second K-loop, a prefetched residual and rings deeper than 4 were built and measured,
+//     none was faster — DESIGN.md 4.1 — and are removed.)
 //   * swapped MFMA operands + permuted W rows: a lane ends with 8 consecutive output columns of one row (one h2 group or
 //     two float4); an odd fragment count leaves one lone fragment with 4 consecutive columns;
 //   * tiles inside the V^T column range (out_t) run the MFMAs UN-swapped: a lane then holds 4 consecutive rows of one
@@ -129,9 +131,9 @@ __device__ __forceinline__ void ln_wave_finish(const int fr, const float eps, co
 // (fr, fg) holds row mw + 16 i + fr; V^T tiles (un-swapped): lane holds rows mw + 16 i + 4 fg + r of one column.
 // ln_mu / ln_rs / rs_mu / rs_rs: (mu, rstd) of the lane's FM rows for the folded LayerNorm of the operand / of the residual (row-major tiles;
 // V^T tiles fetch theirs here); ignored unless p.ln_stats / p.rs_stats
-template <int FM, int FN, bool NAT, bool PRE, int PM, int PP, bool LNF = false, bool SKF = false>
+template <int FM, int FN, bool NAT, bool LNF = false, bool SKF = false>
 __device__ __forceinline__ void h2_tile_epilogue(const GemmArgs& p, f32x4 (&acc)[FM][FN], const int mw, const int nw, const int fr, const int fg,
-                                                 const bool vt_tile, const float (&pre_r)[PM][PP][8], const int split = 0,
+                                                 const bool vt_tile, const int split = 0,
                                                  const float* ln_mu = nullptr, const float* ln_rs = nullptr, const float* rs_mu = nullptr, const float* rs_rs = nullptr) {
     constexpr int FP = NAT ? 0 : FN / 2;
     constexpr bool LONE = !NAT && (FN & 1) != 0;
@@ -207,7 +209,7 @@ __device__ __forceinline__ void h2_tile_epilogue(const GemmArgs& p, f32x4 (&acc)
     float* __restrict__ of32 = to_plane ? p.ws + (long)split * p.ws_plane : p.out_f32;
     const int ldf = to_plane ? p.ldws : p.ldf;
     const bool f32_vec = of32 && (ldf % 4 == 0) && (((uintptr_t)of32 & 15) == 0);
-    auto finish = [&](auto wc, const int m, const int n, float (&x)[decltype(wc)::value], const float (&rpre)[decltype(wc)::value], const bool have_pre, const int i) {
+    auto finish = [&](auto wc, const int m, const int n, float (&x)[decltype(wc)::value], const int i) {
         // x: accumulators (already scaled) of W consecutive columns n.. of row m (fragment row i of the lane) -> bias, residual, activation, stores
         constexpr int W = decltype(wc)::value;
         const bool full = n + W <= ncol_n;
@@ -231,10 +233,7 @@ __device__ __forceinline__ void h2_tile_epilogue(const GemmArgs& p, f32x4 (&acc)
         if (full) {
             if (p.bias) { if constexpr (W == 8) load8<float>(p.bias + n, bv); else { const float4 t = *(const float4*)(p.bias + n); bv[0] = t.x; bv[1] = t.y; bv[2] = t.z; bv[3] = t.w; } }
             if (p.slope) { if constexpr (W == 8) load8<float>(p.slope + n, sv); else { const float4 t = *(const float4*)(p.slope + n); sv[0] = t.x; sv[1] = t.y; sv[2] = t.z; sv[3] = t.w; } }
-            if (have_pre) {
-#pragma unroll
-                for (int e = 0; e < W; ++e) rv[e] = rpre[e];
-            } else if (p.res) {
+            if (p.res) {
                 if (p.res_is_f32) {
                     if constexpr (W == 8) load8<float>((const float*)p.res + (long)m * p.ldr + n, rv);
                     else { const float4 t = *(const float4*)((const float*)p.res + (long)m * p.ldr + n); rv[0] = t.x; rv[1] = t.y; rv[2] = t.z; rv[3] = t.w; }
@@ -336,7 +335,7 @@ __device__ __forceinline__ void h2_tile_epilogue(const GemmArgs& p, f32x4 (&acc)
             float x[8];
 #pragma unroll
             for (int e = 0; e < 8; ++e) x[e] = e < 4 ? acc[i][2 * jp][e] : acc[i][2 * jp + 1][e - 4];
-            finish(IC<8>{}, m, n, x, pre_r[i % PM][jp % PP], PRE && p.res && n + 8 <= ncol_n, i);
+            finish(IC<8>{}, m, n, x, i);
         }
     }
 #pragma unroll
@@ -350,8 +349,7 @@ __device__ __forceinline__ void h2_tile_epilogue(const GemmArgs& p, f32x4 (&acc)
                 float x[4];
 #pragma unroll
                 for (int e = 0; e < 4; ++e) x[e] = acc[i][jl][e];
-                const float none[4] = {0.f, 0.f, 0.f, 0.f};
-                finish(IC<4>{}, m, n, x, none, false, i);
+                finish(IC<4>{}, m, n, x, i);
             }
         }
     }
@@ -359,37 +357,31 @@ __device__ __forceinline__ void h2_tile_epilogue(const GemmArgs& p, f32x4 (&acc)
 
 // KPB (round 5, VERDICT next #1b "BK = 64"): K-tiles per ring slot and per s_barrier — a slot holds KPB consecutive 32-k sub-tiles (each in the
 // unchanged [4 hi | 4 lo] row image), one rendezvous and one counted wait serve KPB x (3 FM FN) MFMAs per wave; the MFMA order per
-// accumulator is that of KPB = 1, so the result is the same bits.  Plain K-loop only (not PIPE / DILV).
+// accumulator is that of KPB = 1, so the result is the same bits.  Not with DILV.
 // LNF: the instantiation carries the LayerNorm-fold paths (GemmArgs::ln_stats / rs_stats / st_out); the plain one ignores those fields
 // SKF: the instantiation carries the in-kernel split-K fix-up (GemmArgs::sk_ws / sk_count)
 // SEG3 (qkv_attention.hip): the BN tile rows are three slices of BN / 3 W rows, p.N / 3 rows apart (q, k, v of one head of a packed in_proj)
-// EPI: a callable that replaces the epilogue — epi(acc, first row of the wave tile, wm, wn, fr, fg, ln_mu, ln_rs), with every compute wave
+// EPI: a callable that replaces the epilogue — epi(acc, first row of the wave tile, wm, wn, fr, fg, ln_mu, ln_rs), with every wave
 // past the K-loop (the operand ring is still being read by other waves: the callable synchronises before it reuses it)
-template <int BM, int BN, int WM, int WN, int NS, int NLW, bool PIPE, bool PRE, bool DILV = false, bool TRACE = false, int KPB = 1, bool LNF = false, bool SKF = false,
-          bool SEG3 = false, typename EPI = std::nullptr_t>
+template <int BM, int BN, int WM, int WN, int NS, bool DILV = false, bool TRACE = false, int KPB = 1, bool LNF = false, bool SKF = false, bool SEG3 = false,
+          typename EPI = std::nullptr_t>
 __device__ __forceinline__ void gemm_h2_tile(const GemmArgs& p, const int m0, const int n0, unsigned char* smem, const int split = 0, EPI epi = nullptr) {
     constexpr int ES = 4, BK = 32, RB = 128, RPI = 8;
-    constexpr int NCW = WM * WN, NL = NLW ? NLW : NCW;
-    constexpr int WTM = BM / WM, WTN = BN / WN, FM = WTM / 16, FN = WTN / 16, FP = FN / 2;
+    constexpr int NW = WM * WN;
+    constexpr int WTM = BM / WM, WTN = BN / WN, FM = WTM / 16, FN = WTN / 16;
     constexpr bool LONE = (FN & 1) != 0;
-    constexpr int GA = BM / RPI / NL, GB = BN / RPI / NL, G = GA + GB;
-    static_assert((BM / RPI) % NL == 0 && (BN / RPI) % NL == 0, "every loading wave issues the same number of DMA instructions");
-    static_assert(WTM % 16 == 0 && WTN % 16 == 0 && NS >= 2 && NS <= 8, "tile shape");
-    static_assert(NS <= 4 || !PIPE, "rings deeper than 4: the plain K-loop");
-    static_assert((NS - 2) * (BM / 8 / (NLW ? NLW : WM * WN) + BN / 8 / (NLW ? NLW : WM * WN)) * KPB <= 63, "vmcnt is a 6-bit counter");
-    static_assert(!PIPE || NS >= 3, "the register-pipelined K-loop reads one stage ahead: ring of >= 3");
-    static_assert(KPB == 1 || (!PIPE && !DILV && KPB == 2), "several K-tiles per slot: the plain K-loop");
+    constexpr int GA = BM / RPI / NW, GB = BN / RPI / NW, G = GA + GB;
+    static_assert((BM / RPI) % NW == 0 && (BN / RPI) % NW == 0, "every wave issues the same number of DMA instructions");
+    static_assert(WTM % 16 == 0 && WTN % 16 == 0 && NS >= 2 && NS <= 4, "tile shape");
+    static_assert((NS - 2) * G * KPB <= 63, "vmcnt is a 6-bit counter");
+    static_assert(KPB == 1 || (!DILV && KPB == 2), "several K-tiles per slot: not with the interleaved DMA issue");
     constexpr int SUB = (BM + BN) * RB;               // one 32-k sub-tile of a slot
     constexpr int STAGE = KPB * SUB;
-    constexpr int AH = PIPE ? 1 : 0;                  // stages the fragment reads run ahead of the MFMAs
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const bool is_loader = NLW ? wave >= NCW : true;
-    const bool is_compute = NLW ? wave < NCW : true;
-    const int lw = NLW ? wave - NCW : wave;
-    const int wm = (wave % NCW) / WN, wn = (wave % NCW) % WN;
+    const int wm = (wave % NW) / WN, wn = (wave % NW) % WN;
     // TRACE (tools): lane 0 of every wave of block 0 stamps s_memtime at the phase boundaries: trace[wave * 512 + k]
     int tr_n = 0;
     auto tr = [&]() {
@@ -403,7 +395,7 @@ __device__ __forceinline__ void gemm_h2_tile(const GemmArgs& p, const int m0, co
     };
     tr();
 
-    // ---- operand DMA (loading waves): lane-fixed byte offsets, K advance in the scalar offset ----
+    // ---- operand DMA: lane-fixed byte offsets, K advance in the scalar offset ----
     const int nbatch = p.M / p.Lout;
     const unsigned a_shift = (unsigned)p.pad * (unsigned)(p.lda * ES);
     const unsigned a_bytes = (unsigned)((((long)nbatch * p.Lin - 1) * p.lda + p.Cp) * ES) + a_shift;
@@ -417,7 +409,7 @@ __device__ __forceinline__ void gemm_h2_tile(const GemmArgs& p, const int m0, co
     unsigned a_voff[GA]; int a_lpos[GA];
 #pragma unroll
     for (int j = 0; j < GA; ++j) {
-        const int row = (lw + NL * j) * RPI + lrow;
+        const int row = (wave + NW * j) * RPI + lrow;
         const int m = m0 + row;
         const int lc = lslot ^ swz<8>(row);
         const unsigned chunk = (unsigned)((2 * (lc & 3) + (lc >> 2)) * 16);
@@ -434,7 +426,7 @@ __device__ __forceinline__ void gemm_h2_tile(const GemmArgs& p, const int m0, co
     unsigned b_voff[GB];
 #pragma unroll
     for (int j = 0; j < GB; ++j) {
-        const int row = (lw + NL * j) * RPI + lrow;
+        const int row = (wave + NW * j) * RPI + lrow;
         const int n = n0 + row + (SEG3 ? (row / (BN / 3)) * (p.N / 3 - BN / 3) : 0);
         const int lc = lslot ^ swzW<8>(row);
         b_voff[j] = n < p.N ? (unsigned)n * (unsigned)(p.K * ES) + (unsigned)((2 * (lc & 3) + (lc >> 2)) * 16) : OOB;
@@ -454,10 +446,10 @@ __device__ __forceinline__ void gemm_h2_tile(const GemmArgs& p, const int m0, co
         if constexpr (J < GA) {
             unsigned vo = a_voff[J];
             if (is_conv) vo = (unsigned)(a_lpos[J] + is_tap) < (unsigned)p.Lin ? vo : OOB;
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(a_rsrc, (__attribute__((address_space(3))) void*)(base + (lw + NL * J) * 1024),
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(a_rsrc, (__attribute__((address_space(3))) void*)(base + (wave + NW * J) * 1024),
                                                      16, (int)vo, (int)soff_a, 0, 0);
         } else {
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(w_rsrc, (__attribute__((address_space(3))) void*)(base + BM * RB + (lw + NL * (J - GA)) * 1024),
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(w_rsrc, (__attribute__((address_space(3))) void*)(base + BM * RB + (wave + NW * (J - GA)) * 1024),
                                                      16, (int)b_voff[J - GA], (int)soff_w, 0, 0);
         }
     };
@@ -478,48 +470,24 @@ __device__ __forceinline__ void gemm_h2_tile(const GemmArgs& p, const int m0, co
         });
     };
 
-    // ---- epilogue operands fetched ahead of the K-loop (compute waves; oldest entries of their memory queue) ----
     const int fr = lane & 15, fg = lane >> 4;
     const bool vt_tile = p.out_t != nullptr && n0 >= p.t_col0;       // block-uniform
-    const int ncol_n = p.out_t ? p.t_col0 : p.N;     // columns below this go to out / out_f32
-    h2_t* __restrict__ out = (h2_t*)p.out;
-    constexpr int PM = PRE ? FM : 1, PP = PRE ? FP : 1;
-    float pre_r[PM][PP][8];
-    if constexpr (PRE) {
-#pragma unroll
-        for (int jp = 0; jp < PP; ++jp) {
-            const int n = n0 + wn * WTN + jp * 32 + fg * 8;
-#pragma unroll
-            for (int i = 0; i < PM; ++i) {
-                const int m = m0 + wm * WTM + i * 16 + fr;
-#pragma unroll
-                for (int e = 0; e < 8; ++e) pre_r[i][jp][e] = 0.f;
-                if (is_compute && !vt_tile && p.res && m < p.M && n + 8 <= ncol_n) {
-                    if (p.res_is_f32) load8<float>((const float*)p.res + (long)m * p.ldr + n, pre_r[i][jp]);
-                    else h2_load8((const h2_t*)p.res + (long)m * p.ldr + n, pre_r[i][jp], p.h2i);
-                }
-            }
-        }
-    }
-
     f32x4 acc[FM][FN];
 #pragma unroll
     for (int i = 0; i < FM; ++i)
 #pragma unroll
         for (int j = 0; j < FN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-    const int nk = (p.ksplit > 1 ? (nk_all - kt0 < p.nk_split ? nk_all - kt0 : p.nk_split) : nk_all) / KPB;      // ring slots to walk (K-tiles: even, gemm_h2.hip)
-    if (is_loader) {
+    const int nk = (p.ksplit > 1 ? (nk_all - kt0 < p.nk_split ? nk_all - kt0 : p.nk_split) : nk_all) / KPB;      // ring slots to walk
 #pragma unroll
-        for (int s = 0; s < NS - 1; ++s)
-            if (s < nk) issue();
-    }
+    for (int s = 0; s < NS - 1; ++s)
+        if (s < nk) issue();
     // folded LayerNorms (GemmArgs::ln_stats / rs_stats): the wave tile's partial row statistics are requested here, behind the first K-tiles'
     // DMA (in front of it, a register-reuse wait of the compiler stalled the DMA issue), ...
     LnPart<LNF ? WTM : 16> lnp, rsp;
     if constexpr (LNF) {
-        if (is_compute && p.ln_stats && !EMAGE_DBG(p, 256)) ln_wave_load<WTM>(p.ln_stats, m0 + wm * WTM, p.M, lane, lnp);       // (tools, timing only: bit 256 = no statistics loads,
-        if (is_compute && p.rs_stats && !EMAGE_DBG(p, 256)) ln_wave_load<WTM>(p.rs_stats, m0 + wm * WTM, p.M, lane, rsp);       //  512 = no merge, 1024 = no c / gamma / beta loads)
+        if (p.ln_stats && !EMAGE_DBG(p, 256)) ln_wave_load<WTM>(p.ln_stats, m0 + wm * WTM, p.M, lane, lnp);       // (tools, timing only: bit 256 = no statistics loads,
+        if (p.rs_stats && !EMAGE_DBG(p, 256)) ln_wave_load<WTM>(p.rs_stats, m0 + wm * WTM, p.M, lane, rsp);       //  512 = no merge, 1024 = no c / gamma / beta loads)
     }
 
     // ---- folded LayerNorms (GemmArgs::ln_stats / rs_stats): (mu, rstd) of the lane's FM rows ----
@@ -572,154 +540,76 @@ __device__ __forceinline__ void gemm_h2_tile(const GemmArgs& p, const int m0, co
         constexpr int NM = 3 * FM * FN;
 
         auto wait_landed = [&](const int st) {
-            // the loading waves wait until stage st + AH has landed; stages issued after it may stay in flight
+            // stage st has landed; stages issued after it may stay in flight
             const int last_issued = (st + NS - 2 < nk - 1) ? st + NS - 2 : nk - 1;
-            const int infl = last_issued - (st + AH);      // 0 .. NS - 2 ring slots stay in flight behind the one needed now
-            if constexpr (NS <= 4) {
-                if (NS >= 4 && infl >= 2) wait_vmcnt<2 * G * KPB>();
-                else if (NS >= 3 && infl >= 1) wait_vmcnt<G * KPB>();
-                else wait_vmcnt<0>();
-            } else {                                       // deep rings (round 5: lone blocks on small grids): one counted wait per depth
-                static_for<NS - 1>([&](auto kc) {
-                    constexpr int KQ = decltype(kc)::value;
-                    if (infl == KQ) wait_vmcnt<KQ * G * KPB>();
-                });
-            }
+            const int infl = last_issued - st;             // 0 .. NS - 2 ring slots stay in flight behind the one needed now
+            if (NS >= 4 && infl >= 2) wait_vmcnt<2 * G * KPB>();
+            else if (NS >= 3 && infl >= 1) wait_vmcnt<G * KPB>();
+            else wait_vmcnt<0>();
         };
 
         // DILV: the DMA instructions of the stage issued in this iteration are spread between the MFMAs instead of in front of them
         // (a barrier per K-tile keeps every wave in the same phase: a burst of DMA issues right behind it stalls all waves on
         // the texture path while the matrix pipes idle; behind an MFMA, one wave's issue stall is covered by its SIMD partner)
         constexpr int DSTEP = NM / G > 0 ? NM / G : 1;
-        if constexpr (!PIPE) {
-            unsigned sb = 0;
-            for (int st = 0; st < nk; ++st) {
-                tr();
-                if (is_loader) wait_landed(st);
-                tr();
-                __builtin_amdgcn_s_barrier();
-                tr();
-                const bool do_issue = is_loader && st + NS - 1 < nk;
-                if (!(DILV && NLW == 0) && do_issue) issue();
-                tr();
-                if (is_compute) {
-                  static_for<KPB>([&](auto subc) {
-                    constexpr int SB2 = decltype(subc)::value * SUB;
-                    Frag f;
-                    if (!EMAGE_DBG(p, 2)) static_for<NR>([&](auto rc) { read_one(rc, f, sb + SB2); });        // (tools, timing only: bit 2 = no fragment reads)
-                    else { static_for<FM>([&](auto ic) { f.ah[decltype(ic)::value] = f.al[decltype(ic)::value] = u32x4{0u, 0u, 0u, 0u}; });
-                           static_for<FN>([&](auto jc) { f.wh[decltype(jc)::value] = f.wl[decltype(jc)::value] = u32x4{0u, 0u, 0u, 0u}; }); }
-                    tr();
-                    wait_lgkmcnt<FN + FM>();              // A hi and W lo are there: first sweep
-                    __builtin_amdgcn_sched_barrier(0);
-                    tr();
-                    static_for<NM>([&](auto qc) {
-                        constexpr int Q = decltype(qc)::value;
-                        if constexpr (Q == FM * FN) {
-                            __builtin_amdgcn_sched_barrier(0);
-                            wait_lgkmcnt<0>();
-                            __builtin_amdgcn_sched_barrier(0);
-                        }
-                        if (!EMAGE_DBG(p, 4)) mma_one(qc, f);                                                 // (bit 4 = no MFMAs)
-                        if constexpr (DILV && NLW == 0 && Q % DSTEP == DSTEP - 1 && Q / DSTEP < G) {
-                            __builtin_amdgcn_sched_barrier(0);
-                            if (do_issue) issue_piece(IC<Q / DSTEP>{});
-                            __builtin_amdgcn_sched_barrier(0);
-                        }
-                    });
-                    if constexpr (decltype(subc)::value + 1 < KPB) __builtin_amdgcn_sched_barrier(0);
-                  });
-                    if constexpr (DILV && NLW == 0) {
-                        static_for<G>([&](auto jc) {      // pieces the interleave did not reach
-                            if constexpr (decltype(jc)::value >= NM / DSTEP) { if (do_issue) issue_piece(jc); }
-                        });
-                        if (do_issue) issue_advance();
-                    }
-                    __builtin_amdgcn_sched_barrier(0);
-                    tr();
-                }
-                sb += STAGE;
-                if (sb == NS * STAGE) sb = 0;
-            }
-        } else {
-            Frag f0, f1;
-            // prologue: stage 0 landed -> first fragments
-            if (is_loader) {
-                const int last_issued = (NS - 2 < nk - 1) ? NS - 2 : nk - 1;
-                if (NS >= 4 && last_issued >= 2) wait_vmcnt<2 * G>();
-                else if (NS >= 3 && last_issued >= 1) wait_vmcnt<G>();
-                else wait_vmcnt<0>();
-            }
+        unsigned sb = 0;
+        for (int st = 0; st < nk; ++st) {
+            tr();
+            wait_landed(st);
+            tr();
             __builtin_amdgcn_s_barrier();
-            if (is_compute) {
-                static_for<NR>([&](auto rc) { read_one(rc, f0, 0u); });
-                wait_lgkmcnt<0>();
-            }
-            unsigned sb = STAGE;                          // ring offset of stage st + 1
-            // reads of the next K-tile are spread between this K-tile's MFMAs: one read after every RSTEP-th MFMA
-            constexpr int RSTEP = NM / NR > 0 ? NM / NR : 1;
-            auto step = [&](const int st, Frag& cur, Frag& nxt) {
+            tr();
+            const bool do_issue = st + NS - 1 < nk;
+            if (!DILV && do_issue) issue();
+            tr();
+            static_for<KPB>([&](auto subc) {
+                constexpr int SB2 = decltype(subc)::value * SUB;
+                Frag f;
+                if (!EMAGE_DBG(p, 2)) static_for<NR>([&](auto rc) { read_one(rc, f, sb + SB2); });        // (tools, timing only: bit 2 = no fragment reads)
+                else { static_for<FM>([&](auto ic) { f.ah[decltype(ic)::value] = f.al[decltype(ic)::value] = u32x4{0u, 0u, 0u, 0u}; });
+                       static_for<FN>([&](auto jc) { f.wh[decltype(jc)::value] = f.wl[decltype(jc)::value] = u32x4{0u, 0u, 0u, 0u}; }); }
                 tr();
-                if (is_loader) wait_landed(st);
+                wait_lgkmcnt<FN + FM>();              // A hi and W lo are there: first sweep
+                __builtin_amdgcn_sched_barrier(0);
                 tr();
-                __builtin_amdgcn_s_barrier();
-                tr();
-                const bool do_issue = is_loader && st + NS - 1 < nk;
-                if (!(DILV && NLW == 0) && do_issue) issue();
-                tr();
-                if (is_compute) {
-                    const bool more = st + 1 < nk;        // wave-uniform
-                    static_for<NM>([&](auto qc) {
-                        constexpr int Q = decltype(qc)::value;
-                        mma_one(qc, cur);
-                        if constexpr (Q % RSTEP == RSTEP - 1 && Q / RSTEP < NR) {
-                            __builtin_amdgcn_sched_barrier(0);
-                            if (more) read_one(IC<Q / RSTEP>{}, nxt, sb);
-                            __builtin_amdgcn_sched_barrier(0);
-                        }
-                        if constexpr (DILV && NLW == 0 && Q % DSTEP == DSTEP / 2 && Q / DSTEP < G) {
-                            __builtin_amdgcn_sched_barrier(0);
-                            if (do_issue) issue_piece(IC<Q / DSTEP>{});
-                            __builtin_amdgcn_sched_barrier(0);
-                        }
-                    });
-                    static_for<NR>([&](auto rc) {         // reads the interleave did not reach
-                        constexpr int R = decltype(rc)::value;
-                        if constexpr (R >= NM / RSTEP) { if (more) read_one(rc, nxt, sb); }
-                    });
-                    if constexpr (DILV && NLW == 0) {
-                        static_for<G>([&](auto jc) {
-                            if constexpr (decltype(jc)::value >= (NM + DSTEP - 1 - DSTEP / 2) / DSTEP) { if (do_issue) issue_piece(jc); }
-                        });
-                        if (do_issue) issue_advance();
+                static_for<NM>([&](auto qc) {
+                    constexpr int Q = decltype(qc)::value;
+                    if constexpr (Q == FM * FN) {
+                        __builtin_amdgcn_sched_barrier(0);
+                        wait_lgkmcnt<0>();
+                        __builtin_amdgcn_sched_barrier(0);
                     }
-                    tr();
-                    wait_lgkmcnt<0>();
-                    __builtin_amdgcn_sched_barrier(0);
-                    tr();
-                }
-                sb += STAGE;
-                if (sb == NS * STAGE) sb = 0;
-            };
-            for (int st = 0; st < nk; st += 2) {          // nk is even (Cp % 64 == 0)
-                step(st, f0, f1);
-                step(st + 1, f1, f0);
+                    if (!EMAGE_DBG(p, 4)) mma_one(qc, f);                                                 // (bit 4 = no MFMAs)
+                    if constexpr (DILV && Q % DSTEP == DSTEP - 1 && Q / DSTEP < G) {
+                        __builtin_amdgcn_sched_barrier(0);
+                        if (do_issue) issue_piece(IC<Q / DSTEP>{});
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
+                });
+                if constexpr (decltype(subc)::value + 1 < KPB) __builtin_amdgcn_sched_barrier(0);
+            });
+            if constexpr (DILV) {
+                static_for<G>([&](auto jc) {          // pieces the interleave did not reach
+                    if constexpr (decltype(jc)::value >= NM / DSTEP) { if (do_issue) issue_piece(jc); }
+                });
+                if (do_issue) issue_advance();
             }
+            __builtin_amdgcn_sched_barrier(0);
+            tr();
+            sb += STAGE;
+            if (sb == NS * STAGE) sb = 0;
         }
     };
     tr();
     if (vt_tile) kloop(IC<1>{}); else kloop(IC<0>{});
     tr();
 
-    if (!is_compute) { if constexpr (TRACE) { if (p.trace && blockIdx.x == 0 && lane == 0) p.trace[wave * 512] = (unsigned long long)tr_n; } __syncthreads(); return; }
-    if constexpr (PRE && NLW > 0) wait_vmcnt<0>();
 
     if constexpr (SKF) {
         if (p.sk_count) {
             // ---- split-K fix-up: this block's accumulators go to its slot of the workspace (write-through: other XCDs' L2s are not coherent);
             // the last block of the tile to arrive adds the slots in slice order (the same bits whoever is last) and goes on to the epilogue ----
-            static_assert(NLW == 0, "every wave computes");
-            constexpr int NF = FM * FN, NT = NCW * 64;
+            constexpr int NF = FM * FN, NT = NW * 64;
             const int tile_id = (m0 / BM) * p.tiles_n + n0 / BN;
             const unsigned slot_bytes = (unsigned)(NT * NF * 16);
             const __amdgpu_buffer_rsrc_t ws_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)p.sk_ws, 0, (unsigned)(p.tiles_m * p.tiles_n * p.ksplit) * slot_bytes, 0x00020000);
@@ -769,7 +659,7 @@ __device__ __forceinline__ void gemm_h2_tile(const GemmArgs& p, const int m0, co
         epi(acc, m0 + wm * WTM, wm, wn, fr, fg, ln_mu, ln_rs);
         return;
     }
-    h2_tile_epilogue<FM, FN, false, PRE, PM, PP, LNF, SKF>(p, acc, m0 + wm * WTM, n0 + wn * WTN, fr, fg, vt_tile, pre_r, split, ln_mu, ln_rs, rs_mu, rs_rs);
+    h2_tile_epilogue<FM, FN, false, LNF, SKF>(p, acc, m0 + wm * WTM, n0 + wn * WTN, fr, fg, vt_tile, split, ln_mu, ln_rs, rs_mu, rs_rs);
     if (vt_tile) { __syncthreads(); return; }
     tr();
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");

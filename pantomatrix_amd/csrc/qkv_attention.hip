@@ -113,7 +113,7 @@ __global__ __launch_bounds__(QA_THREADS, 1) void qkv_attn_kernel(QkvAttnGroup g)
             }
         });
     };
-    gemm_h2_tile<QA_BM, QA_BN, QA_WM, QA_WN, QA_NS, 0, false, false, false, false, 1, true, false, true>(p, b * QA_T, h * QA_HD, smem, 0, epi);
+    gemm_h2_tile<QA_BM, QA_BN, QA_WM, QA_WN, QA_NS, false, false, 1, true, false, true>(p, b * QA_T, h * QA_HD, smem, 0, epi);
     __syncthreads();
     const int wave = (int)(threadIdx.x >> 6);
     if (wave >= QA_T / 16) return;

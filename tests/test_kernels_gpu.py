@@ -488,10 +488,9 @@ def test_gemm_h2(case):
             _cmp(f"{case[0]}.{nm}", gt[..., :width], rf[..., :width], atol=2e-5, rtol=1e-5)
 
 
-@pytest.mark.parametrize("cfg", [100, 101, 102, 103, 105, 107, 108, 110, 111, 113, 115, 116, 119, 120, 121, 122, 123, 124, 125, 127, 130, 131, 141, 144, 148, 150, 160, 164, 166, 170, 171,
-                                 180, 181, 183, 184, 185, 186, 188, 189])
+@pytest.mark.parametrize("cfg", [100, 101, 102, 113, 116, 119, 120, 130, 141, 150, 160, 166, 170, 171, 180, 181, 183, 184, 185, 186, 189])
 def test_gemm_h2_every_tile_configuration(cfg):
-    """Every EMAGE_H2 tile configuration (wave grids, loader waves, register-pipelined / interleaved K-loops, odd fragment
+    """Every EMAGE_H2 tile configuration (wave grids, ring depths, interleaved DMA issue, two K-tiles per slot, odd fragment
     counts) on a ragged shape with a transposed tail and on a convolution with a zero-filled channel tail."""
     from pantomatrix_amd import _lib
     lib = _lib.use_tools(True)
@@ -541,14 +540,14 @@ def test_gemm_h2_dispatch_order_tiles_change_no_bit():
 def test_gemm_h2_two_ktiles_per_slot_change_no_bit():
     """Round 5 (VERDICT next #1b, "BK = 64"): the KPB = 2 configurations — two 32-k sub-tiles per ring slot and s_barrier — issue the MFMAs
     of every accumulator in the order of their KPB = 1 twins: the same bits, on a residual GEMM, a ragged V^T GEMM and a convolution.
-    Likewise the ring-of-8 tile for grids of at most one tile per CU (188: measured slower, tools only) against the three-blocks-per-CU tile (120)."""
+    Likewise the 8-wave twin (189) of the three-blocks-per-CU 64 x 64 tile (120)."""
     from pantomatrix_amd import _lib
     lib = _lib.use_tools(True)
     cases = [("kpb_res", (64, 64, 64), 768, 768, 1, 1, 0, dict(bias=True, res="h2")),
              ("kpb_vt", (3, 70, 70), 768, 2304, 1, 1, 0, dict(bias=True, vt=1536)),
              ("kpb_conv", (3, 37, 37), 337, 106, 3, 1, 1, dict(bias=True, slope=0.2, n_store=128, res=None, want="both"))]
     try:
-        for one, two in ((100, 180), (170, 181), (120, 183), (113, 184), (120, 186), (120, 188), (120, 189)):
+        for one, two in ((100, 180), (170, 181), (120, 183), (113, 184), (120, 186), (120, 189)):
             for case in cases:
                 outs = []
                 for cfg in (one, two):

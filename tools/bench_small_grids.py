@@ -1,8 +1,8 @@
 #!/usr/bin/env python
-"""A/B of the EMAGE_H2 dispatch for grids of at most one tile per CU (config 188: a lone 64 x 64 block per CU with a ring of 8 K-tiles; round 5):
-ONE clip (128 frames, 28 s), 8 clips and the 64-clip BASELINE batch through `runtime.ClipRunner` graph replays, tools library,
-`emage_set_tuning` key 5 = 1048576 (config 189: the tile on 8 waves) / 524288 (config 188 for such grids) against 131072 (neutral: the shipped dispatch, every such launch on the three-blocks-per-CU tile).
-Measured in round 5 (profiles/r05_small_grids_ring_of_8_ab.txt, where the tree still SHIPPED 188 and 262144 switched it off): slower — not shipped.
+"""A/B of the EMAGE_H2 dispatch for grids of at most one tile per CU (round 5): ONE clip (128 frames, 28 s), 8 clips and the 64-clip BASELINE
+batch through `runtime.ClipRunner` graph replays, tools library, `emage_set_tuning` key 7 = a 64 x 64 configuration for such grids (189: the tile on
+8 waves) against 0 (the shipped dispatch, every such launch on the three-blocks-per-CU tile 120).  The other arm measured in round 5, a lone block
+per CU with a ring of 8 K-tiles (profiles/r05_small_grids_ring_of_8_ab.txt), was slower and is removed (see history).
 Prints one JSON line per arm; the results of the two arms are compared bit for bit (same tile, same MFMA order)."""
 import json
 import os
@@ -25,7 +25,7 @@ def main():
     cases = (("b1_128f", 1, synthetic.samples_for_frames(128), 30), ("b1_28s", 1, 448000, 8), ("b8_128f", 8, synthetic.samples_for_frames(128), 20),
              ("b64_128f", 64, synthetic.samples_for_frames(128), 20))
     outs = {}
-    arms = [int(x) for x in sys.argv[1].split(",")] if len(sys.argv) > 1 else [189, 188, 0]      # EMAGE_H2 configuration ids for the lone-block grids; 0 = shipped (120)
+    arms = [int(x) for x in sys.argv[1].split(",")] if len(sys.argv) > 1 else [189, 0]      # EMAGE_H2 configuration ids for the lone-block grids; 0 = shipped (120)
     for rep in range(2):
         for small_cfg in arms:
             lib.emage_set_tuning(5, 131072)

@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Phase timeline of one block of an instrumented EMAGE_H2 tile kernel (configs 201 / 203 / 205 / 241): s_memtime stamps per wave."""
+"""Phase timeline of one block of an instrumented EMAGE_H2 tile kernel (configs 201 / 241): s_memtime stamps per wave."""
 import ctypes as C, os, sys
 import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -18,7 +18,7 @@ w, ws = ops.split_f16_weights_h2((torch.randn(n, k, generator=g) / k ** 0.5).to(
 bias = torch.randn(n, generator=g).to(dev)
 res = torch.randn(m, n, generator=g).to(dev)
 out, outf = torch.zeros(m, n, device=dev), torch.zeros(m, n, device=dev)
-for cfg in [int(c) for c in (sys.argv[1] if len(sys.argv) > 1 else "201,203,205,241").split(",")]:
+for cfg in [int(c) for c in (sys.argv[1] if len(sys.argv) > 1 else "201,241").split(",")]:
     trace = torch.zeros(16 * 512, dtype=torch.int64, device=dev)
     raw.emage_h2_set_trace(C.c_void_p(trace.data_ptr()))
     lib.emage_set_tuning(4, cfg)

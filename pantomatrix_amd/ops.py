@@ -1059,7 +1059,7 @@ def col_sum(x, y=None, out=None, accumulate=False, defer=None):
     m, c = x.shape
     if out is None:                       # the finalize launch WRITES every column unless `accumulate`: no zero fill
         out, accumulate, defer = torch.empty(c, dtype=torch.float32, device=x.device), False, None
-    ws = torch.empty(((m + 63) // 64) * c, dtype=torch.float64, device=x.device)         # one partial per chunk of >= 64 rows (csrc/train.hip STAT_CHUNK)
+    ws = torch.empty(((m + 63) // 64) * c, dtype=torch.float64, device=x.device)         # one partial per chunk of >= 64 rows (csrc/col_reduce.h STAT_CHUNK)
     if defer is not None:
         _col_sum(x, y, None, False, ws)
         defer.add(ws, col_sum_chunks(m), c, out, accumulate)

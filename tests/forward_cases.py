@@ -143,7 +143,7 @@ def layernorm_refused_args(dev, which):
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
-# BatchNorm statistics (train.hip): float64 chunk partials (stat_rows(M) rows each), finalize over 16 lanes
+# BatchNorm statistics (train.hip, col_reduce.h): float64 chunk partials (stat_rows(M) rows each), finalize over 16 lanes
 # ---------------------------------------------------------------------------------------------------------------------------------
 BN_M = (1, 2, 63, 64, 65, 257, 1025, 33001)     # 33 001: 68 rows per chunk (> STAT_CHUNK), 486 chunks, 31 per finalize lane
 BN_CONST, BN_CONST_FULL = 2.5, 1000.1           # short mantissa: M v^2 is exact in float64 -> variance exactly 0; full mantissa: only up to the subtraction

@@ -1,4 +1,4 @@
-"""The case table of the gradient-norm / clipping kernels (csrc/train.hip: emage_grad_sumsq_multi, emage_adam_multi_scaled,
+"""The case table of the gradient-norm / clipping kernels (csrc/optim.hip: emage_grad_sumsq_multi, emage_adam_multi_scaled,
 emage_scale_multi): seeded inputs, float64 references, tolerances derived from the arithmetic.
 
 Every `check_*` takes `impl`: `pantomatrix_amd.ops` (the HIP kernels on the device: tests/test_grad_clip_gpu.py) or `tests/fake_ops.py` with

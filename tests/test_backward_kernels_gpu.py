@@ -1,5 +1,5 @@
-"""The backward kernels of the training step (csrc/train.hip), each called through pantomatrix_amd.ops on the MI355X, against
-float64 torch autograd on the CPU of the forward operation the kernel differentiates — at the shapes the step runs, at ragged and
+"""The backward kernels of the training step (csrc/train_backward.hip; the loss gradients: csrc/train.hip), each called through
+pantomatrix_amd.ops on the MI355X, against float64 torch autograd on the CPU of the forward operation the kernel differentiates — at the shapes the step runs, at ragged and
 degenerate shapes, and at the edges where such kernels go wrong (peaked softmax rows, large row means, chunk boundaries of the
 float64 reductions, padding columns).
 
@@ -100,7 +100,7 @@ MFMA_CASES = [(1, True, False), (1, False, False), (3, True, False), (3, False, 
 @pytest.mark.parametrize("b,masked,peaked", MFMA_CASES,
                          ids=[f"b{b}_{'dropout' if mk else 'nomask'}{'_peaked' if pk else ''}" for b, mk, pk in MFMA_CASES])
 def test_attention_backward_mfma_path(b, masked, peaked):
-    """The path every attention of a training step takes (train.hip: emage_attention_backward sends Tq = Tk = 64, hd = 192 with
+    """The path every attention of a training step takes (train_backward.hip: emage_attention_backward sends Tq = Tk = 64, hd = 192 with
     16-byte aligned operands and every leading dimension % 4 == 0 to attention_backward_mfma_kernel): H = 4 heads, q / k / dO as column
     blocks of one ld = 2304 buffer, V^T with spare rows (vt_rows > H hd) and ldvt in {64, 96}.  The SAME data with a leading dimension
     that is not a multiple of 4 takes the scalar kernel: both match float64 and each other."""
@@ -342,6 +342,9 @@ def test_bn_backward(m):
         for nm, buf, rf, tol in (("dgamma", gb, dg_r, tdg), ("dbeta", bb, db_r, tdb), ("sum dy xhat", sb, dg_r, tdg), ("sum dy", sdb, db_r, tdb)):
             _nan_outside(f"{tag}.{nm}", buf, slice(3, 3 + c))
             _cmp(f"{tag}.{nm}", buf[3:3 + c], rf, tol)
+        # emage_bn_backward IS its two halves with count = M (the same launches): the same bits
+        assert torch.equal(dxb[1:1 + m, 2:2 + c], dxb2[1:1 + m, 2:2 + c]), f"{tag}: dx of the one-call form differs from the split form with count = M"
+        assert torch.equal(gb[3:3 + c], sb[3:3 + c]) and torch.equal(bb[3:3 + c], sdb[3:3 + c]), f"{tag}: dgamma / dbeta differ from the two sums"
         # two shards with global statistics and the global count
         m1 = m // 2 + 1 if m > 2 else 1
         shards = [(0, m1), (m1, m)]

@@ -1,4 +1,4 @@
-"""The forward reductions, LayerNorm, optimizer and rotation kernels that training and decode depend on (csrc/train.hip, elementwise.hip /
+"""The forward reductions, LayerNorm, optimizer and rotation kernels that training and decode depend on (csrc/train.hip, optim.hip, elementwise.hip /
 ln_row.h, vq.hip, motion.hip / rot_math.h), each called through pantomatrix_amd.ops on the MI355X against a float64 reference of the
 mathematical operation on the CPU, at the shapes where such kernels go wrong: lane, chunk and grid-stride boundaries, strided views,
 constant rows, large means, branch thresholds.  The cases, references, tolerances and wrong references live in tests/forward_cases.py

@@ -693,6 +693,39 @@ int emage_mul_add_philox(const float* a, int lda, float p, unsigned long long se
 int emage_adam_step_dev(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, long n, const int* step,
                         float lr, float beta1, float beta2, float eps, float weight_decay, void* stream);
 
+/* A training batch cut out of a device-resident clip store in ONE launch (datasets/beat2.py:97-129 BEAT2DatasetEamgeFootContact.__getitem__ and the
+ * DataLoader's collation, train_emage_audio.py:277), no host work per step.  The store: every recording's frames end to end in four flat fp32 arrays
+ * poses (total_frames, 165), expressions (.., 100), trans (.., 3), contact (.., 4) and its audio end to end in one array of total_samples samples,
+ * audio_fmt EMAGE_PCM_S16 (decoded x * 2^-15, what a 16-bit PCM file loads as) or EMAGE_PCM_F32; `clips`: n_clips rows of three 64-bit words
+ * {first frame, first sample, recording id (unused here)}.  Batch row b takes clip id = order[p * batch + b] with p = *cursor mod n_batches (cursor:
+ * one int32 on the device, so a captured graph walks the epoch; past the epoch's end it wraps to the first batch instead of reading behind the
+ * `order` buffer of n_order >= n_batches * batch int32 ids) and copies `frames` rows of each motion array and frames * samples_per_frame samples:
+ *   out_audio[b * ld_audio + i];  out_X[b * X_clip_pitch + t * X_row_pitch + c]     (pitches in elements: the outputs may be strided views)
+ * Every access is one element at its natural alignment (clips start at any frame and any sample).  An id outside [0, n_clips) zero-fills batch
+ * row b and ORs 1 into *status (one int32 on the device, sticky: the caller clears it); a table row that does not lie inside the flat arrays
+ * zero-fills likewise and ORs 2.  Nothing outside the arrays is ever read. */
+#define EMAGE_CLIP_POSE_DIMS 165
+#define EMAGE_CLIP_EXPR_DIMS 100
+#define EMAGE_CLIP_TRANS_DIMS 3
+#define EMAGE_CLIP_CONTACT_DIMS 4
+int emage_gather_clips(const int* order, long n_order, const int* cursor, int n_batches, int batch,
+                       const long long* clips, long n_clips, int frames, int samples_per_frame,
+                       const float* poses, const float* expressions, const float* trans, const float* contact, long total_frames,
+                       int audio_fmt, const void* audio, long total_samples,
+                       float* out_audio, long ld_audio,
+                       float* out_poses, long poses_clip_pitch, long poses_row_pitch,
+                       float* out_expressions, long expressions_clip_pitch, long expressions_row_pitch,
+                       float* out_trans, long trans_clip_pitch, long trans_row_pitch,
+                       float* out_contact, long contact_clip_pitch, long contact_row_pitch,
+                       int* status, void* stream);
+
+/* The random motion mask of train_emage_audio.py:163-165 (torch.rand(bs, t, 337) < mask_ratio, as float) drawn on the device:
+ *   out[i] = (u_i < (float)(a * iteration + b)) ? 1 : 0,   u_i = (word >> 8) * 2^-24 of Philox4x32-10
+ * with key = seed, counter = (i / 4, mask_id, iteration), element i taking word i % 4 — the convention of emage_dropout_mask.  iteration: one int32
+ * on the device (a captured step draws a fresh mask with a fresh ratio at every replay); a * iteration + b is evaluated in double and rounded to
+ * fp32 once, as torch rounds the reference's Python float for the comparison.  The ratio is not clamped: above 1 every element is 1. */
+int emage_motion_mask(float* out, long n, double a, double b, unsigned long long seed, unsigned mask_id, const int* iteration, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

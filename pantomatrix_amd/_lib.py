@@ -12,7 +12,7 @@ TOOLS_LIB_PATH = os.path.join(_HERE, "csrc", "libemage_hip_tools.so")   # -DEMAG
 F32, BF16, F16X3, H2 = 0, 1, 2, 3
 PCM_S16, PCM_S24, PCM_S32, PCM_F32 = 0, 1, 2, 3       # EMAGE_PCM_*: the sample formats of emage_audio_resample
 AUDIO_TILE = 1024                                     # EMAGE_AUDIO_TILE: outputs per tile of emage_audio_resample
-ABI_VERSION = 20                                      # unchanged by the gradient-norm entry points: they were ADDED, no existing prototype moved
+ABI_VERSION = 20                                      # unchanged by the gradient-norm and clip-store entry points: they were ADDED, no existing prototype moved
 
 _p, _i, _f, _l, _d = C.c_void_p, C.c_int, C.c_float, C.c_long, C.c_double
 
@@ -98,6 +98,8 @@ SIGNATURES = {
     "emage_grad_sumsq_multi": [_p, _p, _p, _i, _i, _d, _d, _p, _p, _p, _p, _p, _l, _p],
     "emage_scale_multi": [_p, _p, _p, _i, _p, _p],
     "emage_dropout_mask": [_p, _l, _f, C.c_ulonglong, C.c_uint, _p, _i, _p],
+    "emage_gather_clips": [_p, _l, _p, _i, _i, _p, _l, _i, _i, _p, _p, _p, _p, _l, _i, _p, _l, _p, _l, _p, _l, _l, _p, _l, _l, _p, _l, _l, _p, _l, _l, _p, _p],
+    "emage_motion_mask": [_p, _l, _d, _d, C.c_ulonglong, C.c_uint, _p, _p],
     "emage_mul_add": [_p, _i, _p, _i, _i, _p, _i, _p, _i, _i, _i, _p],
     "emage_mul_add_philox": [_p, _i, _f, C.c_ulonglong, C.c_uint, _p, _i, _i, _p, _i, _p, _i, _i, _i, _p],
     "emage_layernorm": [_i, _p, _i, _p, _p, _f, _p, _i, _p, _p, _i, _i, _i, _p],

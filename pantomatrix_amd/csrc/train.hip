@@ -13,6 +13,7 @@
 // Statistics are accumulated in float64 (one rounding to fp32 at the end): the batch has up to ~4e5 rows per channel.
 // The backward kernels are in train_backward.hip, the optimizer in optim.hip, the float64 reduction pieces all three share in col_reduce.h.
 #include "col_reduce.h"
+#include "philox.h"
 #include <math.h>
 
 namespace {
@@ -154,15 +155,7 @@ __global__ __launch_bounds__(256) void nll_grad_kernel(const float* __restrict__
 //   keep  <=>  (word >> 8) * 2^-24 >= p      (24 random bits, uniform on [0, 1))
 // The stream is this library's own (documented here, pinned bit for bit by tests/test_train_rng.py against a numpy Philox); it is
 // NOT torch's fused-dropout stream: runs are reproducible for a seed, distribution-identical to the reference, not draw-identical.
-__device__ __forceinline__ void philox4x32_10(unsigned (&c)[4], unsigned k0, unsigned k1) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const unsigned long long p0 = (unsigned long long)0xD2511F53u * c[0], p1 = (unsigned long long)0xCD9E8D57u * c[2];
-        const unsigned n0 = (unsigned)(p1 >> 32) ^ c[1] ^ k0, n1 = (unsigned)p1, n2 = (unsigned)(p0 >> 32) ^ c[3] ^ k1, n3 = (unsigned)p0;
-        c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-}
+// The generator itself, philox4x32_10, is in philox.h (data.hip draws the motion mask from it too).
 // out = a * keep (+ b) with the keep mask DRAWN IN PLACE: element (mask row mr, column c) is element mr * C + c of the mask
 // dropout_mask_kernel would have written for the same key — the same bits as emage_dropout_mask + emage_mul_add, without the mask in
 // memory (a training forward holds ~0.9 GB of (T, B, d) masks for its backward otherwise; the backward draws them again from the key).

@@ -1394,8 +1394,8 @@ def dropout_mask(out, p, seed, mask_id, step):
     return out
 
 
-def philox_dropout_reference(n, p, seed, mask_id, step):
-    """numpy restatement of emage_dropout_mask (Philox4x32-10, csrc/train.hip) — tests and the CPU stand-ins."""
+def _philox_uniform_reference(n, seed, mask_id, step):
+    """The first n uniforms u_i = (word >> 8) * 2^-24 of the Philox4x32-10 stream (csrc/philox.h) keyed by `seed`, counter (i / 4, mask_id, step)."""
     import numpy as np
     nb = (n + 3) // 4
     b = np.arange(nb, dtype=np.uint64)
@@ -1408,8 +1408,78 @@ def philox_dropout_reference(n, p, seed, mask_id, step):
         c = [((p1 >> np.uint64(32)) ^ c[1] ^ k0) & m32, p1 & m32, ((p0 >> np.uint64(32)) ^ c[3] ^ k1) & m32, p0 & m32]
         k0, k1 = (k0 + np.uint64(0x9E3779B9)) & m32, (k1 + np.uint64(0xBB67AE85)) & m32
     words = np.stack(c, axis=1).reshape(-1)[:n]
-    u = (words >> np.uint64(8)).astype(np.float32) * np.float32(1.0 / 16777216.0)
+    return (words >> np.uint64(8)).astype(np.float32) * np.float32(1.0 / 16777216.0)
+
+
+def philox_dropout_reference(n, p, seed, mask_id, step):
+    """numpy restatement of emage_dropout_mask (Philox4x32-10, csrc/train.hip) — tests and the CPU stand-ins."""
+    import numpy as np
+    u = _philox_uniform_reference(n, seed, mask_id, step)
     return np.where(u >= np.float32(p), np.float32(1.0 / (1.0 - p)), np.float32(0.0)).astype(np.float32)
+
+
+def motion_mask_reference(n, a, b, seed, mask_id, iteration):
+    """numpy restatement of emage_motion_mask (csrc/data.hip): (u_i < float32(a * iteration + b)) as float32, the ratio evaluated in double."""
+    import numpy as np
+    u = _philox_uniform_reference(n, seed, mask_id, int(iteration))
+    return (u < np.float32(float(a) * float(int(iteration)) + float(b))).astype(np.float32)
+
+
+@_op("motion_mask", "(Tensor(a!) out, float a, float b, int seed, int mask_id, Tensor iteration) -> ()")
+def _motion_mask(out, a, b, seed, mask_id, iteration):
+    check(_lib.load().emage_motion_mask(_ptr(out), out.numel(), a, b, seed & 0xFFFFFFFFFFFFFFFF, mask_id & 0xFFFFFFFF, _ptr(iteration), _stream()), "motion_mask")
+
+
+def motion_mask(out, a, b, seed, mask_id, iteration):
+    """Fill the contiguous fp32 tensor `out` with the random motion mask of train_emage_audio.py:163-165 for the ratio a * iteration + b, drawn
+    on the device; `iteration`: a one-element int32 device tensor, read by the kernel.  See include/emage_hip.h: emage_motion_mask."""
+    _dev(out)
+    assert out.dtype == torch.float32 and out.is_contiguous()
+    assert iteration.dtype == torch.int32 and iteration.numel() == 1 and iteration.device == out.device
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    if seed >= 1 << 63:           # the op schema's `int` is a signed 64-bit word: pass the same 64 bits in two's complement
+        seed -= 1 << 64
+    _motion_mask(out, float(a), float(b), seed, int(mask_id), iteration)
+    return out
+
+
+CLIP_WIDTHS = {"motion": 165, "expressions": 100, "trans": 3, "foot_contact": 4}       # EMAGE_CLIP_*_DIMS: the row widths of a clip's four motion pieces
+
+
+@_op("gather_clips", "(Tensor order, Tensor cursor, int n_batches, Tensor clips, int frames, int samples_per_frame, Tensor poses, Tensor expressions, "
+                     "Tensor trans, Tensor contact, Tensor audio, Tensor(a!) out_audio, Tensor(b!) out_poses, Tensor(c!) out_expressions, "
+                     "Tensor(d!) out_trans, Tensor(e!) out_contact, Tensor(f!) status) -> ()")
+def _gather_clips(order, cursor, n_batches, clips, frames, samples_per_frame, poses, expressions, trans, contact, audio,
+                  out_audio, out_poses, out_expressions, out_trans, out_contact, status):
+    fmt = _lib.PCM_S16 if audio.dtype == torch.int16 else _lib.PCM_F32
+    pitches = [x for o in (out_poses, out_expressions, out_trans, out_contact) for x in (_ptr(o), o.stride(0), o.stride(1))]
+    check(_lib.load().emage_gather_clips(_ptr(order), order.numel(), _ptr(cursor), n_batches, out_audio.shape[0], _ptr(clips), clips.shape[0], frames,
+                                         samples_per_frame, _ptr(poses), _ptr(expressions), _ptr(trans), _ptr(contact), poses.shape[0], fmt, _ptr(audio),
+                                         audio.numel(), _ptr(out_audio), out_audio.stride(0), *pitches, _ptr(status), _stream()), "gather_clips")
+
+
+def gather_clips(order, cursor, n_batches, clips, arrays, out, status, *, frames, samples_per_frame):
+    """One launch fills the five batch tensors `out` (keys audio, motion, expressions, trans, foot_contact; float32, unit inner stride, any
+    outer strides) with the clips order[(cursor mod n_batches) * B + b] of a device-resident store: `arrays` holds its flat recordings under
+    the same keys (audio int16 or float32), `clips` its (n_clips, 3) int64 table {first frame, first sample, recording id}; `order` int32,
+    `cursor` and `status` one int32 each, all on the device.  See include/emage_hip.h: emage_gather_clips."""
+    _dev(out["audio"])
+    dev = out["audio"].device
+    b = out["audio"].shape[0]
+    assert order.dtype == torch.int32 and order.dim() == 1 and (order.stride(0) == 1 or order.numel() <= 1) and order.numel() >= n_batches * b
+    assert cursor.dtype == torch.int32 and cursor.numel() == 1 and status.dtype == torch.int32 and status.numel() == 1
+    assert clips.dtype == torch.int64 and clips.dim() == 2 and clips.shape[1] == 3 and clips.is_contiguous()
+    assert arrays["audio"].dtype in (torch.int16, torch.float32) and arrays["audio"].dim() == 1 and arrays["audio"].is_contiguous()
+    assert out["audio"].dtype == torch.float32 and out["audio"].dim() == 2 and out["audio"].stride(1) == 1 and out["audio"].shape[1] == frames * samples_per_frame
+    for k, w in CLIP_WIDTHS.items():
+        src, dst = arrays[k], out[k]
+        assert src.dtype == torch.float32 and src.dim() == 2 and src.shape[1] == w and src.is_contiguous() and src.shape[0] == arrays["motion"].shape[0], k
+        assert dst.dtype == torch.float32 and tuple(dst.shape) == (b, frames, w) and dst.stride(2) == 1, (k, dst.shape, dst.stride())
+    for t in (order, cursor, status, clips, *arrays.values(), *out.values()):
+        assert t.device == dev, "gather_clips: every tensor on the device of the batch"
+    _gather_clips(order, cursor, int(n_batches), clips, int(frames), int(samples_per_frame), arrays["motion"], arrays["expressions"], arrays["trans"],
+                  arrays["foot_contact"], arrays["audio"], out["audio"], out["motion"], out["expressions"], out["trans"], out["foot_contact"], status)
+    return out
 
 
 class AdamTable:

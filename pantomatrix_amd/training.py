@@ -1706,7 +1706,7 @@ class Trainer:
         self.fwd._pcache = None
 
     # ---- the step as ONE hipGraph -------------------------------------------------------------------------------------------------
-    def capture(self, batch, random_mask, dropout_masks=None):
+    def capture(self, batch, random_mask, dropout_masks=None, prologue=None):
         """Capture the whole step — re-packing the MFMA operands from the current parameters, targets, three forwards with their
         backward passes, the dropout masks (drawn on the device from the in-graph step counter unless `dropout_masks` buffers are
         given), Adam, BatchNorm buffers — into one hipGraph over the GIVEN tensors: `batch` and `random_mask` (and `dropout_masks`)
@@ -1714,6 +1714,12 @@ class Trainer:
         step at device speed instead of the ~10^4 Python-level launches of `step()`.  Both fp32-storage precisions: in f16x3 the
         split-fp16 operand scales are the ones chosen by the warm-up step's packing (a re-packing with known scales is a pure sequence
         of launches).  One eager warm-up step is run and undone.
+
+        prologue: a callable that refills the input buffers ON THE DEVICE (`data.ClipLoader.fill`: `capture(loader.batch, loader.random_mask,
+        prologue=loader.fill)`); it runs first inside the captured region, so a replay is "next batch, then the step" and the training loop's
+        only host call per step is `replay()`.  It also runs in front of the warm-up step's body; the device tensors it advances (its
+        owner's `prologue_state()`: the loader's cursor and iteration) are put back with the optimiser state, so the first replay trains on
+        the batch the counters pointed at when `capture` was called.  None (the default): the graph is what it was without the argument.
 
         Multi-process runs (round 5): the step is captured WITH its collectives — the four bucket all-reduces (started mid-backward on the
         backend's own stream: they become parallel branches of the graph), SyncBatchNorm's all-gathers and small all-reduces — when the
@@ -1740,8 +1746,13 @@ class Trainer:
         saved = {k: v.clone() for k, v in params.items()}
         done = self.steps_done                                         # a RE-capture (new loss scale / operand scales) keeps the optimiser state
         moments = {k: (st["exp_avg"].clone(), st["exp_avg_sq"].clone()) for k, st in self.state.items()}
+        owner = getattr(prologue, "__self__", None)
+        advanced = list(owner.prologue_state()) if hasattr(owner, "prologue_state") else []
+        rewind = [t.clone() for t in advanced]
         self._graph = None
         with self._deferred_range_check():
+            if prologue is not None:
+                prologue()
             self._device_step(batch, dropout_masks, random_mask)      # warm-up: lazy initialisation inside the library / the allocator, the exchange schedule
         torch.cuda.synchronize(dev)
         for k, v in saved.items():
@@ -1754,13 +1765,17 @@ class Trainer:
                 st["exp_avg"].zero_()
                 st["exp_avg_sq"].zero_()
             st["step"] = done
+        for t, v in zip(advanced, rewind):
+            t.copy_(v)
         self.steps_done = done
         self._step_counter = torch.full((1,), done, dtype=torch.int32, device=dev)
-        self._graph_inputs = (batch, random_mask, dropout_masks)       # the graph reads these buffers at every replay: keep them alive
+        self._graph_inputs = (batch, random_mask, dropout_masks, prologue)       # the graph reads these buffers at every replay: keep them alive
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph, capture_error_mode="thread_local"):
             model.invalidate_packed()                                  # so that the packing of the current parameters is part of the graph
             fwd._pcache = None
+            if prologue is not None:
+                prologue()
             self._step_counter.add_(1)
             self._graph_out, self._graph_ws = self._device_step(batch, dropout_masks, random_mask, step_counter=self._step_counter)
         self._graph, self._recapture_pending = graph, False

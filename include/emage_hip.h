@@ -726,6 +726,53 @@ int emage_gather_clips(const int* order, long n_order, const int* cursor, int n_
  * fp32 once, as torch rounds the reference's Python float for the comparison.  The ratio is not clamped: above 1 every element is 1. */
 int emage_motion_mask(float* out, long n, double a, double b, unsigned long long seed, unsigned mask_id, const int* iteration, void* stream);
 
+/* The metrics of one validation step (train_emage_audio.py:130-204, mode="val": get_rec_loss / get_cls_loss of the three eval forwards, the
+ * arg-max codes) over the REAL clips of a padded batch, in two launches (csrc/val.hip).  `entries`: a HOST array of up to
+ * EMAGE_VAL_MAX_ENTRIES rows, one per (forward, body part), validated here and carried to the device by value in the kernel arguments
+ * (nothing a captured graph must keep alive); every pointer in it is device memory:
+ *   rec (M, C) fp32 rows of pitch ld_rec, latent (M, C) of pitch ld_latent;  logits (M, K) of pitch ld_logits;  index (M) int64;
+ *   pred: NULL, or the int64 arg-max output addressed like idx of emage_argmax_logsoftmax_f32 (pred_rows, pred_ld; pred_rows <= 0: a flat list);
+ *   l_w, c_w: the weights of the entry's MSE / NLL in its forward's rec / cls loss;  tag in [0, EMAGE_VAL_TAGS): the forward.
+ * T: frames per clip (M % T == 0);  n_valid: one int32 in DEVICE memory, the real clips of the batch (clamped to [0, M / T]).
+ * Per row m < n_valid * T of an entry: the fp32 log-softmax over K, NLL at index[m], the arg-max — exactly the index
+ * emage_argmax_logsoftmax_f32 returns on the same logits (first maximum on ties, the same rule for NaN rows) —, hit = (arg-max == index[m]),
+ * and sum_c (rec - latent)^2 with difference and square in fp32 as emage_mse_loss and the sum in float64.  Rows at or beyond n_valid * T
+ * contribute nothing, whatever they hold (NaN, Inf); their pred is still written.  An index outside [0, K) contributes no NLL and no hit
+ * and sets the status word (sticky: the caller clears it), the convention of emage_nll_loss.
+ * acc: EMAGE_VAL_ACC_WORDS 8-byte words in device memory, float64 [LAST, LAST + 7) and [METER, METER + 7), int64 from HITS on:
+ *   last[2 tag] = sum over the tag's entries of l_w * mse (mean over n_valid * T * C), last[2 tag + 1] = sum of c_w * nll (mean over
+ *   n_valid * T), last[6] = their sum — the reference's rec_seed, cls_seed, rec_audio, cls_audio, rec_mask, cls_mask, all for tags 0, 1, 2;
+ *   meter[k] += last[k];  hits[entry] += its hit count;  rows += n_valid * T;  batches += 1;  status |= 1 on a bad index;
+ *   last_hits[entry] / last_rows = this call's hit counts and n_valid * T (the per-batch accuracies beside last[]).
+ * n_valid == 0 changes nothing in acc.  Sums are taken in a fixed order (per-block partials in the workspace, no atomics): the same inputs
+ * give the same bits in every run and every graph replay.  workspace: emage_val_metrics_workspace_bytes(M, n_entries) bytes, 8-byte aligned.
+ * EMAGE_EINVAL before any launch: a NULL entries / n_valid / acc / workspace / rec / latent / logits / index, n_entries outside
+ * [1, EMAGE_VAL_MAX_ENTRIES], M <= 0, T <= 0, M % T != 0, K outside [2, EMAGE_VAL_MAX_WIDTH], C outside [1, EMAGE_VAL_MAX_WIDTH] (neither
+ * needs to be a multiple of anything), a pitch smaller than its width, a pred view that does not divide M, a tag outside its range, a
+ * workspace that is too small, pointers off their natural alignment. */
+#define EMAGE_VAL_MAX_ENTRIES 12
+#define EMAGE_VAL_MAX_WIDTH 1024
+#define EMAGE_VAL_TAGS 3
+#define EMAGE_VAL_LOSSES 7
+#define EMAGE_VAL_ACC_LAST 0
+#define EMAGE_VAL_ACC_METER 7
+#define EMAGE_VAL_ACC_HITS 14
+#define EMAGE_VAL_ACC_ROWS 26
+#define EMAGE_VAL_ACC_BATCHES 27
+#define EMAGE_VAL_ACC_STATUS 28
+#define EMAGE_VAL_ACC_LAST_HITS 29
+#define EMAGE_VAL_ACC_LAST_ROWS 41
+#define EMAGE_VAL_ACC_WORDS 48
+typedef struct emage_val_entry {
+    const float* rec; const float* latent; const float* logits; const int64_t* index; int64_t* pred;
+    int ld_rec, ld_latent, ld_logits, C, K, pred_rows, tag;
+    long pred_ld;
+    double l_w, c_w;
+} emage_val_entry;
+long emage_val_metrics_workspace_bytes(int M, int n_entries);
+int emage_val_metrics(const emage_val_entry* entries, int n_entries, int M, int T, const int* n_valid, void* acc,
+                      void* workspace, long workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,7 +12,7 @@ TOOLS_LIB_PATH = os.path.join(_HERE, "csrc", "libemage_hip_tools.so")   # -DEMAG
 F32, BF16, F16X3, H2 = 0, 1, 2, 3
 PCM_S16, PCM_S24, PCM_S32, PCM_F32 = 0, 1, 2, 3       # EMAGE_PCM_*: the sample formats of emage_audio_resample
 AUDIO_TILE = 1024                                     # EMAGE_AUDIO_TILE: outputs per tile of emage_audio_resample
-ABI_VERSION = 20                                      # unchanged by the gradient-norm and clip-store entry points: they were ADDED, no existing prototype moved
+ABI_VERSION = 20                                      # unchanged by the gradient-norm, clip-store and validation entry points: they were ADDED, no existing prototype moved
 
 _p, _i, _f, _l, _d = C.c_void_p, C.c_int, C.c_float, C.c_long, C.c_double
 
@@ -38,6 +38,16 @@ class FinalizeEntry(C.Structure):
     """`emage_finalize_entry` of include/emage_hip.h (emage_col_sum_finalize_multi takes a host array of them)."""
     _fields_ = [("partial", _p), ("out", _p), ("chunks", _i), ("C", _i), ("accumulate", _i)]
 
+
+class ValEntry(C.Structure):
+    """`emage_val_entry` of include/emage_hip.h (emage_val_metrics takes a host array of them)."""
+    _fields_ = ([(n, _p) for n in ("rec", "latent", "logits", "index", "pred")]
+                + [(n, _i) for n in ("ld_rec", "ld_latent", "ld_logits", "C", "K", "pred_rows", "tag")]
+                + [("pred_ld", _l), ("l_w", _d), ("c_w", _d)])
+
+
+VAL_MAX_ENTRIES, VAL_TAGS, VAL_LOSSES = 12, 3, 7       # EMAGE_VAL_*: the accumulator block of emage_val_metrics, in 8-byte words
+VAL_ACC_LAST, VAL_ACC_METER, VAL_ACC_HITS, VAL_ACC_ROWS, VAL_ACC_BATCHES, VAL_ACC_STATUS, VAL_ACC_LAST_HITS, VAL_ACC_LAST_ROWS, VAL_ACC_WORDS = 0, 7, 14, 26, 27, 28, 29, 41, 48
 
 # name -> argtypes, exactly the prototypes of include/emage_hip.h
 TOOLS_SIGNATURES = {"emage_set_tuning": [_i, _i], "emage_h2_set_trace": [_p]}      # exported by the tools build only
@@ -100,6 +110,8 @@ SIGNATURES = {
     "emage_dropout_mask": [_p, _l, _f, C.c_ulonglong, C.c_uint, _p, _i, _p],
     "emage_gather_clips": [_p, _l, _p, _i, _i, _p, _l, _i, _i, _p, _p, _p, _p, _l, _i, _p, _l, _p, _l, _p, _l, _l, _p, _l, _l, _p, _l, _l, _p, _l, _l, _p, _p],
     "emage_motion_mask": [_p, _l, _d, _d, C.c_ulonglong, C.c_uint, _p, _p],
+    "emage_val_metrics_workspace_bytes": [_i, _i],
+    "emage_val_metrics": [C.POINTER(ValEntry), _i, _i, _i, _p, _p, _p, _l, _p],
     "emage_mul_add": [_p, _i, _p, _i, _i, _p, _i, _p, _i, _i, _i, _p],
     "emage_mul_add_philox": [_p, _i, _f, C.c_ulonglong, C.c_uint, _p, _i, _i, _p, _i, _p, _i, _i, _i, _p],
     "emage_layernorm": [_i, _p, _i, _p, _p, _f, _p, _i, _p, _p, _i, _i, _i, _p],
@@ -122,7 +134,7 @@ SIGNATURES = {
     "emage_rot6d_scatter": [_p, _i, _p, _p, _i, _i, _p],
 }
 RESTYPES = {"emage_bn_stats_workspace_bytes": _l, "emage_vq_quantize_train_workspace_bytes": _l, "emage_wav_conv_in_backward_workspace_bytes": _l, "emage_layernorm_backward_affine_workspace_bytes": _l,
-            "emage_grad_norm_workspace_bytes": _l}
+            "emage_grad_norm_workspace_bytes": _l, "emage_val_metrics_workspace_bytes": _l}
 
 _lib = None
 _tools = None

@@ -2,6 +2,7 @@
 // codebook row gather (K7).  Index outputs are int64 and follow torch's first-extremum tie rule.
 #include "common.h"
 #include "h2.h"
+#include "argmax_row.h"       // take_max, IdxView / idx_at, the classifier row (shared with val.hip)
 #include <math.h>
 
 namespace {
@@ -12,20 +13,6 @@ namespace {
 __device__ __forceinline__ void take_min(float& d, int& i, float od, int oi) {
     const bool od_nan = od != od, d_nan = d != d;
     if (od < d || (od == d && oi < i) || (od_nan && (!d_nan || oi < i))) { d = od; i = oi; }
-}
-__device__ __forceinline__ void take_max(float& d, int& i, float od, int oi) {
-    const bool od_nan = od != od, d_nan = d != d;
-    if (od > d || (od == d && oi < i) || (od_nan && (!d_nan || oi < i))) { d = od; i = oi; }
-}
-
-// Index tensors are addressed as 2-D views: element n of a flat (N,) index list lives at (n / rows)*ld + (n % rows)*ts,
-// so a (B, T) window cut out of a longer (B, L) code buffer (ld = L), or one id per clip broadcast over T frames
-// (ts = 0), is read / written in place.  rows <= 0 means a plain contiguous list.
-struct IdxView { int rows; long ld; int ts; };
-__device__ __forceinline__ long idx_at(const IdxView v, int n) {
-    if (v.rows <= 0) return n;
-    const int b = n / v.rows;
-    return (long)b * v.ld + (long)(n - b * v.rows) * v.ts;
 }
 
 // One block = 4 waves = 16 rows of z.  Wave w scores code tiles {w, w+4, ...} (16 codes each) against
@@ -225,19 +212,8 @@ __global__ __launch_bounds__(256) void argmax_logsoftmax(const float* __restrict
     const int row = blockIdx.x * 4 + wave;
     if (row >= N) return;
     const float* xp = x + (long)row * ld;
-    float mx = -INFINITY;
-    for (int c = lane; c < C; c += 64) mx = fmaxf(mx, xp[c]);
-    for (int m = 32; m >= 1; m >>= 1) mx = fmaxf(mx, __shfl_xor(mx, m));
-    float sum = 0.f;
-    for (int c = lane; c < C; c += 64) sum += expf(xp[c] - mx);
-    for (int m = 32; m >= 1; m >>= 1) sum += __shfl_xor(sum, m);
-    const float ls = logf(sum);
-    float bd = -INFINITY; int bi = 0x7fffffff;
-    for (int c = lane; c < C; c += 64) take_max(bd, bi, __fsub_rn(__fsub_rn(xp[c], mx), ls), c);
-    for (int m = 32; m >= 1; m >>= 1) {
-        const float od = __shfl_xor(bd, m); const int oi = __shfl_xor(bi, m);
-        take_max(bd, bi, od, oi);
-    }
+    float mx, ls, bd; int bi;
+    row_logsoftmax_argmax([&](int c) { return xp[c]; }, C, lane, mx, ls, bd, bi);
     if (lane == 0) idx[idx_at(iv, row)] = (int64_t)bi;
 }
 

@@ -225,15 +225,29 @@ class ClipLoader:
     kernel launches and advances the two device counters (cursor, iteration) with one add; it reads no host state.  The kernel takes the batch
     position as cursor mod len(loader): a replay past the end of an epoch re-reads its first batch.  The mask ratio is a * iteration + b with
     `mask_ratio = (a, b)`, by default the reference's (iteration / 135 * 400) * 0.95 + 0.05, not clamped; `iteration` (a property over the device
-    counter) counts the fills, and a resumed run sets it."""
+    counter) counts the fills, and a resumed run sets it.
 
-    def __init__(self, store, batch, rank=0, world=1, seed=0, mask_seed=0, mask_ratio=(400 / 135 * 0.95, 0.05)):
+    An evaluation loader (the reference's test loader, train_emage_audio.py:276-277: `DistributedSampler(test_dataset)` at epoch 0,
+    `drop_last=False`) is `ClipLoader(store, batch, drop_last=False, hold_iteration=True)`: `len()` counts the short last batch, the order
+    buffer is padded to a whole batch with a valid clip id, and `valid` — one int32 on the device — holds the number of REAL clips of the
+    batch `fill()` has just cut (set from the device cursor, so a captured graph carries it; `validation.Validator` hands it to
+    `emage_val_metrics`).  hold_iteration: `fill()` advances the cursor but not the iteration — the reference draws the validation mask
+    with the TRAINING iteration, which stands still during a validation pass; the caller sets `loader.iteration`."""
+
+    def __init__(self, store, batch, rank=0, world=1, seed=0, mask_seed=0, mask_ratio=(400 / 135 * 0.95, 0.05), drop_last=True, hold_iteration=False):
         self.store, self.batch_size, self.rank, self.world, self.seed, self.mask_seed = store, int(batch), int(rank), int(world), int(seed), int(mask_seed)
         self.mask_a, self.mask_b = float(mask_ratio[0]), float(mask_ratio[1])
+        self.drop_last, self.hold_iteration = bool(drop_last), bool(hold_iteration)
         per_rank = -(-store.n_clips // self.world)
-        self.n_batches = per_rank // self.batch_size if self.batch_size > 0 else 0
+        if self.batch_size <= 0:
+            self.n_batches = 0
+        elif self.drop_last:
+            self.n_batches = per_rank // self.batch_size
+        else:
+            self.n_batches = -(-per_rank // self.batch_size)
         if self.n_batches <= 0:
             raise ValueError(f"ClipLoader: {store.n_clips} clips over {world} ranks give no full batch of {batch}")
+        self.n_real = min(per_rank, self.n_batches * self.batch_size)         # clips of an epoch on this rank; the rest of the order buffer is padding
         dev, t = store.device, store.frames
         self.batch = {k: torch.zeros(self.batch_size, t, w, dtype=torch.float32, device=dev) for k, w in ops.CLIP_WIDTHS.items()}
         self.batch["audio"] = torch.zeros(self.batch_size, t * store.spf, dtype=torch.float32, device=dev)
@@ -242,6 +256,7 @@ class ClipLoader:
         self.counters = torch.zeros(2, dtype=torch.int32, device=dev)          # [cursor, iteration]
         self.cursor, self._iteration = self.counters[0:1], self.counters[1:2]
         self.status = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.valid = torch.full((1,), self.batch_size, dtype=torch.int32, device=dev)      # real clips of the batch `fill()` cut last
         self.epoch, self.epoch_ids = None, None
         self.set_epoch(0)
 
@@ -250,6 +265,8 @@ class ClipLoader:
 
     def set_epoch(self, epoch):
         ids = epoch_order(self.store.n_clips, epoch, self.rank, self.world, self.seed)[:self.n_batches * self.batch_size]
+        if len(ids) < self.n_batches * self.batch_size:                        # drop_last=False: the short last batch is padded with a valid clip
+            ids = np.concatenate([ids, np.full(self.n_batches * self.batch_size - len(ids), ids[0], dtype=ids.dtype)])
         self.epoch, self.epoch_ids = int(epoch), ids.reshape(self.n_batches, self.batch_size)
         self.order.copy_(torch.from_numpy(ids.astype(np.int32)))
         self.cursor.zero_()
@@ -264,13 +281,16 @@ class ClipLoader:
 
     def prologue_state(self):
         """The device tensors `fill()` advances: `Trainer.capture` saves them around its warm-up step and puts them back."""
-        return [self.counters]
+        return [self.counters] if self.drop_last else [self.counters, self.valid]
 
     def fill(self):
         st = self.store
         ops.gather_clips(self.order, self.cursor, self.n_batches, st.clips, st.arrays, self.batch, self.status, frames=st.frames, samples_per_frame=st.spf)
         ops.motion_mask(self.random_mask, self.mask_a, self.mask_b, self.mask_seed, MOTION_MASK_ID, self._iteration)
-        self.counters.add_(1)
+        if not self.drop_last:                                                 # real clips of this batch, from the device cursor alone (capturable)
+            pos = torch.remainder(self.cursor, self.n_batches)
+            torch.clamp(self.n_real - pos * self.batch_size, max=self.batch_size, out=self.valid)
+        (self.cursor if self.hold_iteration else self.counters).add_(1)
 
     def check(self):
         """Read the status word of the gathers so far (one device-to-host copy: call it where the losses are read anyway) and clear it."""

@@ -1482,6 +1482,66 @@ def gather_clips(order, cursor, n_batches, clips, arrays, out, status, *, frames
     return out
 
 
+@_op("val_metrics", "(Tensor[] recs, Tensor[] latents, Tensor[] logits, Tensor[] index, Tensor(a!)[] preds, int[] desc, float[] weights, int T, "
+                    "Tensor n_valid, Tensor(b!) acc, Tensor(c!) workspace) -> ()")
+def _val_metrics(recs, latents, logits, index, preds, desc, weights, t, n_valid, acc, workspace):
+    n = len(recs)
+    arr = (_lib.ValEntry * n)()
+    for i in range(n):
+        e, pred = arr[i], (preds[desc[2 * i + 1]] if desc[2 * i + 1] >= 0 else None)
+        e.rec, e.latent, e.logits, e.index, e.pred = _ptr(recs[i]), _ptr(latents[i]), _ptr(logits[i]), _ptr(index[i]), _ptr(pred)
+        e.ld_rec, e.ld_latent, e.ld_logits, e.C, e.K = _ld(recs[i]), _ld(latents[i]), _ld(logits[i]), recs[i].shape[1], logits[i].shape[1]
+        e.pred_rows, e.pred_ld, _ts = index_view(pred) if pred is not None else (0, 0, 1)
+        e.tag, e.l_w, e.c_w = desc[2 * i], weights[2 * i], weights[2 * i + 1]
+    check(_lib.load().emage_val_metrics(arr, n, recs[0].shape[0], t, _ptr(n_valid), _ptr(acc), _ptr(workspace), workspace.numel() * 8, _stream()), "val_metrics")
+
+
+def val_accumulators(device):
+    """The zeroed accumulator block of `val_metrics` (include/emage_hip.h EMAGE_VAL_ACC_*): a float64 tensor of 48 words whose tail holds int64
+    counters — read it through `val_read`."""
+    return torch.zeros(_lib.VAL_ACC_WORDS, dtype=torch.float64, device=device)
+
+
+def val_read(acc):
+    """ONE device-to-host copy of an accumulator block -> dict(last (7 floats), meter (7 floats), hits (12 ints), rows, batches, status)."""
+    host = acc.cpu()
+    ints = host.view(torch.int64)
+    return dict(last=host[_lib.VAL_ACC_LAST:_lib.VAL_ACC_LAST + _lib.VAL_LOSSES].tolist(),
+                meter=host[_lib.VAL_ACC_METER:_lib.VAL_ACC_METER + _lib.VAL_LOSSES].tolist(),
+                hits=ints[_lib.VAL_ACC_HITS:_lib.VAL_ACC_HITS + _lib.VAL_MAX_ENTRIES].tolist(),
+                rows=int(ints[_lib.VAL_ACC_ROWS]), batches=int(ints[_lib.VAL_ACC_BATCHES]), status=int(ints[_lib.VAL_ACC_STATUS]),
+                last_hits=ints[_lib.VAL_ACC_LAST_HITS:_lib.VAL_ACC_LAST_HITS + _lib.VAL_MAX_ENTRIES].tolist(), last_rows=int(ints[_lib.VAL_ACC_LAST_ROWS]))
+
+
+def val_metrics(entries, t, n_valid, acc, workspace=None):
+    """The losses, arg-max codes and code hits of one validation step in two launches (include/emage_hip.h: emage_val_metrics).  entries: up to
+    12 dicts, one per (forward, part): `rec`, `latent` (M, C) and `logits` (M, K) fp32 views with unit inner stride, `index` (M,) int64,
+    `pred` (optional int64 output: (M,) or a (B, T) view of a code buffer), the weights `l_w`, `c_w` and `tag` in 0..2 (the forward).  t: frames
+    per clip; n_valid: one int32 on the device, the real clips of the batch; acc: `val_accumulators`.  Returns the workspace (pass it again)."""
+    rec0 = entries[0]["rec"]
+    _dev(rec0)
+    dev, m = rec0.device, rec0.shape[0]
+    assert 1 <= len(entries) <= _lib.VAL_MAX_ENTRIES and n_valid.dtype == torch.int32 and n_valid.numel() == 1
+    assert acc.dtype == torch.float64 and acc.numel() == _lib.VAL_ACC_WORDS and acc.is_contiguous()
+    preds, desc, weights = [], [], []
+    for e in entries:
+        for k in ("rec", "latent", "logits"):
+            assert e[k].dtype == torch.float32 and e[k].dim() == 2 and e[k].shape[0] == m and e[k].stride(1) == 1 and e[k].device == dev, k
+        assert e["rec"].shape == e["latent"].shape and e["index"].dtype == torch.int64 and e["index"].numel() == m and e["index"].is_contiguous()
+        pred = e.get("pred")
+        if pred is not None:
+            assert pred.dtype == torch.int64 and pred.numel() == m and index_view(pred)[2] == 1
+            preds.append(pred)
+        desc += [int(e["tag"]), len(preds) - 1 if pred is not None else -1]
+        weights += [float(e["l_w"]), float(e["c_w"])]
+    words = _lib.load().emage_val_metrics_workspace_bytes(m, len(entries)) // 8
+    if workspace is None or workspace.numel() < words:
+        workspace = torch.empty(max(words, 1), dtype=torch.float64, device=dev)
+    _val_metrics([e["rec"] for e in entries], [e["latent"] for e in entries], [e["logits"] for e in entries], [e["index"] for e in entries],
+                 preds, desc, weights, int(t), n_valid, acc, workspace)
+    return workspace
+
+
 class AdamTable:
     """Descriptor tables of `adam_multi` for a fixed list of (param, grad, exp_avg, exp_avg_sq) fp32 tensors (contiguous, same numel per
     quadruple): built once, valid as long as the tensors' storage does not move."""

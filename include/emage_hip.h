@@ -343,6 +343,31 @@ int emage_qkv_attention(int dtype, const void* A, int lda, const void* W, const 
 int emage_qkv_attention_grouped(int dtype, const emage_qkv_attention_problem* problems, int n_problems, int T, int d, int H, void* stream);
 
 /*
+ * One cross-attention site in ONE launch: the q projection of emage_gemm (EMAGE_H2) and emage_attention on it, with q kept on chip.  One
+ * workgroup per (clip, head) computes the 64 x 192 block q_h of the projection, stages it with the layer's memory K_h / V_h^T in LDS and runs
+ * the attention of that head.  `out` is bit for bit what the two-launch sequence writes:
+ *     emage_gemm(dtype, A, lda, W, bias, out_f32 = q (B T, d), M = B T, N = d, Cp = d, a_scale, w_scale)
+ *                (with the LayerNorm fold: the same problem with ln_stats / ln_c / ln_eps, emage_gemm_grouped)
+ *     emage_attention(dtype, q, d, k, ldk, vt, ldvt, vt_rows, out, ldo, B, H, T, Tk, d / H)
+ * (bit for bit as long as that emage_gemm takes its 64 x 64 tile, which it does below ~26 000 rows on 256 CUs: wider tiles merge the folded
+ * LayerNorm's partial statistics in another order).
+ * Only T = Tk = 64, d = 768, H = 4 (hd = 192) and dtype EMAGE_H2 (with any activation shift) are supported; anything else is EMAGE_EINVAL.
+ * A, W, bias, ln_stats / ln_c / ln_eps, out: as for emage_qkv_attention, W the (d, d) packed q projection.
+ * k:    (B Tk, ldk) float32, head h at columns [h hd, (h + 1) hd); ldk % 4 == 0, ldk >= d (a column block of several layers' keys is a view).
+ * vt:   V transposed, (B, vt_rows, ldvt) float32 as emage_attention takes it: vt_rows >= d, ldvt % 32 == 0, ldvt >= 64.
+ * Pointers 16-byte aligned; every operand spans less than 2 GiB.
+ * The grouped form runs 1..4 independent problems in one launch (the part-wise decoder stacks in lock step).
+ */
+typedef struct emage_q_attention_problem {
+    const void* A; const void* W; const float* bias; const float* ln_stats; const float* ln_c;
+    const float* k; const float* vt; void* out;
+    int lda, ldk, ldvt, vt_rows, ldo, B;
+    float a_scale, w_scale, ln_eps;
+} emage_q_attention_problem;
+int emage_q_attention(int dtype, const emage_q_attention_problem* problem, int T, int Tk, int d, int H, void* stream);
+int emage_q_attention_grouped(int dtype, const emage_q_attention_problem* problems, int n_problems, int T, int Tk, int d, int H, void* stream);
+
+/*
  * K5 — LayerNorm(C, eps) over rows (post-norm of every transformer sub-layer):
  *   y = (x - mean) * rsqrt(var + eps) * gamma + beta (+ add[m][:])
  * x: (M, ldx) `dtype` — the residual stream is stored in the compute dtype (fp32 in parity mode, bf16 in bf16

@@ -85,12 +85,12 @@ template <int HD, int NT> struct AttnLds {
     static constexpr int K_BYTES = NKEY * KROW, V_BYTES = HD * VROW, BYTES = K_BYTES + V_BYTES;
 };
 
-// all 256 threads of the workgroup; H2OUT selects the permuted d order of attn_tile's V^T rows.  Every global load of the thread is
+// all NTHR threads of the workgroup (256 in attention.hip); H2OUT selects the permuted d order of attn_tile's V^T rows.  Every global load of the thread is
 // issued before the first split (compile-time trip counts, fully unrolled): one memory latency per workgroup, not one per cell.
-template <int HD, int NT, bool H2OUT>
+// (q_attention.hip stages with its eight K-loop waves).
+template <int HD, int NT, bool H2OUT, int NTHR = 64 * QW>
 __device__ __forceinline__ void attn_stage_kv(const AttnArgs& p, const int b, const int h, unsigned char* smem) {
     using L = AttnLds<HD, NT>;
-    constexpr int NTHR = 64 * QW;
     constexpr int KU = L::NKEY * L::KS * 4 / NTHR, VU = HD * L::VS * 4 / NTHR;      // cells per thread
     static_assert(L::NKEY * L::KS * 4 % NTHR == 0 && HD * L::VS * 4 % NTHR == 0, "cells divide evenly over the workgroup");
     const float* __restrict__ K = (const float*)p.k;

@@ -1,0 +1,191 @@
+// emage_q_attention — one cross-attention site of the EMAGE decoder layers (T = Tk = 64 frames, d = 768, 4 heads of 192) as ONE launch
+// instead of the q projection (emage_gemm, config 120 / 1120: a (B T, d) float32 q to memory) followed by emage_attention (which reads it
+// straight back; nothing else ever does).  One workgroup per (clip, head), the skeleton of qkv_attention.hip:
+//   * K-loop: gemm_h2_tile (h2_tile.h) unchanged on the 64 x 192 block tile of head h (its 192 W rows are contiguous in the packed q
+//     projection) — wave rows of 32 (WM = 2) as in config 1120, so the folded LayerNorm's statistics merge in the same order; eight waves
+//     of 32 x 48 on a ring of 3 (measured: 28.3-28.7 us per launch at 64 clips; four waves of 32 x 96: 31.3, rings of 2 / 4: 29.4 / 29.0; the
+//     K / V^T loads issued in front of the K-loop and split behind it: 28.6, not faster — profiles/r10_q_attention_kernel_variants.txt);
+//   * epilogue: the arithmetic of h2_tile_epilogue's float32 path for these columns (o_scale, the LayerNorm fold, bias), split into fp16
+//     planes in LDS in the layout attn_stage_kv gives K (one row per query);
+//   * K / V^T: float32 views of the layer's projected memory, staged by attn_stage_kv once the K-loop has released the operand ring
+//     (K, V^T and Q together are 149 KiB: they fit the CU only without the ring);
+//   * attention: attn_tile on LDS fragments (QLDS), four waves of 16 queries; `att` is written as the EMAGE_H2 image.
+// Every q value, every split plane and the order of every MFMA over its contraction are those of the two-launch sequence: the output is
+// the same bits (tests/test_q_attention_gpu.py).
+#include "common.h"
+#include <math.h>
+#include "h2_tile.h"
+#include "attn_tile.h"
+
+namespace emage_dev {
+
+constexpr int CA_T = 64, CA_HD = 192, CA_H = 4, CA_D = CA_H * CA_HD;
+constexpr int CA_BM = 64, CA_BN = CA_HD, CA_WM = 2, CA_WN = 4, CA_NS = 3;
+constexpr int CA_THREADS = CA_WM * CA_WN * 64;
+constexpr int CA_MAXG = 4;
+
+struct QAttnArgs {
+    GemmArgs g;                              // the projection as emage_gemm runs it (M = B T, N = K = d; no outputs of its own)
+    const float* k; const float* vt;         // this layer's memory keys (B Tk, ldk) and V^T (B, vt_rows, ldvt), float32
+    void* out;                               // att: (B T, ldo) EMAGE_H2 image
+    int ldk, ldvt, vt_rows, ldo;
+};
+struct QAttnGroup {
+    QAttnArgs p[CA_MAXG];
+    int blk_end[CA_MAXG];                    // running sum of B H
+    int n, total;
+};
+
+}  // namespace emage_dev
+
+namespace {
+
+using namespace emage_dev;
+using L = AttnLds<CA_HD, 4>;
+constexpr int CA_LDS = L::BYTES + L::K_BYTES;            // K | V^T | Q planes
+
+static_assert(h2_smem_bytes<CA_BM, CA_BN, CA_NS>() <= CA_LDS && CA_LDS <= 160 * 1024, "the operand ring lies inside the staged planes: one block per CU");
+
+__global__ __launch_bounds__(CA_THREADS, 1) void q_attn_kernel(QAttnGroup g) {
+    constexpr int WTN = CA_BN / CA_WN, FN = WTN / 16;
+    __shared__ __attribute__((aligned(128))) unsigned char smem[CA_LDS];
+    // XCD-aware order over the whole grid: each XCD walks a contiguous run of (clip, head) blocks, heads fastest (the four heads of a clip share A)
+    const int bid = xcd_run_order((int)blockIdx.x, g.total);
+    int pi = 0;
+#pragma unroll
+    for (int i = 0; i < CA_MAXG - 1; ++i) pi += (i + 1 < g.n && bid >= g.blk_end[i]) ? 1 : 0;
+    pi = __builtin_amdgcn_readfirstlane(pi);
+    const int t = bid - (pi ? g.blk_end[pi - 1] : 0);
+    const QAttnArgs& q = g.p[pi];
+    const GemmArgs& p = q.g;
+    const int b = t / CA_H, h = t - b * CA_H;
+    const AttnArgs a{nullptr, q.k, q.vt, q.out, 0, q.ldk, q.ldvt, q.vt_rows, q.ldo, p.M / CA_T, CA_H, CA_T, CA_T, 1.0f / sqrtf((float)CA_HD), nullptr, p.h2s, p.h2i};
+
+    // the epilogue: q of this wave's 32 frames x WTN columns -> split planes in LDS, K's row layout at smem + L::BYTES
+    auto epi = [&](auto& acc, const int, const int wm, const int wn, const int fr, const int fg, const auto& ln_mu, const auto& ln_rs) {
+        constexpr int NP = FN / 2;                     // fragment pairs (8 consecutive columns per lane); an odd FN leaves a lone fragment (4 columns)
+        constexpr bool LONE = (FN & 1) != 0;
+        // every bias / c value of the lane is requested before the barrier: one memory latency, not one per fragment
+        const bool fold = p.ln_stats != nullptr;
+        const int n0 = h * CA_HD + wn * WTN + fg * 8, nl = h * CA_HD + wn * WTN + (FN - 1) * 16 + fg * 4;
+        float cv[NP][8], bv[NP][8];
+        float4 cl = make_float4(0.f, 0.f, 0.f, 0.f), bl = cl;
+        static_for<NP>([&](auto jc) {
+            constexpr int JP = decltype(jc)::value;
+            if (fold) load8<float>(p.ln_c + n0 + JP * 32, cv[JP]);
+            load8<float>(p.bias + n0 + JP * 32, bv[JP]);
+        });
+        if constexpr (LONE) {
+            if (fold) cl = *(const float4*)(p.ln_c + nl);
+            bl = *(const float4*)(p.bias + nl);
+        }
+        __syncthreads();                               // every wave has read its last fragments of the ring
+        const float os = p.o_scale;
+        // the row-major epilogue's float32 value of one accumulator (o_scale, the LayerNorm fold, bias; no slope, no residual: leaky(., 1), + 0)
+        auto value = [&](const float accv, const float c, const float bias, const float mu, const float rs) {
+            float x = accv * os;
+            if (fold) x = rs * (x - mu * c);
+            float y = x + bias;
+            y = leaky(y, 1.f);
+            y += 0.f;
+            return y;
+        };
+        // K's row layout: row fm, cell (cc / 32, (cc % 16) / 4) holds columns 32 s + 4 g + r (planes [0, 4)) and 32 s + 16 + 4 g + r ([4, 8))
+        auto cell = [&](const int fm, const int cc) { return smem + L::BYTES + fm * L::KROW + (cc >> 5) * 128 + ((cc & 15) >> 2) * 32 + ((cc & 31) >> 4) * 8; };
+        static_for<2 * NP>([&](auto ic) {
+            constexpr int I = decltype(ic)::value / NP, JP = decltype(ic)::value % NP;
+            const int fm = wm * 32 + I * 16 + fr;      // frame of this lane's row
+            const int cc = wn * WTN + JP * 32 + fg * 8;             // this lane's 8 columns inside the head: cc .. cc + 7
+            float v[8];
+#pragma unroll
+            for (int e = 0; e < 8; ++e) v[e] = value(e < 4 ? acc[I][2 * JP][e] : acc[I][2 * JP + 1][e - 4], cv[JP][e], bv[JP][e], ln_mu[I], ln_rs[I]);
+            uint4 hi, lo;
+            h2_split8(v, hi, lo, p.h2s);               // split as attn_tile splits them
+            // columns cc .. cc + 3 and cc + 4 .. cc + 7 fill the same half of two neighbouring cells
+            unsigned char* dst = cell(fm, cc);
+            *(uint2*)dst = make_uint2(hi.x, hi.y);
+            *(uint2*)(dst + 16) = make_uint2(lo.x, lo.y);
+            *(uint2*)(dst + 32) = make_uint2(hi.z, hi.w);
+            *(uint2*)(dst + 48) = make_uint2(lo.z, lo.w);
+        });
+        if constexpr (LONE) {
+            // the lone fragment (natural W row order): 4 consecutive columns per lane, one half of one cell
+            static_for<2>([&](auto ic) {
+                constexpr int I = decltype(ic)::value;
+                const int fm = wm * 32 + I * 16 + fr;
+                const int cc = wn * WTN + (FN - 1) * 16 + fg * 4;
+                const float c4[4] = {cl.x, cl.y, cl.z, cl.w}, b4[4] = {bl.x, bl.y, bl.z, bl.w};
+                float v[4];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) v[e] = value(acc[I][FN - 1][e], c4[e], b4[e], ln_mu[I], ln_rs[I]);
+                uint2 hi, lo;
+                h2_split4(v, hi, lo, p.h2s);
+                unsigned char* dst = cell(fm, cc);
+                *(uint2*)dst = hi;
+                *(uint2*)(dst + 16) = lo;
+            });
+        }
+    };
+    gemm_h2_tile<CA_BM, CA_BN, CA_WM, CA_WN, CA_NS, false, false, 1, true, false, false>(p, b * CA_T, h * CA_HD, smem, 0, epi);
+    attn_stage_kv<CA_HD, 4, true, CA_THREADS>(a, b, h, smem);      // the ring is free: every wave passed the epilogue's barrier
+    __syncthreads();
+    const int wave = (int)(threadIdx.x >> 6);
+    if (wave >= CA_T / 16) return;
+    attn_tile<float, CA_HD, 4, 1, true, true, true, true>(a, b, h, wave, 0, smem);
+}
+
+int make_problem(int dtype, const emage_q_attention_problem& q, int T, int Tk, int d, int H, const H2Scale& hs, QAttnArgs& r) {
+    if (dtype != EMAGE_H2 || T != CA_T || Tk != CA_T || d != CA_D || H != CA_H) return EMAGE_EINVAL;
+    if (!q.A || !q.W || !q.bias || !q.k || !q.vt || !q.out || q.B <= 0) return EMAGE_EINVAL;
+    if (((uintptr_t)q.A | (uintptr_t)q.W | (uintptr_t)q.bias | (uintptr_t)q.k | (uintptr_t)q.vt | (uintptr_t)q.out) & 15) return EMAGE_EINVAL;
+    if (q.lda % 8 || q.lda < d || q.ldo % 8 || q.ldo < d) return EMAGE_EINVAL;
+    if (q.ldk % 4 || q.ldk < d || q.ldvt % 32 || q.ldvt < Tk || q.vt_rows < d) return EMAGE_EINVAL;
+    if (!(q.a_scale > 0.f && q.w_scale > 0.f)) return EMAGE_EINVAL;
+    if (q.ln_stats && (!q.ln_c || ((uintptr_t)q.ln_stats & 15) || ((uintptr_t)q.ln_c & 15) || !(q.ln_eps > 0.f))) return EMAGE_EINVAL;
+    const long rows = (long)q.B * T;
+    if (rows * q.lda * 4 >= (1L << 31) || rows * q.ldo * 4 >= (1L << 31)) return EMAGE_EINVAL;
+    if ((long)q.B * Tk * q.ldk * 4 >= (1L << 31) || (long)q.B * q.vt_rows * q.ldvt * 4 >= (1L << 31)) return EMAGE_EINVAL;
+    GemmArgs a = {};
+    a.A = q.A; a.W = q.W; a.bias = q.bias;
+    a.lda = q.lda;
+    a.M = (int)rows; a.N = d; a.K = d; a.Cp = d;
+    set_geometry(a, 1, 1, 0, a.M, a.M);
+    a.t_col0 = a.N; a.t_rows = 1;
+    a.ksplit = 1;
+    a.a_scale = q.a_scale;
+    a.o_scale = 1.f / (q.a_scale * q.w_scale);    // as emage_gemm computes it
+    a.h2s = hs.s; a.h2i = hs.inv;
+    a.ln_stats = q.ln_stats; a.ln_np = q.ln_stats ? 24 : 0; a.ln_c = q.ln_stats ? q.ln_c : nullptr; a.ln_eps = q.ln_eps;
+    r.g = a;
+    r.k = q.k; r.vt = q.vt; r.out = q.out;
+    r.ldk = q.ldk; r.ldvt = q.ldvt; r.vt_rows = q.vt_rows; r.ldo = q.ldo;
+    return 0;
+}
+
+int q_attention_impl(int dtype, const emage_q_attention_problem* problems, int n, int T, int Tk, int d, int H, hipStream_t s) {
+    H2Scale hs;
+    if (h2_dtype(dtype, hs) || !problems || n <= 0 || n > CA_MAXG) return EMAGE_EINVAL;
+    QAttnGroup g;
+    int total = 0;
+    for (int i = 0; i < n; ++i) {
+        const int rc = make_problem(dtype, problems[i], T, Tk, d, H, hs, g.p[i]);
+        if (rc) return rc;
+        total += problems[i].B * H;
+        g.blk_end[i] = total;
+    }
+    for (int i = n; i < CA_MAXG; ++i) { g.p[i] = g.p[0]; g.blk_end[i] = total; }
+    g.n = n;
+    g.total = total;
+    hipLaunchKernelGGL(q_attn_kernel, dim3(total), dim3(CA_THREADS), 0, s, g);
+    return launch_status();
+}
+
+}  // namespace
+
+extern "C" int emage_q_attention(int dtype, const emage_q_attention_problem* problem, int T, int Tk, int d, int H, void* stream) {
+    return q_attention_impl(dtype, problem, problem ? 1 : 0, T, Tk, d, H, (hipStream_t)stream);
+}
+
+extern "C" int emage_q_attention_grouped(int dtype, const emage_q_attention_problem* problems, int n_problems, int T, int Tk, int d, int H, void* stream) {
+    return q_attention_impl(dtype, problems, n_problems, T, Tk, d, H, (hipStream_t)stream);
+}

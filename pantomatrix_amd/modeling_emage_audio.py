@@ -96,6 +96,8 @@ class _EmageModule(torch.nn.Module):
         self.fuse_self_attention = True        # EMAGE_H2 eval forward, 64-frame windows of enough clips to fill the GPU: each self-attention site's qkv
                                                # projection and attention run as ONE launch (ops.qkv_attention: q / k / v never leave the chip);
                                                # False = the two launches (same bits)
+        self.fuse_cross_attention = True       # the same for the cross-attention sites: the q projection and the attention on the layer's memory
+                                               # K / V^T run as ONE launch (ops.q_attention: q never leaves the chip); False = the two launches (same bits)
         self.group_face_body = False           # forward(): the 4 face decoder layers walk in lock step with the first 4 audio cross-attention
                                                # layers of the body (same shapes, different weights: 6 contractions per layer pair share
                                                # launches) instead of running on two stream lanes; same bits (A/B switch)
@@ -1241,6 +1243,17 @@ class EmageAudioModel(_WavEncoderMixin, _EmageModule):
             return False
         return b >= 16 and b * h >= torch.cuda.get_device_properties(cx.dev).multi_processor_count
 
+    def _fused_cross_attn(self, cx, b, t, tk, d, h):
+        """Whether a cross-attention site runs as one `ops.q_attention` launch: EMAGE_H2 eval forward on the GPU, a full 64-frame window on a
+        64-frame memory, and at least one (clip, head) workgroup per CU.  The q projection takes the 64 x 64 tile (32-row wave tiles, which the
+        fused kernel's K-loop has too) at every row count up to 20 M rows x k per 256 CUs (csrc/gemm_h2.hip: h2_config_for), so there is no
+        floor of 16 clips as for self-attention; beyond that bound emage_gemm's wider tile merges a folded LayerNorm's statistics in another
+        order, and the two launches stay."""
+        if not (self.fuse_cross_attention and cx.h2 and not self.training and cx.dev.type == "cuda" and ops.q_attention_supported(cx.h2dt, t, tk, d, h)):
+            return False
+        cus = torch.cuda.get_device_properties(cx.dev).multi_processor_count
+        return b * h >= cus and b * t * d < 20 * (1_000_000 * cus // 256)
+
     def _ln(self, cx, key, s, add=None, want_f32=False):
         """LayerNorm of a pre-norm sum (residual precision) -> _X; `add`: float32 / storage-type tensor folded in behind the norm.
         want_f32 (EMAGE_H2 mode with H2 residuals): keep a float32 twin anyway (the result is later an `add` operand)."""
@@ -1276,9 +1289,17 @@ class EmageAudioModel(_WavEncoderMixin, _EmageModule):
         d, h = self.config.hidden_size, spec.N_HEAD
         fold = cx.fold_ln
         x = self._ln(cx, name + ".norm1", self._self_attn(cx, name, x, b, t, stats=fold))
-        q = cx.gemm_ln(x, name + ".ca.q", want="f32")[1] if cx.h2 else cx.gemm_r(x.a, name + ".ca.q")
-        att = cx.lo(b * t, d)
-        ops.attention(cx.gdt, q, mem_k, mem_vt, vt_rows, att, b, h, t, tk, d // h)
+        if self._fused_cross_attn(cx, b, t, tk, d, h):
+            att = cx.lo(b * t, d)
+            key = name + ".ca.q"
+            e = cx.pk.w[key] if x.ln is None else cx.pk.w[key + "@" + x.ln[1]]
+            assert e["cp"] == d and e["n"] == d
+            ops.q_attention(cx.h2dt, x.a, e["w"], e["b"], mem_k, mem_vt, vt_rows, att, b, w_scale=e.get("ws", 1.0),
+                            ln=None if x.ln is None else (x.ln[0], e["c"]))
+        else:
+            q = cx.gemm_ln(x, name + ".ca.q", want="f32")[1] if cx.h2 else cx.gemm_r(x.a, name + ".ca.q")
+            att = cx.lo(b * t, d)
+            ops.attention(cx.gdt, q, mem_k, mem_vt, vt_rows, att, b, h, t, tk, d // h)
         x = self._ln(cx, name + ".norm2", cx.gemm_s(att, name + ".ca.out", x, fold))
         return self._ln(cx, name + ".norm3", self._ffn(cx, name, x, stats=fold and fold_out and post_add is None), add=post_add)
 

@@ -724,8 +724,76 @@ def qkv_attention(dtype, a, w, bias, out, b, *, w_scale, a_scale=None, ln=None, 
                    float(ln_eps) if ln is not None else 0.0)
 
 
+# Fused cross-attention site (include/emage_hip.h: emage_q_attention): q projection + attention on the layer's memory K / V^T in one launch
+_QA_PTRS = ("A", "W", "bias", "ln_stats", "ln_c", "k", "vt", "out")
+_QA_INTS = ("lda", "ldk", "ldvt", "vt_rows", "ldo", "B")
+
+
+def q_attention_supported(dtype, t, tk, d, h):
+    """Shapes `q_attention` is built for: EMAGE_H2 (any activation shift), T = Tk = 64 frames, d = 768, 4 heads."""
+    return dtype & 0xff == H2 and t == _QKV_T and tk == _QKV_T and d == _QKV_D and h == _QKV_H
+
+
+def _qa_fields(a, w, bias, ln_stats, ln_c, k, vt, vt_rows, out, b, w_scale, a_scale, ln_eps):
+    return dict(A=_ptr(a), W=_ptr(w), bias=_ptr(bias), ln_stats=_ptr(ln_stats), ln_c=_ptr(ln_c), k=_ptr(k), vt=_ptr(vt), out=_ptr(out),
+                lda=_ld(a), ldk=_ld(k), ldvt=vt.shape[-1], vt_rows=vt_rows, ldo=_ld(out), B=b, a_scale=a_scale, w_scale=w_scale, ln_eps=ln_eps)
+
+
+def _qa_problems(desc, scales):
+    k = len(_QA_PTRS) + len(_QA_INTS)
+    n = len(desc) // k
+    arr = (_lib.QAttentionProblem * n)()
+    for i in range(n):
+        for j, name in enumerate(_QA_PTRS + _QA_INTS):
+            v = desc[k * i + j]
+            setattr(arr[i], name, (v or None) if j < len(_QA_PTRS) else v)
+        arr[i].a_scale, arr[i].w_scale, arr[i].ln_eps = scales[3 * i], scales[3 * i + 1], scales[3 * i + 2]
+    return arr, n
+
+
+@_op("q_attention", "(int dtype, Tensor a, Tensor w, Tensor bias, Tensor? ln_stats, Tensor? ln_c, Tensor k, Tensor vt, int vt_rows, Tensor(a!) out, "
+                    "int b, float w_scale, float a_scale, float ln_eps) -> ()")
+def _q_attention(dtype, a, w, bias, ln_stats, ln_c, k, vt, vt_rows, out, b, w_scale, a_scale, ln_eps):
+    f = _qa_fields(a, w, bias, ln_stats, ln_c, k, vt, vt_rows, out, b, w_scale, a_scale, ln_eps)
+    arr, _ = _qa_problems([int(f[n] or 0) for n in _QA_PTRS + _QA_INTS], [a_scale, w_scale, ln_eps])
+    check(_lib.load().emage_q_attention(dtype, arr, _QKV_T, _QKV_T, _QKV_D, _QKV_H, _stream()), "q_attention")
+
+
+@_op("q_attention_grouped", "(int dtype, Tensor(a!)[] tensors, int[] desc, float[] scales) -> ()")
+def _q_attention_grouped(dtype, tensors, desc, scales):
+    arr, n = _qa_problems(desc, scales)
+    check(_lib.load().emage_q_attention_grouped(dtype, arr, n, _QKV_T, _QKV_T, _QKV_D, _QKV_H, _stream()), "q_attention_grouped")
+
+
+def _q_attention_grouped_entries(entries):
+    """Recorded `emage::q_attention` calls (Lockstep) of ONE dtype -> grouped calls of up to _QKV_MAXG problems each."""
+    dtype = entries[0][2][0]
+    for i in range(0, len(entries), _QKV_MAXG):
+        tensors, desc, scales = [], [], []
+        for _name, _op_, args, _meta in entries[i:i + _QKV_MAXG]:
+            assert args[0] == dtype
+            f = _qa_fields(*args[1:])
+            desc += [int(f[n] or 0) for n in _QA_PTRS + _QA_INTS]
+            scales += [float(f["a_scale"]), float(f["w_scale"]), float(f["ln_eps"])]
+            tensors += [t for t in args[1:10] if torch.is_tensor(t)]
+        _q_attention_grouped.op(dtype, tensors, desc, scales)
+
+
+def q_attention(dtype, a, w, bias, k, vt, vt_rows, out, b, *, w_scale, a_scale=None, ln=None, ln_eps=1e-5):
+    """One cross-attention site in one launch (include/emage_hip.h: emage_q_attention): `out` (B*64, ldo) EMAGE_H2 image <- the attention of
+    the q projection of `a` (packed `w` / `bias`) on the memory keys `k` (B*64, ldk) float32 and `vt`, a float32 view into a (B, vt_rows, ldvt)
+    V^T buffer starting at this layer's first row (as `attention` takes them) — bit-identical to `gemm` (q float32) + `attention`.
+    ln = (row statistics of `a`, c): `a` is the raw pre-norm sum of a folded LayerNorm and `w` / `bias` its folded twins (see `gemm`).
+    Inside a `lockstep()` the sites at the heads of the chains share grouped launches."""
+    _dev(a)
+    ln_stats, ln_c = ln if ln is not None else (None, None)
+    _q_attention(dtype, a, w, bias, ln_stats, ln_c, k, vt, int(vt_rows), out, int(b), float(w_scale),
+                 float(act_scale(dtype) if a_scale is None else a_scale), float(ln_eps) if ln is not None else 0.0)
+
+
 _GROUPED = {"gemm": ("gemm_grouped", lambda entries: _gemm_grouped_entries(entries)),
-            "qkv_attention": ("qkv_attention_grouped", lambda entries: _qkv_attention_grouped_entries(entries))}
+            "qkv_attention": ("qkv_attention_grouped", lambda entries: _qkv_attention_grouped_entries(entries)),
+            "q_attention": ("q_attention_grouped", lambda entries: _q_attention_grouped_entries(entries))}
 
 
 @_op("wav_conv_in", "(int dtype, Tensor wav, Tensor w, Tensor? bias, Tensor? slope, Tensor(a!) out, int lout, int stride, int pad, "

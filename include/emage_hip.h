@@ -751,6 +751,25 @@ int emage_gather_clips(const int* order, long n_order, const int* cursor, int n_
  * fp32 once, as torch rounds the reference's Python float for the comparison.  The ratio is not clamped: above 1 every element is 1. */
 int emage_motion_mask(float* out, long n, double a, double b, unsigned long long seed, unsigned mask_id, const int* iteration, void* stream);
 
+/* A batch of audio windows cut out of the flat array that holds every recording end to end, in ONE launch (csrc/recordings.hip; the audio
+ * slices of EmageAudioModel.inference's windows, M:393-394 / M:441-442, for recordings of different lengths): row b of out (n rows of pitch
+ * ld_out >= samples floats) takes `samples` samples starting at offsets[b] (n 64-bit words on the device), audio_fmt EMAGE_PCM_S16 (decoded
+ * x * 2^-15) or EMAGE_PCM_F32 as in emage_gather_clips.  Rows may start at any sample of any recording: 16-byte loads from the first aligned
+ * sample of the source on, 16-byte stores where the destination is aligned at the same sample, single elements before and behind.  A row with
+ * offsets[b] < 0 or offsets[b] + samples > total_samples is zero-filled and ORs 1 into *status (one int32 on the device, sticky); nothing
+ * outside the array is ever read. */
+int emage_gather_windows(int audio_fmt, const void* audio, long total_samples, const long long* offsets, int n, int samples,
+                         float* out, long ld_out, int* status, void* stream);
+
+/* Table-driven row copies between two device buffers of src_rows / dst_rows rows of width_bytes bytes each, in ONE launch: `segments` holds
+ * n_segments rows of three 64-bit words {first source row, first destination row, rows} on the device; max_rows: an upper bound of every
+ * segment's length (it sizes the grid).  16-byte accesses where source and destination are aligned alike, 4-byte words or single bytes
+ * otherwise.  A segment that does not lie inside both buffers, or is longer than max_rows, is skipped and ORs 2 into *status; destination
+ * rows no segment names are left as they are.  Segments whose destinations overlap each other or their sources are the caller's error
+ * (pantomatrix_amd.ops.segment_table checks a table when it is built). */
+int emage_copy_segments(const void* src, long src_rows, void* dst, long dst_rows, const long long* segments, int n_segments,
+                        long width_bytes, long max_rows, int* status, void* stream);
+
 /* The metrics of one validation step (train_emage_audio.py:130-204, mode="val": get_rec_loss / get_cls_loss of the three eval forwards, the
  * arg-max codes) over the REAL clips of a padded batch, in two launches (csrc/val.hip).  `entries`: a HOST array of up to
  * EMAGE_VAL_MAX_ENTRIES rows, one per (forward, body part), validated here and carried to the device by value in the kernel arguments

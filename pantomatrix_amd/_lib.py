@@ -119,6 +119,8 @@ SIGNATURES = {
     "emage_dropout_mask": [_p, _l, _f, C.c_ulonglong, C.c_uint, _p, _i, _p],
     "emage_gather_clips": [_p, _l, _p, _i, _i, _p, _l, _i, _i, _p, _p, _p, _p, _l, _i, _p, _l, _p, _l, _p, _l, _l, _p, _l, _l, _p, _l, _l, _p, _l, _l, _p, _p],
     "emage_motion_mask": [_p, _l, _d, _d, C.c_ulonglong, C.c_uint, _p, _p],
+    "emage_gather_windows": [_i, _p, _l, _p, _i, _i, _p, _l, _p, _p],
+    "emage_copy_segments": [_p, _l, _p, _l, _p, _i, _l, _l, _p, _p],
     "emage_val_metrics_workspace_bytes": [_i, _i],
     "emage_val_metrics": [C.POINTER(ValEntry), _i, _i, _i, _p, _p, _p, _l, _p],
     "emage_mul_add": [_p, _i, _p, _i, _i, _p, _i, _p, _i, _i, _i, _p],

@@ -1550,6 +1550,73 @@ def gather_clips(order, cursor, n_batches, clips, arrays, out, status, *, frames
     return out
 
 
+@_op("gather_windows", "(Tensor audio, Tensor offsets, Tensor(a!) out, Tensor(b!) status) -> ()")
+def _gather_windows(audio, offsets, out, status):
+    fmt = _lib.PCM_S16 if audio.dtype == torch.int16 else _lib.PCM_F32
+    check(_lib.load().emage_gather_windows(fmt, _ptr(audio), audio.numel(), _ptr(offsets), out.shape[0], out.shape[1], _ptr(out), out.stride(0),
+                                           _ptr(status), _stream()), "gather_windows")
+
+
+def gather_windows(audio, offsets, out, status):
+    """One launch fills `out` (n, samples) float32 (unit inner stride) with the windows audio[offsets[b] : offsets[b] + samples] of the flat
+    1-D array `audio` (int16 decoded x * 2^-15, or float32); `offsets` (n,) int64 and `status` (one int32, sticky: bit 0 = a window outside
+    the array, zero-filled) on the device.  See include/emage_hip.h: emage_gather_windows."""
+    _dev(out)
+    assert audio.dtype in (torch.int16, torch.float32) and audio.dim() == 1 and audio.is_contiguous()
+    assert out.dtype == torch.float32 and out.dim() == 2 and out.stride(1) == 1 and out.shape[0] > 0
+    assert offsets.dtype == torch.int64 and offsets.dim() == 1 and offsets.numel() == out.shape[0] and (offsets.stride(0) == 1 or offsets.numel() <= 1)
+    assert status.dtype == torch.int32 and status.numel() == 1
+    for t in (audio, offsets, status):
+        assert t.device == out.device, "gather_windows: every tensor on the device of the batch"
+    _gather_windows(audio, offsets, out, status)
+    return out
+
+
+def segment_table(segments, src_rows, dst_rows, device=None, same_buffer=False):
+    """The (n, 3) int64 table {first source row, first destination row, rows} of `copy_segments`, checked on the host: every segment inside
+    its buffers, no two destinations overlapping (and, with same_buffer, no destination overlapping a source).  -> (table on `device` — or
+    the host array when device is None —, the longest segment)."""
+    import numpy as np
+    tab = np.asarray(segments, dtype=np.int64).reshape(-1, 3)
+    if tab.shape[0] == 0:
+        raise ValueError("segment_table: no segments")
+    s, d, n = tab[:, 0], tab[:, 1], tab[:, 2]
+    if (n <= 0).any() or (s < 0).any() or (d < 0).any() or (s + n > src_rows).any() or (d + n > dst_rows).any():
+        raise ValueError(f"segment_table: a segment lies outside its buffers ({src_rows} source rows, {dst_rows} destination rows)")
+    spans = [(int(a), int(a + k), 1) for a, k in zip(d, n)] + ([(int(a), int(a + k), 0) for a, k in zip(s, n)] if same_buffer else [])
+    spans.sort()
+    end_dst, end_src = -1, -1
+    for lo, hi, is_dst in spans:                 # sorted by start: an overlap shows against the furthest end so far (sources may overlap sources)
+        if lo < end_dst or (is_dst and lo < end_src):
+            raise ValueError("segment_table: segments overlap within one launch")
+        if is_dst:
+            end_dst = max(end_dst, hi)
+        else:
+            end_src = max(end_src, hi)
+    return (tab if device is None else torch.from_numpy(tab).to(device)), int(n.max())
+
+
+@_op("copy_segments", "(Tensor src, Tensor(a!) dst, Tensor segments, int width_bytes, int max_rows, Tensor(b!) status) -> ()")
+def _copy_segments(src, dst, segments, width_bytes, max_rows, status):
+    sb, db = src.numel() * src.element_size(), dst.numel() * dst.element_size()
+    check(_lib.load().emage_copy_segments(_ptr(src), sb // width_bytes, _ptr(dst), db // width_bytes, _ptr(segments), segments.shape[0], width_bytes,
+                                          max_rows, _ptr(status), _stream()), "copy_segments")
+
+
+def copy_segments(src, dst, segments, width_bytes, max_rows, status):
+    """One launch copies the row segments of `segments` ((n, 3) int64 on the device, `segment_table`) from `src` to `dst`: contiguous tensors
+    of one dtype, read as rows of `width_bytes` bytes; `max_rows`: the longest segment.  Destination rows no segment names keep their
+    contents; a segment outside the buffers is skipped and sets bit 1 of `status`.  See include/emage_hip.h: emage_copy_segments."""
+    _dev(dst)
+    assert src.is_contiguous() and dst.is_contiguous() and src.dtype == dst.dtype and width_bytes > 0 and width_bytes % src.element_size() == 0
+    assert segments.dtype == torch.int64 and segments.dim() == 2 and segments.shape[1] == 3 and segments.is_contiguous() and segments.shape[0] > 0
+    assert status.dtype == torch.int32 and status.numel() == 1
+    for t in (src, segments, status):
+        assert t.device == dst.device, "copy_segments: every tensor on one device"
+    _copy_segments(src, dst, segments, int(width_bytes), int(max_rows), status)
+    return dst
+
+
 @_op("val_metrics", "(Tensor[] recs, Tensor[] latents, Tensor[] logits, Tensor[] index, Tensor(a!)[] preds, int[] desc, float[] weights, int T, "
                     "Tensor n_valid, Tensor(b!) acc, Tensor(c!) workspace) -> ()")
 def _val_metrics(recs, latents, logits, index, preds, desc, weights, t, n_valid, acc, workspace):

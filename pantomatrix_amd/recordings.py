@@ -1,0 +1,560 @@
+"""The test pass on the device: whole recordings of different lengths generated as ONE lock-step batch — the reference's `inference_fn`
+(train_emage_audio.py:33-102, called every `test_steps` iterations) and the loop of test_emage_audio.py:96-105, which generate every
+recording alone at B = 1 (`librosa.load`, `model.inference`, `motion_vq.decode(get_global_motion=True, ref_trans=trans[:, 0])`,
+`beat_format_save`).  B = 1 is the worst operating point of this code: ~280 dependent launches of 64 rows per window.
+
+No kernel learns about lengths.  The window schedule of `inference()` (M:343-470) makes the ragged batch a STATIC schedule of ordinary ones:
+
+1. every recording runs `rounds_r = (T_r - 4) // 60` full windows of exactly 64 frames at starts 0, 60, 120, ...: window step i is an
+   ordinary batch of the recordings with rounds_r > i — one shape, one start, only the row count shrinks as short recordings finish;
+2. a tail window exists when remain_r > 4 and has 4 + remain_r frames (the whole recording when T_r < 64): recordings with the SAME tail
+   length form one ordinary batch although their tails start at different frames;
+3. the final decode is convolutional with zero padding at each recording's own end: it runs per group of recordings of EQUAL length, at
+   the true length — never on a zero-padded batch.
+
+Two data-movement kernels (csrc/recordings.hip) keep the pass free of host state, so it is capturable as one hipGraph per tuple of lengths:
+`emage_gather_windows` cuts the audio windows of a step / a tail group out of the flat array of all recordings, `emage_copy_segments` gathers
+a tail group's seed rows, scatters its codes into each recording's slot and packs every recording's result into one flat buffer per output
+(three device-to-host copies per pass, not three per recording).
+
+* ``window_schedule``   the schedule itself, pure Python (the host tests restate M:364-368 / M:428-431 against it);
+* ``RecordingSet``      the recordings of a split (``from_index``) or a list of waveforms / WAV files (``from_audio``) on the device;
+* ``RecordingRunner``   the pass for one tuple of lengths, eager or as one captured graph;
+* ``test_pass``         `inference_fn`: the index JSONs in, `<video_id>_output.npz` files and (test_list, save_list) out;
+* ``generate_folder``   the same for a folder of `*.wav` files (test_emage_audio.py: no seed, zero `ref_trans`)."""
+from __future__ import annotations
+
+import glob
+import json
+import os
+
+import numpy as np
+import torch
+
+from . import motion_io, ops
+from .data import SMPLX_FPS, _is_s16_mono, foot_contact_path
+
+MODEL_SR = 16000                                        # `inference()` hard-codes 16000 // 30 samples per frame (M:345, M:393)
+SPF = MODEL_SR // SMPLX_FPS
+SEED_DIMS = 337                                         # 55 joints x 6, trans, foot contact (T:59-60)
+WIDTHS = (("poses", 165), ("expressions", 100), ("trans", 3))
+STATUS_TEXT = "1: an audio window outside the flat array (zero-filled); 2: a copy segment outside its buffers (skipped)"
+
+
+class Schedule:
+    """What `window_schedule` returns.  rounds / remain / frames: per recording (frames = output frames).  steps: [(start frame, [ids of the
+    recordings that run full window i])]; tails: {tail length: [(recording id, start frame)]} in input order."""
+
+    def __init__(self, lengths, rounds, remain, frames, steps, tails, window, seed_frames):
+        self.lengths, self.rounds, self.remain, self.frames, self.steps, self.tails = lengths, rounds, remain, frames, steps, tails
+        self.window, self.seed_frames = window, seed_frames
+
+    @property
+    def n_windows(self):
+        """(recording, window) pairs of the schedule, tails included."""
+        return sum(len(ids) for _s, ids in self.steps) + sum(len(v) for v in self.tails.values())
+
+
+def window_schedule(lengths, window=64, seed_frames=4):
+    """The windows `EmageAudioModel.inference` (M:364-368, M:380-382, M:428-431) runs for recordings of `lengths` frames, as a lock-step
+    schedule -> `Schedule`.  Full windows: `rounds = (T - seed) // (window - seed)` of them at starts i * (window - seed), each keeping its
+    first window - seed frames.  Tail: when `remain = (T - seed) % (window - seed)` exceeds seed, seed + remain frames from
+    rounds * (window - seed), kept whole; T < window is a tail only, T == window one full window (window - seed frames out, no tail), and a
+    remainder of at most `seed` frames is dropped.  Output frames: (window - seed) * rounds + (seed + remain if remain > seed else 0)."""
+    pre, hop = int(seed_frames), int(window) - int(seed_frames)
+    if hop <= 0:
+        raise ValueError(f"window_schedule: window {window} must exceed seed_frames {seed_frames}")
+    lengths = [int(t) for t in lengths]
+    if any(t <= pre for t in lengths):
+        raise ValueError(f"window_schedule: every recording needs more than {pre} frames, got {lengths}")
+    rounds = [(t - pre) // hop for t in lengths]
+    remain = [(t - pre) % hop for t in lengths]
+    frames = [hop * r + (pre + m if m > pre else 0) for r, m in zip(rounds, remain)]
+    steps = [(i * hop, [k for k, r in enumerate(rounds) if r > i]) for i in range(max(rounds, default=0))]
+    tails = {}
+    for k, (r, m) in enumerate(zip(rounds, remain)):
+        if m > pre:
+            tails.setdefault(pre + m, []).append((k, r * hop))
+    return Schedule(lengths, rounds, remain, frames, steps, tails, int(window), pre)
+
+
+def frames_of(n_samples):
+    """M:345."""
+    return int(n_samples) * SMPLX_FPS // MODEL_SR
+
+
+def axis_angle_to_rot6d(aa):
+    """`rc.axis_angle_to_rotation_6d` (T:59) in host torch arithmetic, for the few seed frames of a recording: axis-angle -> quaternion
+    (small-angle branch below 1e-6) -> rotation matrix, first two rows.  (..., 3) -> (..., 6)."""
+    aa = torch.as_tensor(aa, dtype=torch.float32)
+    angles = torch.norm(aa, p=2, dim=-1, keepdim=True)
+    half = 0.5 * angles
+    small = angles.abs() < 1e-6
+    safe = torch.where(small, torch.ones_like(angles), angles)
+    s = torch.where(small, 0.5 - (angles * angles) / 48, torch.sin(half) / safe)
+    q = torch.cat([torch.cos(half), aa * s], dim=-1)
+    r, i, j, k = torch.unbind(q, -1)
+    two_s = 2.0 / (q * q).sum(-1)
+    return torch.stack((1 - two_s * (j * j + k * k), two_s * (i * j - k * r), two_s * (i * k + j * r),
+                        two_s * (i * j + k * r), 1 - two_s * (i * i + k * k), two_s * (j * k - i * r)), -1)
+
+
+def identity_seed(n, frames=4):
+    """(n, frames, 337): identity rot6d [1, 0, 0, 0, 1, 0] per joint, zero trans / foot contact (M:348-351)."""
+    seed = torch.zeros(n, frames, SEED_DIMS)
+    seed[:, :, 0:330:6] = 1.0
+    seed[:, :, 4:330:6] = 1.0
+    return seed
+
+
+def _load_wave(path, audio_sr, device, s16):
+    from . import audio as paudio
+    if s16:
+        return np.frombuffer(motion_io._wav_chunks(path)[1], dtype="<i2").copy()
+    if torch.device(device).type == "cuda":
+        return paudio.load_audio(path, audio_sr, device)[0]
+    return paudio.load_audio(path, audio_sr)[0]
+
+
+class RecordingSet:
+    """Whole recordings on the device: the flat audio array (`audio`, int16 when EVERY recording is int16 — decoded x * 2^-15 by the
+    kernel — else float32) with `sample_counts` / `sample_offsets`, and per recording the motion seed `seeds` (R, 4, 337) =
+    rot6d(poses[:4]) | trans[:4] | foot_contact[:4] and `ref_trans` (R, 3) = trans[0] (T:53-60, T:83).
+
+    The poses are RAW: `inference_fn` does not apply the dataset's `normalize` that `data.ClipStore` applies.  The rest of the ground-truth
+    motion is not kept: with `mask=None` the forward replaces every non-seed frame by the mask embedding (M:267-268) and the windows
+    re-seed themselves from their own decode (M:384-391), so only the first four frames of `masked_motion` ever reach the network.
+    Motion hints and masks beyond the seed are out of scope."""
+
+    def __init__(self, audios, device, seeds=None, ref_trans=None, items=None, audio_sr=MODEL_SR, seed_poses=None):
+        if audio_sr != MODEL_SR:
+            raise ValueError(f"RecordingSet: the model's windows are cut at {MODEL_SR} Hz (M:345), not {audio_sr}")
+        if not len(audios):
+            raise ValueError("RecordingSet: no recordings")
+        self.device, self.audio_sr = torch.device(device), int(audio_sr)
+        waves = []
+        for i, a in enumerate(audios):
+            a = a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a))
+            if a.dim() != 1 or a.dtype not in (torch.int16, torch.float32):
+                raise ValueError(f"RecordingSet: recording {i}: audio must be a 1-D int16 or float32 array, not {tuple(a.shape)} {a.dtype}")
+            waves.append(a)
+        self.audio_format = "int16" if all(a.dtype == torch.int16 for a in waves) else "float32"
+        dtype = torch.int16 if self.audio_format == "int16" else torch.float32
+        self.sample_counts = [int(a.numel()) for a in waves]
+        self.sample_offsets = np.cumsum([0] + self.sample_counts)
+        self.audio = torch.empty(int(self.sample_offsets[-1]), dtype=dtype, device=self.device)
+        for a, lo, hi in zip(waves, self.sample_offsets[:-1], self.sample_offsets[1:]):
+            self.audio[lo:hi].copy_(a if a.dtype == dtype else a.to(torch.float32) * (1.0 / 32768.0))
+        n = len(waves)
+        self.seeded = seeds is not None
+        seeds = identity_seed(n) if seeds is None else torch.as_tensor(seeds, dtype=torch.float32)
+        ref_trans = torch.zeros(n, 3) if ref_trans is None else torch.as_tensor(ref_trans, dtype=torch.float32)
+        if tuple(seeds.shape) != (n, 4, SEED_DIMS) or tuple(ref_trans.shape) != (n, 3):
+            raise ValueError(f"RecordingSet: seeds {tuple(seeds.shape)} / ref_trans {tuple(ref_trans.shape)}, expected ({n}, 4, {SEED_DIMS}) / ({n}, 3)")
+        self.seeds, self.ref_trans = seeds.to(self.device).contiguous(), ref_trans.to(self.device).contiguous()
+        self.items, self.seed_poses = items, seed_poses      # seed_poses: (R, 4, 165) host tensor, the raw axis-angle frames behind `seeds` (from_index)
+
+    def __len__(self):
+        return len(self.sample_counts)
+
+    @property
+    def frames(self):
+        return [frames_of(n) for n in self.sample_counts]
+
+    @classmethod
+    def from_audio(cls, audios, device, seeds=None, ref_trans=None, audio_sr=MODEL_SR):
+        """1-D waveforms (int16 / float32 arrays or tensors) or WAV paths — the test_emage_audio.py case: no motion, identity seed, zero
+        `ref_trans` unless given.  Paths load by the rule of `ClipStore.from_index`."""
+        paths = [a for a in audios if isinstance(a, (str, os.PathLike))]
+        s16 = all(_is_s16_mono(p, audio_sr) for p in paths)
+        waves = [_load_wave(a, audio_sr, device, s16) if isinstance(a, (str, os.PathLike)) else a for a in audios]
+        return cls(waves, device, seeds=seeds, ref_trans=ref_trans, audio_sr=audio_sr)
+
+    @classmethod
+    def from_index(cls, meta_paths, split="test", device="cuda", audio_sr=MODEL_SR):
+        """The reference's index JSONs (one path, a list of paths, or the items), filtered by `mode == split`, then the FIRST item per
+        `video_id` (T:38-42).  Each recording is loaded once: `beat_format_load`, the foot-contact `.npy` next to it, and the audio — the
+        file's int16 samples when every file is mono 16-bit PCM at `audio_sr`, else `audio.load_audio` (on the device when there is one)."""
+        if isinstance(meta_paths, (str, os.PathLike)):
+            meta_paths = [meta_paths]
+        items = []
+        for m in meta_paths:
+            if isinstance(m, dict):
+                items.append(m)
+            else:
+                with open(m, "r") as f:
+                    items.extend(json.load(f))
+        items = [it for it in items if it.get("mode") == split]
+        seen = set()
+        items = [it for it in items if not (it["video_id"] in seen or seen.add(it["video_id"]))]
+        if not items:
+            raise ValueError(f"RecordingSet.from_index: no item with mode == {split!r}")
+        s16 = all(_is_s16_mono(it["audio_path"], audio_sr) for it in items)
+        waves, seeds, ref, raw = [], [], [], []
+        for it in items:
+            rec = motion_io.beat_format_load(it["motion_path"], mask=None)
+            contact = np.load(foot_contact_path(it["motion_path"]))
+            poses, trans = np.asarray(rec["poses"], dtype=np.float32), np.asarray(rec["trans"], dtype=np.float32)
+            if min(poses.shape[0], trans.shape[0], contact.shape[0]) < 4:
+                raise ValueError(f"RecordingSet.from_index: {it['video_id']} has fewer than 4 motion frames")
+            rot6d = axis_angle_to_rot6d(torch.from_numpy(poses[:4]).reshape(4, -1, 3)).reshape(4, -1)
+            seeds.append(torch.cat([rot6d, torch.from_numpy(trans[:4]), torch.from_numpy(np.asarray(contact[:4], dtype=np.float32))], dim=-1))
+            ref.append(torch.from_numpy(trans[0]))
+            raw.append(torch.from_numpy(poses[:4].copy()))
+            waves.append(_load_wave(it["audio_path"], audio_sr, device, s16))
+        return cls(waves, device, seeds=torch.stack(seeds), ref_trans=torch.stack(ref), items=items, audio_sr=audio_sr, seed_poses=torch.stack(raw))
+
+
+class _Unit:
+    """One `forward` of the schedule: rows [lo, hi) of the length-sorted recordings at frame `start` (a full window), or a tail group."""
+    __slots__ = ("start", "lo", "hi", "seq", "need_seed")
+
+
+class _Tail:
+    __slots__ = ("t", "n", "offsets", "seed_segs", "code_segs")
+
+
+class _Decode:
+    __slots__ = ("lo", "hi", "frames", "segs")
+
+
+class RecordingRunner:
+    """The test pass for recordings of `lengths_in_samples` samples each (16 kHz), in input order.
+
+    Internally the recordings are sorted by length, longest first, so the recordings active in window step i are a PREFIX of the per-recording
+    buffers (seed chain, code buffers) and recordings of equal output length are neighbours: every full-window step is one `forward` on a row
+    range (split into groups of at most `max_batch` rows), reading its audio from a contiguous batch `emage_gather_windows` fills.  The
+    waveform-only work (WavEncoders, audio projection, cross-attention K / V) is hoisted ahead of the sequential loop as `_windows` does,
+    in chunks of at most `max_hoist_rows` (recording, window) sequences, so its memory is bounded.  Each tail group — the recordings
+    with the same tail length — is one `forward`: audio and seed rows gathered, codes scattered into each recording's slot by the two kernels.
+    The final decode runs per group of equal length at the true length with `get_global_motion=True` and each recording's own `ref_trans`;
+    its rows are packed into one flat buffer per output, in INPUT order.  Seed chain, lean code path and health counter are those of
+    `infer_codes` / `ClipRunner._step`; non-finite outputs raise FloatingPointError.
+
+    seeded: take the motion seeds and `ref_trans` of the `RecordingSet` handed to `__call__`; False: identity seed, zero `ref_trans`.
+    speaker_id: one id for every recording (both reference loops pass zeros).  audio_dtype: the flat array's dtype (torch.float32 / int16).
+
+    use_graph: the whole pass is ONE captured graph for this tuple of lengths; a second call with other audio of the same lengths replays
+    it — the periodic test pass of a training run.  New weights reach a replay as in `validation.Validator`: the packing of the model's
+    operand set is captured into a second graph over the same memory pool, and `__call__` replays it first whenever the model's version
+    stamp has moved (a training step, `load_state_dict`), so the pass reads operands packed from the current parameters at the addresses it
+    was captured with.  The VQ models are frozen in the reference's training (T:233-245); after changing THEM build a new runner."""
+
+    def __init__(self, model, vq_model, lengths_in_samples, seeded=False, use_graph=True, max_batch=64, max_hoist_rows=256, speaker_id=0,
+                 audio_dtype=torch.float32):
+        dev = model.device
+        model._require_device(dev)                          # an MI355X: there is no CPU path (the host tests lift this check over stand-in ops)
+        on_gpu = dev.type == "cuda"
+        if audio_dtype not in (torch.float32, torch.int16):
+            raise ValueError("audio_dtype must be torch.float32 or torch.int16")
+        c = model.config
+        self.model, self.vq, self.device, self.seeded = model, vq_model, dev, bool(seeded)
+        self.window, self.pre = int(c.pose_length), int(c.seed_frames)
+        self.max_batch, self.max_hoist_rows = int(max_batch), max(int(max_hoist_rows), int(max_batch))
+        if self.max_batch <= 0 or self.pre != 4:
+            raise ValueError("RecordingRunner: max_batch must be positive and the model's seed_frames 4")
+        self.sample_counts = [int(n) for n in lengths_in_samples]
+        self.sample_offsets = np.cumsum([0] + self.sample_counts)
+        n_rec = len(self.sample_counts)
+        self.schedule = sched = window_schedule([frames_of(n) for n in self.sample_counts], self.window, self.pre)
+        if min(sched.frames) == 0:
+            raise ValueError(f"RecordingRunner: recordings of {[t for t, f in zip(sched.lengths, sched.frames) if f == 0]} frames generate nothing "
+                             "(the reference's inference() fails on them too)")
+        self.order = sorted(range(n_rec), key=lambda r: -sched.lengths[r])                 # stable: input order among equal lengths
+        self.rank = {r: k for k, r in enumerate(self.order)}
+        self.frames_out = list(sched.frames)
+        self.out_offsets = np.cumsum([0] + self.frames_out)
+        self._plan(sched)
+        # ---- static buffers ----
+        lmax, w, mb = max(sched.lengths), self.window, min(self.max_batch, n_rec)
+        self.audio = torch.zeros(int(self.sample_offsets[-1]), dtype=audio_dtype, device=dev)
+        self.speaker_id = torch.full((n_rec, 1), int(speaker_id), dtype=torch.long, device=dev)
+        self.seed0 = identity_seed(n_rec).to(dev)                                      # sorted order, as every per-recording buffer below
+        self.seeds = torch.zeros(n_rec, self.pre, SEED_DIMS, device=dev)
+        self.ref_trans = torch.zeros(n_rec, 1, 3, device=dev)
+        self.tmpl_motion = identity_seed(mb, w).to(dev)                                # identity pose + all-ones mask (M:347-358), read-only
+        self.tmpl_mask = torch.ones_like(self.tmpl_motion)
+        routes = model._routes()
+        self.codes = {p: torch.zeros(n_rec, lmax, dtype=torch.int64, device=dev) for p, r in routes.items() if r}
+        n_win = max([c_[1] for c_ in self.chunks], default=0)
+        self.win_audio = torch.zeros(max(n_win, 1), w * SPF, device=dev)
+        tail_rows = max([g.n * g.t for g in self.tails], default=0)
+        self.tail_audio = torch.zeros(max(tail_rows, 1) * SPF, device=dev)
+        self.tail_seed = torch.zeros(mb, self.pre, SEED_DIMS, device=dev)
+        self.tail_codes = {p: torch.zeros(max(tail_rows, 1), dtype=torch.int64, device=dev) for p in self.codes}
+        total = int(self.out_offsets[-1])
+        self.flat = tuple(torch.zeros(total, wd, device=dev) for _k, wd in WIDTHS)
+        self.host = tuple(torch.zeros(total, wd, pin_memory=on_gpu) for _k, wd in WIDTHS)
+        self.flags = torch.zeros(2, dtype=torch.int32, device=dev)                     # [non-finite values, status word of the two kernels]
+        self.nonfinite, self.status = self.flags[0:1], self.flags[1:2]
+        self.flags_host = torch.zeros(2, dtype=torch.int32, pin_memory=on_gpu)
+        self._order_dev = torch.tensor(self.order, dtype=torch.long, device=dev)
+        self.precision = model.precision
+        self.graph, self._pack_graph, self._packed_stamp, self._operands = None, None, None, None
+        self._pass()                                                                    # packs weights, warms the allocator, validates shapes
+        if on_gpu:
+            torch.cuda.synchronize(dev)
+        if use_graph and on_gpu:
+            self._capture()
+
+    # ---- the static plan (host, once) ----------------------------------------------------------------------------------------------
+    def _plan(self, sched):
+        dev, w, hop = self.model.device, self.window, self.window - self.pre
+        srt_rounds = [sched.rounds[r] for r in self.order]
+        has_tail = [sched.remain[r] > self.pre for r in self.order]
+        units, offsets = [], []
+        for i in range(max(srt_rounds, default=0)):
+            active = sum(1 for r in srt_rounds if r > i)                                # a prefix: rounds is monotone in the length
+            for lo in range(0, active, self.max_batch):
+                u = _Unit()
+                u.start, u.lo, u.hi, u.seq = i * hop, lo, min(lo + self.max_batch, active), len(offsets)
+                u.need_seed = any(srt_rounds[k] > i + 1 or has_tail[k] for k in range(u.lo, u.hi))
+                offsets += [int(self.sample_offsets[self.order[k]]) + u.start * SPF for k in range(u.lo, u.hi)]
+                units.append(u)
+        # hoisting chunks: whole units, at most max_hoist_rows sequences each -> (first sequence, sequences, units)
+        self.chunks = []
+        for u in units:
+            n = u.hi - u.lo
+            if self.chunks and self.chunks[-1][1] + n <= self.max_hoist_rows:
+                s0, cnt, us = self.chunks[-1]
+                self.chunks[-1] = (s0, cnt + n, us + [u])
+            else:
+                self.chunks.append((u.seq, n, [u]))
+        self.units = units
+        self.win_offsets = torch.tensor(offsets, dtype=torch.int64, device=dev) if offsets else None
+        lmax, n_rec = max(sched.lengths), len(self.order)
+        self.tails = []
+        for t in sorted(sched.tails, reverse=True):
+            members = sched.tails[t]
+            for lo in range(0, len(members), self.max_batch):
+                grp = members[lo:lo + self.max_batch]
+                g = _Tail()
+                g.t, g.n = t, len(grp)
+                g.offsets = torch.tensor([int(self.sample_offsets[r]) + s * SPF for r, s in grp], dtype=torch.int64, device=dev)
+                g.seed_segs = ops.segment_table([(self.rank[r], j, 1) for j, (r, _s) in enumerate(grp)], n_rec, g.n, dev)[0]
+                g.code_segs = ops.segment_table([(j * t, self.rank[r] * lmax + s, t) for j, (r, s) in enumerate(grp)], g.n * t, n_rec * lmax, dev)[0]
+                self.tails.append(g)
+        self.decodes = []
+        k = 0
+        while k < n_rec:
+            f = sched.frames[self.order[k]]
+            hi = k + 1
+            while hi < n_rec and hi - k < self.max_batch and sched.frames[self.order[hi]] == f:
+                hi += 1
+            d = _Decode()
+            d.lo, d.hi, d.frames = k, hi, f
+            d.segs = ops.segment_table([(j * f, int(self.out_offsets[self.order[k + j]]), f) for j in range(hi - k)], (hi - k) * f,
+                                       int(self.out_offsets[-1]), dev)[0]
+            self.decodes.append(d)
+            k = hi
+
+    @property
+    def steps(self):
+        """`forward` calls of one pass (full-window units + tail groups)."""
+        return len(self.units) + len(self.tails)
+
+    @property
+    def mean_batch(self):
+        """Mean rows per `forward` of the pass."""
+        rows = sum(u.hi - u.lo for u in self.units) + sum(g.n for g in self.tails)
+        return rows / max(self.steps, 1)
+
+    # ---- the pass: launches only, no host state ---------------------------------------------------------------------------------------
+    def _flush_health(self, pending):
+        if pending:
+            ops.count_nonfinite_multi(list(pending), self.nonfinite)
+            del pending[:]
+
+    def _sliced_tables(self, tables, n):
+        from .modeling_emage_audio import _X
+        m = n * self.window
+        f0 = tables["face0"]
+        face0 = _X(f0.a[:m], f0.a[:m] if f0.r is f0.a else f0.r[:m], f0.h2r, f0.ln)
+        return dict(spk_body=tables["spk_body"][:m], face0=face0, pos_spk=tables["pos_spk"][:m], t=self.window)
+
+    def _pass(self):
+        """The three phases in order; the tool times them one by one."""
+        self._full_windows()
+        self._tail_groups()
+        self._decode()
+
+    def _full_windows(self):
+        from .modeling_emage_audio import _Ctx, Fork
+        model, vq, w, pre = self.model, self.vq, self.window, self.pre
+        self.nonfinite.zero_()
+        self.seeds.copy_(self.seed0)
+        model.health_pending = pending = []
+        try:
+            tables = None
+            if self.units:
+                nmax = max(u.hi - u.lo for u in self.units)
+                tables = model._speaker_tables(_Ctx(model._engine()), self.speaker_id[:nmax], nmax, w)
+            for s0, cnt, units in self.chunks:
+                win = self.win_audio[:cnt]
+                ops.gather_windows(self.audio, self.win_offsets[s0:s0 + cnt], win, self.status)
+                feats = None
+                if model.hoist_audio:                       # the waveform-only work of the chunk's windows: one set of launches on `cnt` sequences
+                    with Fork(self.device, 3, model.concurrent) as fk:
+                        feats = model._audio_features(_Ctx(model._engine()), win, cnt, w, True, fk, 1, 2)
+                    if feats["ta"] != w:
+                        feats = None
+                for u in units:
+                    n, k0 = u.hi - u.lo, u.seq - s0
+                    f = None
+                    if feats is not None:
+                        ta = feats["ta"]
+                        f = dict(memcat=feats["memcat"][k0 * w:(k0 + n) * w], ta=ta, bk=feats["bk"][k0 * ta:(k0 + n) * ta], bvt=feats["bvt"][k0:k0 + n])
+                    net = model.forward(win[k0:k0 + n], self.speaker_id[:n], self.tmpl_motion[:n], self.tmpl_mask[:n], use_audio=True,
+                                        _audio_feats=f, _tables=self._sliced_tables(tables, n), _lean=True, _seed=self.seeds[u.lo:u.hi])
+                    codes = {p: v[u.lo:u.hi] for p, v in self.codes.items()}
+                    model._window_codes(net, vq, codes, u.start, n, w)
+                    self._flush_health(pending)
+                    if u.need_seed:                         # M:412-418: only the last frames of the decode feed the next window's seed
+                        ts = model._seed_decode_frames(vq, w) if model.seed_only_decode else w
+                        sel = {f"{p}_index": v[:, u.start + w - ts:u.start + w] for p, v in codes.items()}
+                        dec = vq.decode(**sel)["all_motion4inference"]
+                        self.seeds[u.lo:u.hi].copy_(dec[:, ts - pre:])
+                del feats
+        finally:
+            model.health_pending = None
+
+    def _tail_groups(self):
+        model, vq, pre = self.model, self.vq, self.pre
+        model.health_pending = pending = []
+        try:
+            for g in self.tails:
+                n, t = g.n, g.t
+                a = self.tail_audio[:n * t * SPF].view(n, t * SPF)
+                ops.gather_windows(self.audio, g.offsets, a, self.status)
+                ops.copy_segments(self.seeds, self.tail_seed, g.seed_segs, pre * SEED_DIMS * 4, 1, self.status)
+                net = model.forward(a, self.speaker_id[:n], self.tmpl_motion[:n, :t], self.tmpl_mask[:n, :t], use_audio=True, _lean=True,
+                                    _seed=self.tail_seed[:n])
+                model._window_codes(net, vq, {p: v[:n * t].view(n, t) for p, v in self.tail_codes.items()}, 0, n, t)
+                self._flush_health(pending)
+                for p, v in self.tail_codes.items():
+                    ops.copy_segments(v, self.codes[p], g.code_segs, 8, t, self.status)
+        finally:
+            model.health_pending = None
+
+    def _decode(self):
+        vq = self.vq
+        for d in self.decodes:
+            sel = {f"{p}_index": v[d.lo:d.hi, :d.frames] for p, v in self.codes.items()}
+            pred = vq.decode(**sel, get_global_motion=True, ref_trans=self.ref_trans[d.lo:d.hi])
+            outs = [pred["motion_axis_angle"].contiguous(), pred["expression"].contiguous(), pred["trans"].contiguous()]
+            ops.count_nonfinite_multi(outs, self.nonfinite)
+            for src, dst, (_k, wd) in zip(outs, self.flat, WIDTHS):
+                ops.copy_segments(src, dst, d.segs, wd * 4, d.frames, self.status)
+
+    def _capture(self):
+        model, vq = self.model, self.vq
+        pack_graph, graph = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
+        with torch.cuda.graph(pack_graph, capture_error_mode="thread_local"):
+            model.invalidate_packed()
+            packed = model._engine()
+        with torch.cuda.graph(graph, pool=pack_graph.pool(), capture_error_mode="thread_local"):
+            self._pass()
+        if model._packed is not packed:
+            raise RuntimeError("RecordingRunner: the pass re-packed the operand set the packing graph had just built")
+        self._pack_graph, self.graph, self._packed_stamp = pack_graph, graph, None      # the first replay packs
+        # what the captured launches read (and the packing graph re-writes): alive as long as the graphs, and nobody else's
+        self._operands = (packed, [m._packed for m in vq._models()], dict(vq._templates))
+        model.invalidate_packed()
+
+    # ---- one pass end to end ------------------------------------------------------------------------------------------------------------
+    def load(self, recording_set):
+        """Copy a set's audio (and, when `seeded`, its seeds and `ref_trans`) into the runner's input buffers (stream-ordered)."""
+        rs = recording_set
+        if list(rs.sample_counts) != self.sample_counts:
+            raise ValueError("RecordingRunner: this runner was built for other recording lengths (one runner, one graph, per tuple of lengths)")
+        if rs.audio.dtype != self.audio.dtype:
+            raise ValueError(f"RecordingRunner: the set's audio is {rs.audio.dtype}, the runner was built with audio_dtype={self.audio.dtype}")
+        self.audio.copy_(rs.audio, non_blocking=True)
+        if self.seeded:
+            self.seed0.copy_(rs.seeds.to(self.device).index_select(0, self._order_dev))
+            self.ref_trans.copy_(rs.ref_trans.to(self.device).index_select(0, self._order_dev).view(-1, 1, 3))
+
+    def run_device(self):
+        """One pass over the current input buffers, on the current stream; the results stay in `flat` (rows in input order)."""
+        if self.graph is None:
+            self._pass()
+            return
+        stamp = self.model._version_stamp()
+        if stamp != self._packed_stamp:
+            self._pack_graph.replay()
+            self._packed_stamp = stamp
+        self.graph.replay()
+
+    def __call__(self, recording_set=None):
+        """-> [(poses (T_r, 165), expressions (T_r, 100), trans (T_r, 3))] per recording in input order: numpy views of pinned buffers,
+        valid until the next call."""
+        if recording_set is not None:
+            self.load(recording_set)
+        self.run_device()
+        for h, d in zip(self.host, self.flat):
+            h.copy_(d, non_blocking=True)
+        self.flags_host.copy_(self.flags, non_blocking=True)
+        if self.device.type == "cuda":
+            torch.cuda.current_stream(self.device).synchronize()
+        bad, status = int(self.flags_host[0]), int(self.flags_host[1])
+        if status:
+            self.status.zero_()
+            raise RuntimeError(f"RecordingRunner: the data-movement kernels reported status {status} ({STATUS_TEXT})")
+        if bad:
+            raise FloatingPointError(f"{bad} non-finite values among the network outputs / the generated motion (precision {self.precision!r}): in f16x3 an "
+                                     "activation beyond |x| < 4094 overflows the fp16 planes — run this checkpoint with set_precision('fp32')")
+        host = [h.numpy() for h in self.host]
+        return [tuple(h[self.out_offsets[r]:self.out_offsets[r + 1]] for h in host) for r in range(len(self.sample_counts))]
+
+    def codes_of(self, r):
+        """The code indices of recording `r` (input order) from the last pass: {part: (frames,) int64 device tensor}."""
+        return {p: v[self.rank[r], :self.frames_out[r]] for p, v in self.codes.items()}
+
+    @classmethod
+    def for_set(cls, model, vq_model, recording_set, **kw):
+        kw.setdefault("seeded", recording_set.seeded)
+        return cls(model, vq_model, recording_set.sample_counts, audio_dtype=recording_set.audio.dtype, **kw)
+
+
+def _save_outputs(results, names, audio_paths, save_path, pose_fps):
+    os.makedirs(save_path, exist_ok=True)
+    save_list = []
+    for (poses, expressions, trans), name, audio_path in zip(results, names, audio_paths):
+        out = os.path.join(save_path, f"{name}_output.npz")
+        motion_io.beat_format_save(out, poses, upsample=SMPLX_FPS // pose_fps, expressions=expressions, trans=trans)      # T:91
+        save_list.append({"audio_path": audio_path, "motion_path": out, "video_id": name})
+    return save_list
+
+
+def test_pass(model, vq, meta_paths, save_path, runner=None, pose_fps=None, device=None):
+    """`inference_fn` (T:33-102): generate every test recording of the index JSONs and write `<video_id>_output.npz`
+    -> (test_list, save_list) with the reference's keys.  runner: a `RecordingRunner` built for these recordings (the periodic test pass of
+    a training run keeps one and replays its graph) or any callable `recording_set -> [(poses, expressions, trans)]`; None builds one."""
+    if device is None:
+        device = getattr(runner, "device", None) or model.device
+    rs = RecordingSet.from_index(meta_paths, "test", device)
+    if runner is None:
+        runner = RecordingRunner.for_set(model, vq, rs)
+    if pose_fps is None:
+        pose_fps = int(getattr(getattr(model, "config", None), "pose_fps", SMPLX_FPS))
+    results = runner(rs)
+    save_list = _save_outputs(results, [it["video_id"] for it in rs.items], [it["audio_path"] for it in rs.items], save_path, pose_fps)
+    return rs.items, save_list
+
+
+test_pass.__test__ = False                               # a library function, not a pytest case
+
+
+def generate_folder(model, vq, audio_folder, save_folder, runner=None, pose_fps=None):
+    """test_emage_audio.py:96-105: every `*.wav` of `audio_folder` (sorted) -> `<stem>_output.npz` in `save_folder`, no seed and zero
+    `ref_trans` -> save_list."""
+    paths = sorted(glob.glob(os.path.join(audio_folder, "*.wav")))
+    if not paths:
+        raise ValueError(f"generate_folder: no *.wav in {audio_folder}")
+    rs = RecordingSet.from_audio(paths, getattr(runner, "device", None) or model.device)
+    if runner is None:
+        runner = RecordingRunner.for_set(model, vq, rs)
+    if pose_fps is None:
+        pose_fps = int(getattr(getattr(model, "config", None), "pose_fps", SMPLX_FPS))
+    names = [os.path.splitext(os.path.basename(p))[0] for p in paths]
+    return _save_outputs(runner(rs), names, paths, save_folder, pose_fps)

@@ -308,8 +308,8 @@ __global__ __launch_bounds__(C.waves() * 64, C.occ * C.waves() / 4) void gemm_h2
     // XCD-aware order over the WHOLE grid: each XCD walks a contiguous run of the concatenated tile list, i.e. mostly one problem
     // (its W panel stays in that XCD's L2)
     const int bid = xcd_run_order((int)blockIdx.x, g.total);
-    // which problem is this block in (written out here and in qkv_attention.hip: moved into a shared function, the same scan
-    // makes the compiler number these kernels' scalar registers differently)
+    // which problem is this block in (written out here, in qkv_attention.hip and in q_attention.hip: moved into a shared function,
+    // the same scan makes the compiler number these kernels' scalar registers differently)
     int pi = 0;
 #pragma unroll
     for (int i = 0; i < MAXG - 1; ++i) pi += (i + 1 < g.n && bid >= g.tile_end[i]) ? 1 : 0;

@@ -16,6 +16,7 @@
 #include <math.h>
 #include "h2_tile.h"
 #include "attn_tile.h"
+#include "attn_site.h"
 
 namespace emage_dev {
 
@@ -30,11 +31,7 @@ struct QAttnArgs {
     void* out;                               // att: (B T, ldo) EMAGE_H2 image
     int ldk, ldvt, vt_rows, ldo;
 };
-struct QAttnGroup {
-    QAttnArgs p[CA_MAXG];
-    int blk_end[CA_MAXG];                    // running sum of B H
-    int n, total;
-};
+using QAttnGroup = SiteGroup<QAttnArgs, CA_MAXG>;
 
 }  // namespace emage_dev
 
@@ -134,50 +131,23 @@ __global__ __launch_bounds__(CA_THREADS, 1) void q_attn_kernel(QAttnGroup g) {
     attn_tile<float, CA_HD, 4, 1, true, true, true, true>(a, b, h, wave, 0, smem);
 }
 
+// what the site adds to the shared refusals (attn_site.h): its shape and the layer's memory K / V^T with their limits; N = d
 int make_problem(int dtype, const emage_q_attention_problem& q, int T, int Tk, int d, int H, const H2Scale& hs, QAttnArgs& r) {
-    if (dtype != EMAGE_H2 || T != CA_T || Tk != CA_T || d != CA_D || H != CA_H) return EMAGE_EINVAL;
-    if (!q.A || !q.W || !q.bias || !q.k || !q.vt || !q.out || q.B <= 0) return EMAGE_EINVAL;
-    if (((uintptr_t)q.A | (uintptr_t)q.W | (uintptr_t)q.bias | (uintptr_t)q.k | (uintptr_t)q.vt | (uintptr_t)q.out) & 15) return EMAGE_EINVAL;
-    if (q.lda % 8 || q.lda < d || q.ldo % 8 || q.ldo < d) return EMAGE_EINVAL;
+    if (T != CA_T || Tk != CA_T || d != CA_D || H != CA_H) return EMAGE_EINVAL;
+    const int rc = site_check(dtype, q, T, d);
+    if (rc) return rc;
+    if (!q.k || !q.vt || (((uintptr_t)q.k | (uintptr_t)q.vt) & 15)) return EMAGE_EINVAL;
     if (q.ldk % 4 || q.ldk < d || q.ldvt % 32 || q.ldvt < Tk || q.vt_rows < d) return EMAGE_EINVAL;
-    if (!(q.a_scale > 0.f && q.w_scale > 0.f)) return EMAGE_EINVAL;
-    if (q.ln_stats && (!q.ln_c || ((uintptr_t)q.ln_stats & 15) || ((uintptr_t)q.ln_c & 15) || !(q.ln_eps > 0.f))) return EMAGE_EINVAL;
-    const long rows = (long)q.B * T;
-    if (rows * q.lda * 4 >= (1L << 31) || rows * q.ldo * 4 >= (1L << 31)) return EMAGE_EINVAL;
     if ((long)q.B * Tk * q.ldk * 4 >= (1L << 31) || (long)q.B * q.vt_rows * q.ldvt * 4 >= (1L << 31)) return EMAGE_EINVAL;
-    GemmArgs a = {};
-    a.A = q.A; a.W = q.W; a.bias = q.bias;
-    a.lda = q.lda;
-    a.M = (int)rows; a.N = d; a.K = d; a.Cp = d;
-    set_geometry(a, 1, 1, 0, a.M, a.M);
-    a.t_col0 = a.N; a.t_rows = 1;
-    a.ksplit = 1;
-    a.a_scale = q.a_scale;
-    a.o_scale = 1.f / (q.a_scale * q.w_scale);    // as emage_gemm computes it
-    a.h2s = hs.s; a.h2i = hs.inv;
-    a.ln_stats = q.ln_stats; a.ln_np = q.ln_stats ? 24 : 0; a.ln_c = q.ln_stats ? q.ln_c : nullptr; a.ln_eps = q.ln_eps;
-    r.g = a;
+    r.g = site_projection(q, T, d, d, hs);
     r.k = q.k; r.vt = q.vt; r.out = q.out;
     r.ldk = q.ldk; r.ldvt = q.ldvt; r.vt_rows = q.vt_rows; r.ldo = q.ldo;
     return 0;
 }
 
 int q_attention_impl(int dtype, const emage_q_attention_problem* problems, int n, int T, int Tk, int d, int H, hipStream_t s) {
-    H2Scale hs;
-    if (h2_dtype(dtype, hs) || !problems || n <= 0 || n > CA_MAXG) return EMAGE_EINVAL;
-    QAttnGroup g;
-    int total = 0;
-    for (int i = 0; i < n; ++i) {
-        const int rc = make_problem(dtype, problems[i], T, Tk, d, H, hs, g.p[i]);
-        if (rc) return rc;
-        total += problems[i].B * H;
-        g.blk_end[i] = total;
-    }
-    for (int i = n; i < CA_MAXG; ++i) { g.p[i] = g.p[0]; g.blk_end[i] = total; }
-    g.n = n;
-    g.total = total;
-    hipLaunchKernelGGL(q_attn_kernel, dim3(total), dim3(CA_THREADS), 0, s, g);
-    return launch_status();
+    const auto make = [=](int dt, const emage_q_attention_problem& q, const H2Scale& hs, QAttnArgs& r) { return make_problem(dt, q, T, Tk, d, H, hs, r); };
+    return launch_sites(dtype, problems, n, H, make, q_attn_kernel, CA_THREADS, s);
 }
 
 }  // namespace

@@ -14,6 +14,7 @@
 #include <math.h>
 #include "h2_tile.h"
 #include "attn_tile.h"
+#include "attn_site.h"
 
 namespace emage_dev {
 
@@ -26,11 +27,7 @@ struct QkvAttnArgs {
     GemmArgs g;              // the projection as emage_gemm runs it (M = B T, N = 3 d, K = d; no outputs of its own)
     void* out; int ldo;      // att: (B T, ldo) EMAGE_H2 image
 };
-struct QkvAttnGroup {
-    QkvAttnArgs p[QA_MAXG];
-    int blk_end[QA_MAXG];    // running sum of B H
-    int n, total;
-};
+using QkvAttnGroup = SiteGroup<QkvAttnArgs, QA_MAXG>;
 
 }  // namespace emage_dev
 
@@ -121,46 +118,19 @@ __global__ __launch_bounds__(QA_THREADS, 1) void qkv_attn_kernel(QkvAttnGroup g)
     attn_tile<float, QA_HD, 4, 1, true, true, true, true>(a, b, h, wave, 0, smem);
 }
 
+// what the site adds to the shared refusals (attn_site.h): its shape; the projection is the packed in_proj, N = 3 d
 int make_problem(int dtype, const emage_qkv_attention_problem& q, int T, int d, int H, const H2Scale& hs, QkvAttnArgs& r) {
-    if (dtype != EMAGE_H2 || T != QA_T || d != QA_D || H != QA_H) return EMAGE_EINVAL;
-    if (!q.A || !q.W || !q.bias || !q.out || q.B <= 0) return EMAGE_EINVAL;
-    if ((((uintptr_t)q.A | (uintptr_t)q.W | (uintptr_t)q.bias | (uintptr_t)q.out) & 15) || q.lda % 8 || q.lda < d || q.ldo % 8 || q.ldo < d) return EMAGE_EINVAL;
-    if (!(q.a_scale > 0.f && q.w_scale > 0.f)) return EMAGE_EINVAL;
-    if (q.ln_stats && (!q.ln_c || ((uintptr_t)q.ln_stats & 15) || ((uintptr_t)q.ln_c & 15) || !(q.ln_eps > 0.f))) return EMAGE_EINVAL;
-    const long rows = (long)q.B * T;
-    if (rows * q.lda * 4 >= (1L << 31) || rows * q.ldo * 4 >= (1L << 31)) return EMAGE_EINVAL;
-    GemmArgs a = {};
-    a.A = q.A; a.W = q.W; a.bias = q.bias;
-    a.lda = q.lda;
-    a.M = (int)rows; a.N = 3 * d; a.K = d; a.Cp = d;
-    set_geometry(a, 1, 1, 0, a.M, a.M);
-    a.t_col0 = a.N; a.t_rows = 1;
-    a.ksplit = 1;
-    a.a_scale = q.a_scale;
-    a.o_scale = 1.f / (q.a_scale * q.w_scale);    // as emage_gemm computes it
-    a.h2s = hs.s; a.h2i = hs.inv;
-    a.ln_stats = q.ln_stats; a.ln_np = q.ln_stats ? 24 : 0; a.ln_c = q.ln_stats ? q.ln_c : nullptr; a.ln_eps = q.ln_eps;
-    r.g = a;
+    if (T != QA_T || d != QA_D || H != QA_H) return EMAGE_EINVAL;
+    const int rc = site_check(dtype, q, T, d);
+    if (rc) return rc;
+    r.g = site_projection(q, T, 3 * d, d, hs);
     r.out = q.out; r.ldo = q.ldo;
     return 0;
 }
 
 int qkv_attention_impl(int dtype, const emage_qkv_attention_problem* problems, int n, int T, int d, int H, hipStream_t s) {
-    H2Scale hs;
-    if (h2_dtype(dtype, hs) || !problems || n <= 0 || n > QA_MAXG) return EMAGE_EINVAL;
-    QkvAttnGroup g;
-    int total = 0;
-    for (int i = 0; i < n; ++i) {
-        const int rc = make_problem(dtype, problems[i], T, d, H, hs, g.p[i]);
-        if (rc) return rc;
-        total += problems[i].B * H;
-        g.blk_end[i] = total;
-    }
-    for (int i = n; i < QA_MAXG; ++i) { g.p[i] = g.p[0]; g.blk_end[i] = total; }
-    g.n = n;
-    g.total = total;
-    hipLaunchKernelGGL(qkv_attn_kernel, dim3(total), dim3(QA_THREADS), 0, s, g);
-    return launch_status();
+    const auto make = [=](int dt, const emage_qkv_attention_problem& q, const H2Scale& hs, QkvAttnArgs& r) { return make_problem(dt, q, T, d, H, hs, r); };
+    return launch_sites(dtype, problems, n, H, make, qkv_attn_kernel, QA_THREADS, s);
 }
 
 }  // namespace

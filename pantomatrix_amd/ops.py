@@ -507,6 +507,59 @@ def splitk_scope(scratch):
     return cm()
 
 
+class _ProblemTable:
+    """One problem structure of `_lib` as the words the grouped operators carry (`int[] desc`, `float[] scales`): per problem every
+    non-float field in `_fields_` order (device addresses as integers, 0 = NULL) and every float field in order.  The structure's
+    `_fields_` is the one place that spells the order out."""
+
+    def __init__(self, struct):
+        self.struct = struct
+        self.ints = tuple(n for n, t in struct._fields_ if t is not C.c_float)
+        self.floats = tuple(n for n, t in struct._fields_ if t is C.c_float)
+        self._int_fields = tuple((n, t is C.c_void_p) for n, t in struct._fields_ if t is not C.c_float)
+
+    def pack(self, fields):
+        """The field dict of one problem -> (its int words, its float words)."""
+        return [int(fields[k] or 0) for k in self.ints], [float(fields[k]) for k in self.floats]
+
+    def array(self, desc, scales):
+        """The words of n problems -> (ctypes array of the structure, n)."""
+        ki, kf = len(self.ints), len(self.floats)
+        n = len(desc) // ki
+        arr = (self.struct * n)()
+        for i in range(n):
+            p = arr[i]
+            for (name, is_ptr), v in zip(self._int_fields, desc[i * ki:(i + 1) * ki]):
+                setattr(p, name, (v or None) if is_ptr else v)
+            for name, v in zip(self.floats, scales[i * kf:(i + 1) * kf]):
+                setattr(p, name, v)
+        return arr, n
+
+
+def _pack_entries(table, fields, entries):
+    """Recorded calls (Lockstep) of ONE dtype -> what the grouped operator of their kind takes: (dtype, every tensor among the recorded
+    arguments in order, desc, scales).  `fields` maps a call's arguments to the field dict of its problem."""
+    dtype = entries[0][2][0]
+    tensors, desc, scales = [], [], []
+    for _name, _op_, args, _meta in entries:
+        ints, floats = table.pack(fields(*args))
+        desc += ints
+        scales += floats
+        tensors += [t for t in args if isinstance(t, torch.Tensor)]
+    return dtype, tensors, desc, scales
+
+
+def _grouped(kind, table, fields, grouped, max_per_call=None):
+    """One line of `_GROUPED`: (kind, recorded calls of ONE dtype -> calls of the operator `grouped` with at most `max_per_call` problems
+    each; None: one call, the library cuts it into launches itself)."""
+    def issue(entries):
+        assert all(e[2][0] == entries[0][2][0] for e in entries)
+        step = max_per_call or len(entries)
+        for i in range(0, len(entries), step):
+            grouped.op(*_pack_entries(table, fields, entries[i:i + step]))
+    return kind, issue
+
+
 def _gemm_fields(dtype, a, w, bias, slope, res, out, out_f32, out_t, n, cp, n_store, t_col0, t_rows, res_first, taps, stride, pad, lin, lout, m,
                  w_scale, a_scale, res_h2, ln_stats=None, ln_c=None, rs_stats=None, rs_gamma=None, rs_beta=None, st_out=None, ln_eps=0.0,
                  sk_ws=None, sk_count=None):
@@ -526,6 +579,12 @@ def _gemm_fields(dtype, a, w, bias, slope, res, out, out_f32, out_t, n, cp, n_st
                 sk_count=_ptr(sk_count), sk_tiles=sk_count.numel() if sk_count is not None else 0)
 
 
+_GEMM_TABLE = _ProblemTable(_lib.GemmProblem)
+# the flat argument list of emage_gemm / emage_gemm_ws between `dtype` and what follows w_scale, in the prototype's order
+_GEMM_FLAT = ("A", "lda", "W", "bias", "slope", "res", "ldr", "res_is_f32", "res_first", "out", "ldo", "n_store", "out_f32", "ldf", "out_t",
+              "t_col0", "t_rows", "t_ld", "M", "N", "Cp", "taps", "stride", "pad", "Lin", "Lout", "a_scale", "w_scale")
+
+
 @_op("gemm", "(int dtype, Tensor a, Tensor w, Tensor? bias, Tensor? slope, Tensor? res, Tensor(a!)? out, Tensor(b!)? out_f32, "
              "Tensor(c!)? out_t, int n, int cp, int n_store, int t_col0, int t_rows, bool res_first, int taps, int stride, int pad, "
              "int lin, int lout, int m, float w_scale, float a_scale, bool res_h2, Tensor? ln_stats=None, Tensor? ln_c=None, "
@@ -534,12 +593,10 @@ def _gemm_fields(dtype, a, w, bias, slope, res, out, out_f32, out_t, n, cp, n_st
 def _gemm(dtype, *args):
     f = _gemm_fields(dtype, *args)
     if f["ln_stats"] or f["rs_stats"] or f["st_out"] or f["sk_ws"]:     # LayerNorm fold / split-K scratch: the problem-struct entry point carries those fields
-        arr, n = _problem_array([int(f[k] or 0) for k in _GEMM_PROBLEM_INTS], [float(f["a_scale"]), float(f["w_scale"]), float(f["ln_eps"])])
+        arr, n = _GEMM_TABLE.array(*_GEMM_TABLE.pack(f))
         check(_lib.load().emage_gemm_grouped(dtype, arr, n, _stream()), "gemm (LayerNorm fold)")
         return
-    check(_lib.load().emage_gemm(dtype, f["A"], f["lda"], f["W"], f["bias"], f["slope"], f["res"], f["ldr"], f["res_is_f32"], f["res_first"],
-                                 f["out"], f["ldo"], f["n_store"], f["out_f32"], f["ldf"], f["out_t"], f["t_col0"], f["t_rows"], f["t_ld"],
-                                 f["M"], f["N"], f["Cp"], f["taps"], f["stride"], f["pad"], f["Lin"], f["Lout"], f["a_scale"], f["w_scale"], _stream()), "gemm")
+    check(_lib.load().emage_gemm(dtype, *[f[k] for k in _GEMM_FLAT], _stream()), "gemm")
 
 
 @_op("gemm_ws", "(int dtype, Tensor a, Tensor w, Tensor? bias, Tensor? slope, Tensor? res, Tensor(a!)? out, Tensor(b!)? out_f32, "
@@ -548,64 +605,25 @@ def _gemm(dtype, *args):
 def _gemm_ws(dtype, *args):
     ws = args[-1]
     f = _gemm_fields(dtype, *args[:-1])
-    check(_lib.load().emage_gemm_ws(dtype, f["A"], f["lda"], f["W"], f["bias"], f["slope"], f["res"], f["ldr"], f["res_is_f32"], f["res_first"],
-                                    f["out"], f["ldo"], f["n_store"], f["out_f32"], f["ldf"], f["out_t"], f["t_col0"], f["t_rows"], f["t_ld"],
-                                    f["M"], f["N"], f["Cp"], f["taps"], f["stride"], f["pad"], f["Lin"], f["Lout"], f["a_scale"], f["w_scale"],
-                                    _ptr(ws), ws.numel() * ws.element_size(), _stream()), "gemm_ws")
+    check(_lib.load().emage_gemm_ws(dtype, *[f[k] for k in _GEMM_FLAT], _ptr(ws), ws.numel() * ws.element_size(), _stream()), "gemm_ws")
 
 
-# Descriptor-table operator: `tensors` lists every tensor the problems touch (dispatch key, aliasing: they may be written), `desc` holds
-# per problem the 26 integer words of `emage_gemm_problem` in field order (device addresses first), `scales` its (a_scale, w_scale).
-_GEMM_PROBLEM_PTRS = ("A", "W", "bias", "slope", "res", "out", "out_f32", "out_t", "ln_stats", "ln_c", "rs_stats", "rs_gamma", "rs_beta", "st_out", "sk_ws", "sk_count")
-_GEMM_PROBLEM_INTS = ("A", "W", "bias", "slope", "res", "out", "out_f32", "out_t", "lda", "ldr", "res_is_f32", "res_first", "ldo", "n_store", "ldf",
-                      "t_col0", "t_rows", "t_ld", "M", "N", "Cp", "taps", "stride", "pad", "Lin", "Lout",
-                      "ln_stats", "ln_c", "rs_stats", "rs_gamma", "rs_beta", "st_out", "ln_np", "rs_np", "sk_ws", "sk_ws_bytes", "sk_count", "sk_tiles")
-_GEMM_PROBLEM_SCALES = 3                  # floats per problem: a_scale, w_scale, ln_eps
-
-
-def _problem_array(desc, scales):
-    k = len(_GEMM_PROBLEM_INTS)
-    n = len(desc) // k
-    arr = (_lib.GemmProblem * n)()
-    for i in range(n):
-        for j, name in enumerate(_GEMM_PROBLEM_INTS):
-            v = desc[i * k + j]
-            setattr(arr[i], name, (v or None) if name in _GEMM_PROBLEM_PTRS else v)
-        arr[i].a_scale, arr[i].w_scale, arr[i].ln_eps = scales[3 * i], scales[3 * i + 1], scales[3 * i + 2]
-    return arr, n
-
-
+# Descriptor-table operators (gemm_grouped and the fused attention sites' twins below): `tensors` lists every tensor the problems touch
+# (dispatch key, aliasing: they may be written), `desc` / `scales` hold per problem the int / float words of its structure (`_ProblemTable`).
 @_op("gemm_grouped", "(int dtype, Tensor(a!)[] tensors, int[] desc, float[] scales) -> ()")
 def _gemm_grouped(dtype, tensors, desc, scales):
-    arr, n = _problem_array(desc, scales)
+    arr, n = _GEMM_TABLE.array(desc, scales)
     check(_lib.load().emage_gemm_grouped(dtype, arr, n, _stream()), "gemm_grouped")
 
 
 def grouped_launch_count(entries):
     """Kernel launches `emage_gemm_grouped` makes of these recorded `emage::gemm` calls (measurement bookkeeping; launches nothing)."""
-    dtype, desc, scales = entries[0][2][0], [], []
-    for e in entries:
-        f = _gemm_fields(*e[2])
-        desc += [int(f[k] or 0) for k in _GEMM_PROBLEM_INTS]
-        scales += [float(f["a_scale"]), float(f["w_scale"]), float(f["ln_eps"])]
-    arr, n = _problem_array(desc, scales)
+    dtype, _tensors, desc, scales = _pack_entries(_GEMM_TABLE, _gemm_fields, entries)
+    arr, n = _GEMM_TABLE.array(desc, scales)
     rc = _lib.load().emage_gemm_grouped_launches(dtype, arr, n)
     if rc <= 0:
         check(rc or -1, "gemm_grouped_launches")
     return rc
-
-
-def _gemm_grouped_entries(entries):
-    """Recorded `emage::gemm` calls (Lockstep) of ONE dtype -> one `emage::gemm_grouped` call."""
-    dtype = entries[0][2][0]
-    tensors, desc, scales = [], [], []
-    for _name, _op_, args, _meta in entries:
-        assert args[0] == dtype
-        f = _gemm_fields(*args)
-        desc += [int(f[k] or 0) for k in _GEMM_PROBLEM_INTS]
-        scales += [float(f["a_scale"]), float(f["w_scale"]), float(f["ln_eps"])]
-        tensors += [t for t in list(args[1:9]) + list(args[24:30]) + list(args[31:33]) if torch.is_tensor(t)]
-    _gemm_grouped.op(dtype, tensors, desc, scales)
 
 
 def gemm_grouped(dtype, problems):
@@ -674,7 +692,10 @@ def qkv_attention_supported(dtype, t, d, h):
     return dtype & 0xff == H2 and t == _QKV_T and d == _QKV_D and h == _QKV_H
 
 
-def _qkv_fields(a, w, bias, ln_stats, ln_c, out, b, w_scale, a_scale, ln_eps):
+_QKV_TABLE = _ProblemTable(_lib.QkvAttentionProblem)
+
+
+def _qkv_fields(dtype, a, w, bias, ln_stats, ln_c, out, b, w_scale, a_scale, ln_eps):
     return dict(A=_ptr(a), W=_ptr(w), bias=_ptr(bias), ln_stats=_ptr(ln_stats), ln_c=_ptr(ln_c), out=_ptr(out), lda=_ld(a), ldo=_ld(out), B=b,
                 a_scale=a_scale, w_scale=w_scale, ln_eps=ln_eps)
 
@@ -682,35 +703,15 @@ def _qkv_fields(a, w, bias, ln_stats, ln_c, out, b, w_scale, a_scale, ln_eps):
 @_op("qkv_attention", "(int dtype, Tensor a, Tensor w, Tensor bias, Tensor? ln_stats, Tensor? ln_c, Tensor(a!) out, int b, float w_scale, "
                       "float a_scale, float ln_eps) -> ()")
 def _qkv_attention(dtype, a, w, bias, ln_stats, ln_c, out, b, w_scale, a_scale, ln_eps):
-    f = _qkv_fields(a, w, bias, ln_stats, ln_c, out, b, w_scale, a_scale, ln_eps)
+    f = _qkv_fields(dtype, a, w, bias, ln_stats, ln_c, out, b, w_scale, a_scale, ln_eps)
     check(_lib.load().emage_qkv_attention(dtype, f["A"], f["lda"], f["W"], f["bias"], f["ln_stats"], f["ln_c"], f["ln_eps"], f["out"], f["ldo"],
                                           b, _QKV_T, _QKV_D, _QKV_H, a_scale, w_scale, _stream()), "qkv_attention")
 
 
 @_op("qkv_attention_grouped", "(int dtype, Tensor(a!)[] tensors, int[] desc, float[] scales) -> ()")
 def _qkv_attention_grouped(dtype, tensors, desc, scales):
-    n = len(desc) // 9
-    arr = (_lib.QkvAttentionProblem * n)()
-    for i in range(n):
-        for j, name in enumerate(("A", "W", "bias", "ln_stats", "ln_c", "out", "lda", "ldo", "B")):
-            v = desc[9 * i + j]
-            setattr(arr[i], name, (v or None) if j < 6 else v)
-        arr[i].a_scale, arr[i].w_scale, arr[i].ln_eps = scales[3 * i], scales[3 * i + 1], scales[3 * i + 2]
+    arr, n = _QKV_TABLE.array(desc, scales)
     check(_lib.load().emage_qkv_attention_grouped(dtype, arr, n, _QKV_T, _QKV_D, _QKV_H, _stream()), "qkv_attention_grouped")
-
-
-def _qkv_attention_grouped_entries(entries):
-    """Recorded `emage::qkv_attention` calls (Lockstep) of ONE dtype -> grouped calls of up to _QKV_MAXG problems each."""
-    dtype = entries[0][2][0]
-    for i in range(0, len(entries), _QKV_MAXG):
-        tensors, desc, scales = [], [], []
-        for _name, _op_, args, _meta in entries[i:i + _QKV_MAXG]:
-            assert args[0] == dtype
-            f = _qkv_fields(*args[1:])
-            desc += [int(f[k] or 0) for k in ("A", "W", "bias", "ln_stats", "ln_c", "out", "lda", "ldo", "B")]
-            scales += [float(f["a_scale"]), float(f["w_scale"]), float(f["ln_eps"])]
-            tensors += [t for t in args[1:7] if torch.is_tensor(t)]
-        _qkv_attention_grouped.op(dtype, tensors, desc, scales)
 
 
 def qkv_attention(dtype, a, w, bias, out, b, *, w_scale, a_scale=None, ln=None, ln_eps=1e-5):
@@ -725,8 +726,7 @@ def qkv_attention(dtype, a, w, bias, out, b, *, w_scale, a_scale=None, ln=None, 
 
 
 # Fused cross-attention site (include/emage_hip.h: emage_q_attention): q projection + attention on the layer's memory K / V^T in one launch
-_QA_PTRS = ("A", "W", "bias", "ln_stats", "ln_c", "k", "vt", "out")
-_QA_INTS = ("lda", "ldk", "ldvt", "vt_rows", "ldo", "B")
+_QA_TABLE = _ProblemTable(_lib.QAttentionProblem)
 
 
 def q_attention_supported(dtype, t, tk, d, h):
@@ -734,49 +734,22 @@ def q_attention_supported(dtype, t, tk, d, h):
     return dtype & 0xff == H2 and t == _QKV_T and tk == _QKV_T and d == _QKV_D and h == _QKV_H
 
 
-def _qa_fields(a, w, bias, ln_stats, ln_c, k, vt, vt_rows, out, b, w_scale, a_scale, ln_eps):
+def _qa_fields(dtype, a, w, bias, ln_stats, ln_c, k, vt, vt_rows, out, b, w_scale, a_scale, ln_eps):
     return dict(A=_ptr(a), W=_ptr(w), bias=_ptr(bias), ln_stats=_ptr(ln_stats), ln_c=_ptr(ln_c), k=_ptr(k), vt=_ptr(vt), out=_ptr(out),
                 lda=_ld(a), ldk=_ld(k), ldvt=vt.shape[-1], vt_rows=vt_rows, ldo=_ld(out), B=b, a_scale=a_scale, w_scale=w_scale, ln_eps=ln_eps)
-
-
-def _qa_problems(desc, scales):
-    k = len(_QA_PTRS) + len(_QA_INTS)
-    n = len(desc) // k
-    arr = (_lib.QAttentionProblem * n)()
-    for i in range(n):
-        for j, name in enumerate(_QA_PTRS + _QA_INTS):
-            v = desc[k * i + j]
-            setattr(arr[i], name, (v or None) if j < len(_QA_PTRS) else v)
-        arr[i].a_scale, arr[i].w_scale, arr[i].ln_eps = scales[3 * i], scales[3 * i + 1], scales[3 * i + 2]
-    return arr, n
 
 
 @_op("q_attention", "(int dtype, Tensor a, Tensor w, Tensor bias, Tensor? ln_stats, Tensor? ln_c, Tensor k, Tensor vt, int vt_rows, Tensor(a!) out, "
                     "int b, float w_scale, float a_scale, float ln_eps) -> ()")
 def _q_attention(dtype, a, w, bias, ln_stats, ln_c, k, vt, vt_rows, out, b, w_scale, a_scale, ln_eps):
-    f = _qa_fields(a, w, bias, ln_stats, ln_c, k, vt, vt_rows, out, b, w_scale, a_scale, ln_eps)
-    arr, _ = _qa_problems([int(f[n] or 0) for n in _QA_PTRS + _QA_INTS], [a_scale, w_scale, ln_eps])
+    arr, _ = _QA_TABLE.array(*_QA_TABLE.pack(_qa_fields(dtype, a, w, bias, ln_stats, ln_c, k, vt, vt_rows, out, b, w_scale, a_scale, ln_eps)))
     check(_lib.load().emage_q_attention(dtype, arr, _QKV_T, _QKV_T, _QKV_D, _QKV_H, _stream()), "q_attention")
 
 
 @_op("q_attention_grouped", "(int dtype, Tensor(a!)[] tensors, int[] desc, float[] scales) -> ()")
 def _q_attention_grouped(dtype, tensors, desc, scales):
-    arr, n = _qa_problems(desc, scales)
+    arr, n = _QA_TABLE.array(desc, scales)
     check(_lib.load().emage_q_attention_grouped(dtype, arr, n, _QKV_T, _QKV_T, _QKV_D, _QKV_H, _stream()), "q_attention_grouped")
-
-
-def _q_attention_grouped_entries(entries):
-    """Recorded `emage::q_attention` calls (Lockstep) of ONE dtype -> grouped calls of up to _QKV_MAXG problems each."""
-    dtype = entries[0][2][0]
-    for i in range(0, len(entries), _QKV_MAXG):
-        tensors, desc, scales = [], [], []
-        for _name, _op_, args, _meta in entries[i:i + _QKV_MAXG]:
-            assert args[0] == dtype
-            f = _qa_fields(*args[1:])
-            desc += [int(f[n] or 0) for n in _QA_PTRS + _QA_INTS]
-            scales += [float(f["a_scale"]), float(f["w_scale"]), float(f["ln_eps"])]
-            tensors += [t for t in args[1:10] if torch.is_tensor(t)]
-        _q_attention_grouped.op(dtype, tensors, desc, scales)
 
 
 def q_attention(dtype, a, w, bias, k, vt, vt_rows, out, b, *, w_scale, a_scale=None, ln=None, ln_eps=1e-5):
@@ -791,9 +764,10 @@ def q_attention(dtype, a, w, bias, k, vt, vt_rows, out, b, *, w_scale, a_scale=N
                  float(act_scale(dtype) if a_scale is None else a_scale), float(ln_eps) if ln is not None else 0.0)
 
 
-_GROUPED = {"gemm": ("gemm_grouped", lambda entries: _gemm_grouped_entries(entries)),
-            "qkv_attention": ("qkv_attention_grouped", lambda entries: _qkv_attention_grouped_entries(entries)),
-            "q_attention": ("q_attention_grouped", lambda entries: _q_attention_grouped_entries(entries))}
+# recorded operator -> (the kind its grouped calls carry to the trace hook, recorded entries -> those calls)
+_GROUPED = {"gemm": _grouped("gemm_grouped", _GEMM_TABLE, _gemm_fields, _gemm_grouped),
+            "qkv_attention": _grouped("qkv_attention_grouped", _QKV_TABLE, _qkv_fields, _qkv_attention_grouped, _QKV_MAXG),
+            "q_attention": _grouped("q_attention_grouped", _QA_TABLE, _qa_fields, _q_attention_grouped, _QKV_MAXG)}
 
 
 @_op("wav_conv_in", "(int dtype, Tensor wav, Tensor w, Tensor? bias, Tensor? slope, Tensor(a!) out, int lout, int stride, int pad, "

@@ -123,6 +123,21 @@ int emage_vq_quantize_backward(const float* z, int ldz, const float* codebook, c
                                void* stream);
 
 /*
+ * The gradient of an embedding table read one row per CLIP — the backward of emage_gather_rows(table, ids broadcast over T) with respect to
+ * `table` (EmageAudioModel's two speaker tables, M:217-219 / 285-286; csrc/embedding.hip):
+ *   dw[s][c] = sum over clips b with clamp(ids[b]) == s, b ascending, of sum over t < T, t ascending, of g[(b * T + t) * ldg + c]
+ * g: (B * T, D) fp32 rows of pitch ldg >= D; ids: (B,) int64 contiguous, clamped exactly as emage_gather_rows clamps (below 0 -> 0, at or
+ * above S -> S - 1: forward and backward agree on the row a clip used, and nothing is indexed with an unclamped id); dw: (S, D) fp32 rows
+ * of pitch lddw >= D, WRITTEN (not accumulated): a row no clip names is 0.0f.  1 <= D <= 4096, 1 <= S <= 1024, B, T >= 1.
+ * Sums are float64, rounded to fp32 once, in the fixed order above; no floating-point atomics: bit-reproducible run to run and replay to
+ * replay.  workspace: emage_embedding_backward_workspace_bytes(B, D) = B * D * 8 bytes, 8-byte aligned, lent by the caller (the per-clip
+ * sums of the first of the two launches); the library never allocates.
+ */
+long emage_embedding_backward_workspace_bytes(int B, int D);
+int emage_embedding_backward(const float* g, long ldg, const int64_t* ids, int B, int T, int D, int S, float* dw, long lddw,
+                             void* workspace, long workspace_bytes, void* stream);
+
+/*
  * K1/K2/K3 — the one contraction kernel: Linear and Conv1d as (implicit) GEMM with a fused epilogue.
  * Replaces nn.Linear (M:232-263 call sites, MLP P:316-326), nn.Conv1d k=3 of VQEncoderV5/V6,
  * VQDecoderV5, ResBlock (P:178-261) and nn.Conv1d k=15 (+ folded eval BatchNorm1d + LeakyReLU +
@@ -750,6 +765,15 @@ int emage_gather_clips(const int* order, long n_order, const int* cursor, int n_
  * on the device (a captured step draws a fresh mask with a fresh ratio at every replay); a * iteration + b is evaluated in double and rounded to
  * fp32 once, as torch rounds the reference's Python float for the comparison.  The ratio is not clamped: above 1 every element is 1. */
 int emage_motion_mask(float* out, long n, double a, double b, unsigned long long seed, unsigned mask_id, const int* iteration, void* stream);
+
+/* The speaker-table row of every clip of the batch emage_gather_clips cuts for the same cursor value:
+ *   out[b] = speakers[clips[id * 3 + 2]],  id = order[(*cursor mod n_batches) * batch + b]
+ * speakers: n_recordings int64 rows (one per recording of the store, >= 0); out: `batch` int64 words.  An id outside [0, n_clips) writes 0 and
+ * ORs 1 into *status; a clip whose recording id lies outside [0, n_recordings), or a negative speaker row, writes 0 and ORs 2 (the status word
+ * and its meaning are emage_gather_clips').  Nothing outside the three tables is ever read. */
+int emage_gather_clip_speakers(const int* order, long n_order, const int* cursor, int n_batches, int batch,
+                               const long long* clips, long n_clips, const int64_t* speakers, long n_recordings,
+                               int64_t* out, int* status, void* stream);
 
 /* A batch of audio windows cut out of the flat array that holds every recording end to end, in ONE launch (csrc/recordings.hip; the audio
  * slices of EmageAudioModel.inference's windows, M:393-394 / M:441-442, for recordings of different lengths): row b of out (n rows of pitch

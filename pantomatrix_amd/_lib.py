@@ -65,6 +65,8 @@ SIGNATURES = {
     "emage_vq_quantize_train_workspace_bytes": [_i],
     "emage_vq_quantize_train": [_p, _i, _p, _p, _p, _i, _p, _i, _i, _i, _p, _p, _f, _p, _l, _i, _i, _i, _p],
     "emage_vq_quantize_backward": [_p, _i, _p, _p, _p, _i, _p, _f, _p, _i, _p, _i, _i, _i, _p],
+    "emage_embedding_backward_workspace_bytes": [_i, _i],
+    "emage_embedding_backward": [_p, _l, _p, _i, _i, _i, _i, _p, _l, _p, _l, _p],
     "emage_gemm": [_i, _p, _i, _p, _p, _p, _p, _i, _i, _i, _p, _i, _i, _p, _i, _p, _i, _i, _i,
                    _i, _i, _i, _i, _i, _i, _i, _i, _f, _f, _p],
     "emage_gemm_ws": [_i, _p, _i, _p, _p, _p, _p, _i, _i, _i, _p, _i, _i, _p, _i, _p, _i, _i, _i,
@@ -119,6 +121,7 @@ SIGNATURES = {
     "emage_dropout_mask": [_p, _l, _f, C.c_ulonglong, C.c_uint, _p, _i, _p],
     "emage_gather_clips": [_p, _l, _p, _i, _i, _p, _l, _i, _i, _p, _p, _p, _p, _l, _i, _p, _l, _p, _l, _p, _l, _l, _p, _l, _l, _p, _l, _l, _p, _l, _l, _p, _p],
     "emage_motion_mask": [_p, _l, _d, _d, C.c_ulonglong, C.c_uint, _p, _p],
+    "emage_gather_clip_speakers": [_p, _l, _p, _i, _i, _p, _l, _p, _l, _p, _p, _p],
     "emage_gather_windows": [_i, _p, _l, _p, _i, _i, _p, _l, _p, _p],
     "emage_copy_segments": [_p, _l, _p, _l, _p, _i, _l, _l, _p, _p],
     "emage_val_metrics_workspace_bytes": [_i, _i],
@@ -145,7 +148,7 @@ SIGNATURES = {
     "emage_rot6d_scatter": [_p, _i, _p, _p, _i, _i, _p],
 }
 RESTYPES = {"emage_bn_stats_workspace_bytes": _l, "emage_vq_quantize_train_workspace_bytes": _l, "emage_wav_conv_in_backward_workspace_bytes": _l, "emage_layernorm_backward_affine_workspace_bytes": _l,
-            "emage_grad_norm_workspace_bytes": _l, "emage_val_metrics_workspace_bytes": _l}
+            "emage_grad_norm_workspace_bytes": _l, "emage_val_metrics_workspace_bytes": _l, "emage_embedding_backward_workspace_bytes": _l}
 
 _lib = None
 _tools = None

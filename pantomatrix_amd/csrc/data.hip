@@ -4,6 +4,7 @@
 //                        clip table row {first frame, first sample, recording id}; T frames of poses (165) / expressions (100) / trans (3) /
 //                        foot contact (4) and T * samples_per_frame audio samples (s16 decoded x * 2^-15, or float32) are copied into the batch
 //                        tensors.  The cursor is read from device memory, so a captured graph walks the epoch by itself.
+//   emage_gather_clip_speakers   the speaker-table row of each of those clips (speakers[recording id]), for stores of more than one speaker
 //   emage_motion_mask    out[i] = (u_i < a * iteration + b) ? 1 : 0 with u_i from Philox4x32-10 (philox.h), iteration read from device memory
 // A block of emage_gather_clips serves a (clip, span) pair: span s of a clip is elements [s * SPAN, +SPAN) of the clip's five pieces laid end
 // to end (audio, poses, expressions, trans, contact).  Every access is ONE element at its natural alignment (2 bytes for s16, 4 otherwise): a clip
@@ -85,6 +86,31 @@ __global__ __launch_bounds__(THREADS) void motion_mask_kernel(float* __restrict_
     }
 }
 
+// out[b] = speakers[recording of the clip batch row b takes]: the same cursor arithmetic as gather_clips_kernel, one thread per batch row
+__global__ __launch_bounds__(THREADS) void gather_clip_speakers_kernel(const int* __restrict__ order, const int* __restrict__ cursor, int n_batches, int batch,
+                                                                       const long long* __restrict__ clips, long n_clips,
+                                                                       const int64_t* __restrict__ speakers, long n_recordings,
+                                                                       int64_t* __restrict__ out, int* __restrict__ status) {
+    const int b = blockIdx.x * THREADS + threadIdx.x;
+    if (b >= batch) return;
+    int pos = *cursor % n_batches;
+    if (pos < 0) pos += n_batches;
+    const long id = order[(long)pos * batch + b];
+    int64_t row = 0;
+    int bad = 0;
+    if (id < 0 || id >= n_clips) bad = 1;
+    else {
+        const long r = clips[id * 3 + 2];
+        if (r < 0 || r >= n_recordings) bad = 2;
+        else {
+            row = speakers[r];
+            if (row < 0) { row = 0; bad = 2; }
+        }
+    }
+    if (bad) atomicOr(status, bad);
+    out[b] = row;
+}
+
 bool fits(long clip_pitch, long row_pitch, int frames, int width) { return row_pitch >= width && clip_pitch >= (long)(frames - 1) * row_pitch + width; }
 
 }  // namespace
@@ -120,6 +146,17 @@ extern "C" int emage_gather_clips(const int* order, long n_order, const int* cur
     if (audio_fmt == EMAGE_PCM_S16) EMAGE_GATHER(EMAGE_PCM_S16);
     else EMAGE_GATHER(EMAGE_PCM_F32);
 #undef EMAGE_GATHER
+    return launch_status();
+}
+
+extern "C" int emage_gather_clip_speakers(const int* order, long n_order, const int* cursor, int n_batches, int batch,
+                                          const long long* clips, long n_clips, const int64_t* speakers, long n_recordings,
+                                          int64_t* out, int* status, void* stream) {
+    if (!order || !cursor || !clips || !speakers || !out || !status) return EMAGE_EINVAL;
+    if (batch <= 0 || batch > 65535 || n_batches <= 0 || n_clips <= 0 || n_recordings <= 0 || n_order < (long)n_batches * batch) return EMAGE_EINVAL;
+    if (((uintptr_t)clips & 7) || ((uintptr_t)speakers & 7) || ((uintptr_t)out & 7)) return EMAGE_EINVAL;
+    hipLaunchKernelGGL(gather_clip_speakers_kernel, dim3((unsigned)((batch + THREADS - 1) / THREADS)), dim3(THREADS), 0, (hipStream_t)stream, order, cursor,
+                       n_batches, batch, clips, n_clips, speakers, n_recordings, out, status);
     return launch_status();
 }
 

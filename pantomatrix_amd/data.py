@@ -8,6 +8,7 @@ recording is loaded ONCE and uploaded (a speaker's training split is a few hundr
 of a table, and `ClipLoader.fill()` reads neither host memory nor host state: as the `prologue` of `Trainer.capture` it becomes the head of the
 captured step, and a training loop's only host call per step is `trainer.replay()`.
 
+* ``speaker_number`` / ``SpeakerMap``   BEAT2's `<speaker number>_<name>_...` recording names -> dense rows of the model's speaker tables.
 * ``ClipStore``      the dataset (``from_index``: the reference's clip index JSON; ``from_arrays``: in-memory recordings);
                      ``gather_host`` is the numpy restatement of the reference's batch — the ORACLE of the GPU tests, not a fallback.
 * ``epoch_order``    `DistributedSampler(shuffle=True, drop_last=False)` restated.
@@ -43,6 +44,72 @@ def _is_s16_mono(path, audio_sr):
     return (tag, ch, sr, bits) == (1, 1, audio_sr, 16)
 
 
+def speaker_number(video_id):
+    """The BEAT2 speaker number of a recording name: the leading integer before the first `_` (`2_scott_0_103_103` -> 2).  ValueError for a
+    name without one."""
+    head = str(video_id).split("_", 1)[0]
+    if "_" not in str(video_id) or not head.isdigit():
+        raise ValueError(f"speaker_number: {video_id!r} does not start with '<speaker number>_'")
+    return int(head)
+
+
+def _index_items(meta_paths_or_items):
+    if isinstance(meta_paths_or_items, (str, dict)):
+        meta_paths_or_items = [meta_paths_or_items]
+    items = []
+    for m in meta_paths_or_items:
+        if isinstance(m, dict):
+            items.append(m)
+        else:
+            with open(m, "r") as f:
+                items.extend(json.load(f))
+    return items
+
+
+class SpeakerMap:
+    """{BEAT2 speaker number: row of the model's speaker tables}.  `from_index` numbers the speakers of ALL items of a clip index — every
+    split — densely in ascending speaker number, so a train store and a test set built from the same index agree; `len(map)` is the
+    `speaker_dims` to configure.  Calling the map with an index item returns the row of its `video_id`."""
+
+    def __init__(self, rows):
+        self.rows = {int(k): int(v) for k, v in dict(rows).items()}
+        if any(v < 0 for v in self.rows.values()):
+            raise ValueError(f"SpeakerMap: negative rows in {self.rows}")
+
+    @classmethod
+    def from_index(cls, meta_paths_or_items):
+        numbers = sorted({speaker_number(it["video_id"]) for it in _index_items(meta_paths_or_items)})
+        return cls({n: i for i, n in enumerate(numbers)})
+
+    def __len__(self):
+        return max(self.rows.values()) + 1 if self.rows else 0
+
+    def __getitem__(self, number):
+        if int(number) not in self.rows:
+            raise ValueError(f"SpeakerMap: speaker number {number} is not among {sorted(self.rows)}")
+        return self.rows[int(number)]
+
+    def __call__(self, item):
+        return self[speaker_number(item["video_id"] if isinstance(item, dict) else item)]
+
+    def __eq__(self, other):
+        return isinstance(other, SpeakerMap) and self.rows == other.rows
+
+    def __repr__(self):
+        return f"SpeakerMap({self.rows})"
+
+
+def _speaker_rows(speakers):
+    """`speakers` of `ClipStore.from_index` / `recordings.RecordingSet.from_index` as a callable item -> row (None: every item is row 0)."""
+    if speakers is None:
+        return lambda item: 0
+    if isinstance(speakers, dict):
+        speakers = SpeakerMap(speakers)
+    if not callable(speakers):
+        raise ValueError("speakers: None, a SpeakerMap, a dict {speaker number: row} or a callable item -> row")
+    return speakers
+
+
 class ClipStore:
     """Every recording of a split, end to end in flat device arrays, and the clip table over them.
 
@@ -50,7 +117,8 @@ class ClipStore:
     `.float()` does; the poses first go through the reference's `normalize(motion, 0, 1)` = x / (1 + 1e-7), once, at upload) and `audio`: a 1-D int16 array (mono 16-bit PCM at the model's rate, kept as it is and decoded x * 2^-15 by the kernel —
     exactly what `motion_io.load_audio` / `librosa.load` give for such a file) or float32 (numpy, or a tensor already on the device).  One format
     per store: int16 only when every recording has it.  clips: (recording index, start_idx, end_idx) triples or dicts with those keys
-    (`recording`, `start_idx`, `end_idx`, optionally `video_id`).  A clip of T frames carries T * samples_per_frame samples starting at
+    (`recording`, `start_idx`, `end_idx`, optionally `video_id`).  A recording dict may carry `speaker` (int >= 0, default 0): its row of the
+    model's speaker tables, kept as `speakers` ((n_recordings,) int64 on the device) and `speakers_host`.  A clip of T frames carries T * samples_per_frame samples starting at
     start_idx * samples_per_frame (beat2.py:111-114).  Refused with ValueError naming the clip: a clip that does not lie inside its recording
     in frames or in samples (the reference would collate a ragged batch), clips of unequal length, pose_fps != 30 (the reference down-samples
     `motion` only, beat2.py:106-108)."""
@@ -91,6 +159,9 @@ class ClipStore:
             a = rec["audio"]
             self.arrays["audio"][sample0[i]:sample0[i + 1]].copy_(a if a.dtype == self.arrays["audio"].dtype else a.to(torch.float32) * (1.0 / 32768.0))
         self.clips = torch.from_numpy(table).to(self.device)
+        self.speakers_host = np.asarray([r["speaker"] for r in self.recordings], dtype=np.int64)
+        self.speakers = torch.from_numpy(self.speakers_host).to(self.device)
+        self.has_speakers = bool(self.speakers_host.any())       # False: the reference's single speaker 0 — the loader launches what it always launched
 
     @staticmethod
     def _host_recording(i, r):
@@ -110,6 +181,10 @@ class ClipStore:
         if a.dim() != 1 or a.dtype not in (torch.int16, torch.float32):
             raise ValueError(f"ClipStore: recording {i}: audio must be a 1-D int16 or float32 array, not {tuple(a.shape)} {a.dtype}")
         out["audio"] = a
+        spk = r.get("speaker", 0)
+        if isinstance(spk, bool) or not isinstance(spk, (int, np.integer)) or spk < 0:
+            raise ValueError(f"ClipStore: recording {i}: speaker must be an int >= 0 (a row of the model's speaker tables), not {spk!r}")
+        out["speaker"] = int(spk)
         return out
 
     def _clip(self, i, c):
@@ -130,36 +205,33 @@ class ClipStore:
         return cls(recordings, clips, device, audio_sr=audio_sr, pose_fps=pose_fps)
 
     @classmethod
-    def from_index(cls, meta_paths_or_items, split, device, audio_sr=16000, pose_fps=30):
+    def from_index(cls, meta_paths_or_items, split, device, audio_sr=16000, pose_fps=30, speakers=None):
         """The reference's clip index (beat2.py:14-17): JSON lists of dicts `video_id, motion_path, audio_path, mode, start_idx, end_idx`, given
         as one path, a list of paths, or the items themselves; filtered by `mode == split`.  Each distinct recording is loaded once:
         `motion_io.beat_format_load`, the foot-contact `.npy` next to it (beat2.py:104), and the audio — the file's int16 samples as they are
         when EVERY file is mono 16-bit PCM at `audio_sr`, else `audio.load_audio(path, audio_sr, device)` (decode, down-mix and resampling
-        on the device)."""
+        on the device).  speakers: where a recording's speaker-table row comes from — None: every recording is speaker 0 (the reference's
+        behaviour); a `SpeakerMap`, a dict {speaker number: row} (looked up with `speaker_number(video_id)`) or a callable item -> row."""
         from . import audio as paudio
         if pose_fps != SMPLX_FPS:
             raise ValueError(f"ClipStore: pose_fps must be {SMPLX_FPS}, not {pose_fps} (the reference down-samples `motion` only: the batch would be ragged)")
-        if isinstance(meta_paths_or_items, str):
-            meta_paths_or_items = [meta_paths_or_items]
-        items = []
-        for m in meta_paths_or_items:
-            if isinstance(m, dict):
-                items.append(m)
-            else:
-                with open(m, "r") as f:
-                    items.extend(json.load(f))
-        items = [it for it in items if it.get("mode") == split]
+        items = [it for it in _index_items(meta_paths_or_items) if it.get("mode") == split]
         if not items:
             raise ValueError(f"ClipStore.from_index: no clip with mode == {split!r}")
-        keys = {}
+        keys, row_of, rows = {}, _speaker_rows(speakers), {}
         for it in items:
-            keys.setdefault((it["motion_path"], it["audio_path"]), len(keys))
+            k = (it["motion_path"], it["audio_path"])
+            keys.setdefault(k, len(keys))
+            row = int(row_of(it))
+            if rows.setdefault(k, row) != row:
+                raise ValueError(f"ClipStore.from_index: the clips of recording {k[0]} name different speakers ({rows[k]} and {row})")
         s16 = all(_is_s16_mono(a, audio_sr) for _m, a in keys)
         device = torch.device(device)
         recordings = []
         for motion_path, audio_path in keys:
             rec = dict(motion_io.beat_format_load(motion_path, mask=None))
             rec["foot_contact"] = np.load(foot_contact_path(motion_path))
+            rec["speaker"] = rows[(motion_path, audio_path)]
             if s16:
                 rec["audio"] = np.frombuffer(motion_io._wav_chunks(audio_path)[1], dtype="<i2").copy()
             elif device.type == "cuda":
@@ -232,12 +304,22 @@ class ClipLoader:
     buffer is padded to a whole batch with a valid clip id, and `valid` — one int32 on the device — holds the number of REAL clips of the
     batch `fill()` has just cut (set from the device cursor, so a captured graph carries it; `validation.Validator` hands it to
     `emage_val_metrics`).  hold_iteration: `fill()` advances the cursor but not the iteration — the reference draws the validation mask
-    with the TRAINING iteration, which stands still during a validation pass; the caller sets `loader.iteration`."""
+    with the TRAINING iteration, which stands still during a validation pass; the caller sets `loader.iteration`.
 
-    def __init__(self, store, batch, rank=0, world=1, seed=0, mask_seed=0, mask_ratio=(400 / 135 * 0.95, 0.05), drop_last=True, hold_iteration=False):
+    Speakers: `speaker_id` — (B, 1) int64 at a fixed address, next to `random_mask` — holds the speaker-table row of every clip of the batch
+    (`Trainer.capture(..., speaker_id=loader.speaker_id)`).  A store with any non-zero speaker makes `fill()` issue one more launch
+    (`emage_gather_clip_speakers`, the same cursor value as the clip gather); a store of speaker 0 only launches what it always launched and
+    `speaker_id` stays zero.  speaker_dims: the model's `speaker_dims`; the store's rows are checked against it here (ValueError), since a
+    captured step does not read ids back."""
+
+    def __init__(self, store, batch, rank=0, world=1, seed=0, mask_seed=0, mask_ratio=(400 / 135 * 0.95, 0.05), drop_last=True, hold_iteration=False,
+                 speaker_dims=None):
         self.store, self.batch_size, self.rank, self.world, self.seed, self.mask_seed = store, int(batch), int(rank), int(world), int(seed), int(mask_seed)
         self.mask_a, self.mask_b = float(mask_ratio[0]), float(mask_ratio[1])
         self.drop_last, self.hold_iteration = bool(drop_last), bool(hold_iteration)
+        if speaker_dims is not None and int(store.speakers_host.max()) >= int(speaker_dims):
+            raise ValueError(f"ClipLoader: the store holds speaker row {int(store.speakers_host.max())}; the model's speaker tables have "
+                             f"{int(speaker_dims)} rows (speaker_dims)")
         per_rank = -(-store.n_clips // self.world)
         if self.batch_size <= 0:
             self.n_batches = 0
@@ -252,6 +334,7 @@ class ClipLoader:
         self.batch = {k: torch.zeros(self.batch_size, t, w, dtype=torch.float32, device=dev) for k, w in ops.CLIP_WIDTHS.items()}
         self.batch["audio"] = torch.zeros(self.batch_size, t * store.spf, dtype=torch.float32, device=dev)
         self.random_mask = torch.zeros(self.batch_size, t, MASK_DIMS, dtype=torch.float32, device=dev)
+        self.speaker_id = torch.zeros(self.batch_size, 1, dtype=torch.int64, device=dev)
         self.order = torch.zeros(self.n_batches * self.batch_size, dtype=torch.int32, device=dev)
         self.counters = torch.zeros(2, dtype=torch.int32, device=dev)          # [cursor, iteration]
         self.cursor, self._iteration = self.counters[0:1], self.counters[1:2]
@@ -286,6 +369,8 @@ class ClipLoader:
     def fill(self):
         st = self.store
         ops.gather_clips(self.order, self.cursor, self.n_batches, st.clips, st.arrays, self.batch, self.status, frames=st.frames, samples_per_frame=st.spf)
+        if st.has_speakers:                                                    # the same cursor value as the gather above: it advances below
+            ops.gather_clip_speakers(self.order, self.cursor, self.n_batches, st.clips, st.speakers, self.speaker_id, self.status)
         ops.motion_mask(self.random_mask, self.mask_a, self.mask_b, self.mask_seed, MOTION_MASK_ID, self._iteration)
         if not self.drop_last:                                                 # real clips of this batch, from the device cursor alone (capturable)
             pos = torch.remainder(self.cursor, self.n_batches)
@@ -298,4 +383,5 @@ class ClipLoader:
         if bad:
             self.status.zero_()
             raise RuntimeError(f"ClipLoader: emage_gather_clips reported status {bad} (1: a clip id outside [0, {self.store.n_clips}) in the order buffer; "
-                               "2: a clip table row outside the flat arrays) — those batch rows were zero-filled")
+                               "2: a clip table row outside the flat arrays, or — emage_gather_clip_speakers — a recording id outside the speaker "
+                               "list) — those batch rows were zero-filled")

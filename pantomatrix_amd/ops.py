@@ -471,6 +471,31 @@ def vq_quantize_backward(z2d, codebook, idx, g_zq, g_loss, beta, dz=None, d_code
     return dz, d_codebook
 
 
+@_op("embedding_backward", "(Tensor g, Tensor ids, int t, Tensor(a!) dw, Tensor(b!) workspace) -> ()")
+def _embedding_backward(g, ids, t, dw, workspace):
+    b, (s, d) = ids.numel(), dw.shape
+    check(_lib.load().emage_embedding_backward(_ptr(g), _ld(g), _ptr(ids), b, t, d, s, _ptr(dw), _ld(dw), _ptr(workspace), workspace.numel() * 8,
+                                               _stream()), "embedding_backward")
+
+
+def embedding_backward(g, ids, rows, dw=None):
+    """The gradient of `gather_rows(table, ids broadcast over T)` w.r.t. the (rows, D) table (include/emage_hip.h: emage_embedding_backward):
+    g (B * T, D) fp32 view with unit inner stride, ids (B,) int64 (one per clip, clamped like the forward) -> dw (rows, D) fp32, WRITTEN:
+    float64 sums in a fixed order, rows no clip names exactly zero.  `dw`: an fp32 (rows, D) view to fill instead."""
+    _dev(g)
+    assert g.dtype == torch.float32 and g.dim() == 2 and ids.dtype == torch.int64 and ids.device == g.device
+    ids = ids.reshape(-1)
+    if ids.numel() > 1 and ids.stride(0) != 1:
+        ids = ids.contiguous()
+    b, d = ids.numel(), g.shape[1]
+    assert b >= 1 and g.shape[0] % b == 0, (g.shape, b)
+    dw = torch.empty(rows, d, dtype=torch.float32, device=g.device) if dw is None else dw
+    assert dw.dtype == torch.float32 and tuple(dw.shape) == (rows, d) and dw.device == g.device
+    ws = torch.empty(b * d, dtype=torch.float64, device=g.device)
+    _embedding_backward(g, ids, g.shape[0] // b, dw, ws)
+    return dw
+
+
 class SplitKScratch:
     """Scratch memory a caller lends to `gemm` launches of few rows so that they may split their K range inside the launch (include/emage_hip.h:
     emage_gemm_problem sk_ws / sk_count): one (workspace, zeroed tile counters) pair per (device, stream) — launches on one stream are ordered, so
@@ -1521,6 +1546,28 @@ def gather_clips(order, cursor, n_batches, clips, arrays, out, status, *, frames
         assert t.device == dev, "gather_clips: every tensor on the device of the batch"
     _gather_clips(order, cursor, int(n_batches), clips, int(frames), int(samples_per_frame), arrays["motion"], arrays["expressions"], arrays["trans"],
                   arrays["foot_contact"], arrays["audio"], out["audio"], out["motion"], out["expressions"], out["trans"], out["foot_contact"], status)
+    return out
+
+
+@_op("gather_clip_speakers", "(Tensor order, Tensor cursor, int n_batches, Tensor clips, Tensor speakers, Tensor(a!) out, Tensor(b!) status) -> ()")
+def _gather_clip_speakers(order, cursor, n_batches, clips, speakers, out, status):
+    check(_lib.load().emage_gather_clip_speakers(_ptr(order), order.numel(), _ptr(cursor), n_batches, out.numel(), _ptr(clips), clips.shape[0],
+                                                 _ptr(speakers), speakers.numel(), _ptr(out), _ptr(status), _stream()), "gather_clip_speakers")
+
+
+def gather_clip_speakers(order, cursor, n_batches, clips, speakers, out, status):
+    """out[b] = speakers[recording of clip order[(cursor mod n_batches) * B + b]]: the speaker-table rows of the batch `gather_clips` cuts for
+    the same cursor.  speakers (n_recordings,) int64, out (B, 1) or (B,) int64 contiguous; the rest as in `gather_clips`.  See
+    include/emage_hip.h: emage_gather_clip_speakers."""
+    _dev(out)
+    b = out.numel()
+    assert order.dtype == torch.int32 and order.dim() == 1 and (order.stride(0) == 1 or order.numel() <= 1) and order.numel() >= n_batches * b
+    assert cursor.dtype == torch.int32 and cursor.numel() == 1 and status.dtype == torch.int32 and status.numel() == 1
+    assert clips.dtype == torch.int64 and clips.dim() == 2 and clips.shape[1] == 3 and clips.is_contiguous()
+    assert speakers.dtype == torch.int64 and speakers.dim() == 1 and speakers.is_contiguous() and out.dtype == torch.int64 and out.is_contiguous()
+    for t in (order, cursor, status, clips, speakers):
+        assert t.device == out.device, "gather_clip_speakers: every tensor on the device of the batch"
+    _gather_clip_speakers(order, cursor, int(n_batches), clips, speakers, out, status)
     return out
 
 

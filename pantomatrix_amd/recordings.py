@@ -32,7 +32,7 @@ import numpy as np
 import torch
 
 from . import motion_io, ops
-from .data import SMPLX_FPS, _is_s16_mono, foot_contact_path
+from .data import SMPLX_FPS, _is_s16_mono, _speaker_rows, foot_contact_path
 
 MODEL_SR = 16000                                        # `inference()` hard-codes 16000 // 30 samples per frame (M:345, M:393)
 SPF = MODEL_SR // SMPLX_FPS
@@ -107,6 +107,21 @@ def identity_seed(n, frames=4):
     return seed
 
 
+def _host_ids(ids, n, who, speaker_dims=None):
+    """One speaker-table row per recording as a host (n,) int64 tensor: None -> zeros, an int -> that id for every recording."""
+    if ids is None:
+        ids = 0
+    if isinstance(ids, (int, np.integer)) and not isinstance(ids, bool):
+        ids = [int(ids)] * n
+    ids = torch.as_tensor(ids).detach().cpu().reshape(-1)
+    if ids.numel() != n or ids.dtype not in (torch.int64, torch.int32):
+        raise ValueError(f"{who}: speaker ids must be an int or {n} integers (one per recording), got {tuple(ids.shape)} {ids.dtype}")
+    ids = ids.to(torch.int64)
+    if n and (int(ids.min()) < 0 or (speaker_dims is not None and int(ids.max()) >= speaker_dims)):
+        raise ValueError(f"{who}: speaker ids {ids.tolist()} outside [0, {speaker_dims if speaker_dims is not None else 'speaker_dims'})")
+    return ids
+
+
 def _load_wave(path, audio_sr, device, s16):
     from . import audio as paudio
     if s16:
@@ -124,9 +139,13 @@ class RecordingSet:
     The poses are RAW: `inference_fn` does not apply the dataset's `normalize` that `data.ClipStore` applies.  The rest of the ground-truth
     motion is not kept: with `mask=None` the forward replaces every non-seed frame by the mask embedding (M:267-268) and the windows
     re-seed themselves from their own decode (M:384-391), so only the first four frames of `masked_motion` ever reach the network.
-    Motion hints and masks beyond the seed are out of scope."""
+    Motion hints and masks beyond the seed are out of scope.
 
-    def __init__(self, audios, device, seeds=None, ref_trans=None, items=None, audio_sr=MODEL_SR, seed_poses=None):
+    speaker_ids: one row of the model's speaker tables per recording (ints >= 0), kept on the host as `speaker_ids` ((R,) int64) —
+    `RecordingRunner.load` copies them into the runner's id buffers.  None (both reference loops): the set names no speakers and the
+    runner keeps the ids it was built with (0 by default)."""
+
+    def __init__(self, audios, device, seeds=None, ref_trans=None, items=None, audio_sr=MODEL_SR, seed_poses=None, speaker_ids=None):
         if audio_sr != MODEL_SR:
             raise ValueError(f"RecordingSet: the model's windows are cut at {MODEL_SR} Hz (M:345), not {audio_sr}")
         if not len(audios):
@@ -152,6 +171,7 @@ class RecordingSet:
         if tuple(seeds.shape) != (n, 4, SEED_DIMS) or tuple(ref_trans.shape) != (n, 3):
             raise ValueError(f"RecordingSet: seeds {tuple(seeds.shape)} / ref_trans {tuple(ref_trans.shape)}, expected ({n}, 4, {SEED_DIMS}) / ({n}, 3)")
         self.seeds, self.ref_trans = seeds.to(self.device).contiguous(), ref_trans.to(self.device).contiguous()
+        self.speaker_ids = None if speaker_ids is None else _host_ids(speaker_ids, n, "RecordingSet")
         self.items, self.seed_poses = items, seed_poses      # seed_poses: (R, 4, 165) host tensor, the raw axis-angle frames behind `seeds` (from_index)
 
     def __len__(self):
@@ -162,19 +182,21 @@ class RecordingSet:
         return [frames_of(n) for n in self.sample_counts]
 
     @classmethod
-    def from_audio(cls, audios, device, seeds=None, ref_trans=None, audio_sr=MODEL_SR):
+    def from_audio(cls, audios, device, seeds=None, ref_trans=None, audio_sr=MODEL_SR, speaker_ids=None):
         """1-D waveforms (int16 / float32 arrays or tensors) or WAV paths — the test_emage_audio.py case: no motion, identity seed, zero
         `ref_trans` unless given.  Paths load by the rule of `ClipStore.from_index`."""
         paths = [a for a in audios if isinstance(a, (str, os.PathLike))]
         s16 = all(_is_s16_mono(p, audio_sr) for p in paths)
         waves = [_load_wave(a, audio_sr, device, s16) if isinstance(a, (str, os.PathLike)) else a for a in audios]
-        return cls(waves, device, seeds=seeds, ref_trans=ref_trans, audio_sr=audio_sr)
+        return cls(waves, device, seeds=seeds, ref_trans=ref_trans, audio_sr=audio_sr, speaker_ids=speaker_ids)
 
     @classmethod
-    def from_index(cls, meta_paths, split="test", device="cuda", audio_sr=MODEL_SR):
+    def from_index(cls, meta_paths, split="test", device="cuda", audio_sr=MODEL_SR, speakers=None):
         """The reference's index JSONs (one path, a list of paths, or the items), filtered by `mode == split`, then the FIRST item per
         `video_id` (T:38-42).  Each recording is loaded once: `beat_format_load`, the foot-contact `.npy` next to it, and the audio — the
-        file's int16 samples when every file is mono 16-bit PCM at `audio_sr`, else `audio.load_audio` (on the device when there is one)."""
+        file's int16 samples when every file is mono 16-bit PCM at `audio_sr`, else `audio.load_audio` (on the device when there is one).
+        speakers: as in `data.ClipStore.from_index` — None (every recording is speaker 0), a `data.SpeakerMap`, a dict {speaker number: row}
+        or a callable item -> row."""
         if isinstance(meta_paths, (str, os.PathLike)):
             meta_paths = [meta_paths]
         items = []
@@ -202,7 +224,9 @@ class RecordingSet:
             ref.append(torch.from_numpy(trans[0]))
             raw.append(torch.from_numpy(poses[:4].copy()))
             waves.append(_load_wave(it["audio_path"], audio_sr, device, s16))
-        return cls(waves, device, seeds=torch.stack(seeds), ref_trans=torch.stack(ref), items=items, audio_sr=audio_sr, seed_poses=torch.stack(raw))
+        row_of = _speaker_rows(speakers)
+        return cls(waves, device, seeds=torch.stack(seeds), ref_trans=torch.stack(ref), items=items, audio_sr=audio_sr, seed_poses=torch.stack(raw),
+                   speaker_ids=None if speakers is None else [int(row_of(it)) for it in items])
 
 
 class _Unit:
@@ -211,7 +235,7 @@ class _Unit:
 
 
 class _Tail:
-    __slots__ = ("t", "n", "offsets", "seed_segs", "code_segs")
+    __slots__ = ("t", "n", "offsets", "seed_segs", "code_segs", "ranks", "ids")
 
 
 class _Decode:
@@ -232,7 +256,13 @@ class RecordingRunner:
     `infer_codes` / `ClipRunner._step`; non-finite outputs raise FloatingPointError.
 
     seeded: take the motion seeds and `ref_trans` of the `RecordingSet` handed to `__call__`; False: identity seed, zero `ref_trans`.
-    speaker_id: one id for every recording (both reference loops pass zeros).  audio_dtype: the flat array's dtype (torch.float32 / int16).
+    speaker_id: one id for every recording (an int; both reference loops pass zeros) or one id per recording, in input order.  Ids are INPUT
+    DATA like the audio: `load()` copies a set's ids into static buffers (`speaker_id`: (R, 1) in the sorted order; one small buffer per
+    tail group, whose members are arbitrary recordings), and a replay with other ids of the same lengths needs no new graph.  With EQUAL ids
+    (an int, or a list of equal ones) the pass issues what it always issued: one speaker / positional table of the widest unit, whose prefix
+    serves every forward.  A runner built with ids that DIFFER builds the table over every recording that runs a full window and hands each
+    unit its own rows, and each tail group its own ids; it serves any ids afterwards, a runner built with equal ids only equal ones
+    (`load()` refuses the rest: build the runner from the set, `for_set`).  audio_dtype: the flat array's dtype (torch.float32 / int16).
 
     use_graph: the whole pass is ONE captured graph for this tuple of lengths; a second call with other audio of the same lengths replays
     it — the periodic test pass of a training run.  New weights reach a replay as in `validation.Validator`: the packing of the model's
@@ -268,7 +298,9 @@ class RecordingRunner:
         # ---- static buffers ----
         lmax, w, mb = max(sched.lengths), self.window, min(self.max_batch, n_rec)
         self.audio = torch.zeros(int(self.sample_offsets[-1]), dtype=audio_dtype, device=dev)
-        self.speaker_id = torch.full((n_rec, 1), int(speaker_id), dtype=torch.long, device=dev)
+        ids = _host_ids(speaker_id, n_rec, "RecordingRunner", int(c.speaker_dims))
+        self.per_recording_ids = bool((ids != ids[0]).any())                           # fixed at construction: it decides the launch sequence
+        self.speaker_id = torch.zeros(n_rec, 1, dtype=torch.long, device=dev)          # sorted order, as every per-recording buffer below
         self.seed0 = identity_seed(n_rec).to(dev)                                      # sorted order, as every per-recording buffer below
         self.seeds = torch.zeros(n_rec, self.pre, SEED_DIMS, device=dev)
         self.ref_trans = torch.zeros(n_rec, 1, 3, device=dev)
@@ -289,6 +321,7 @@ class RecordingRunner:
         self.nonfinite, self.status = self.flags[0:1], self.flags[1:2]
         self.flags_host = torch.zeros(2, dtype=torch.int32, pin_memory=on_gpu)
         self._order_dev = torch.tensor(self.order, dtype=torch.long, device=dev)
+        self.set_speaker_ids(ids)
         self.precision = model.precision
         self.graph, self._pack_graph, self._packed_stamp, self._operands = None, None, None, None
         self._pass()                                                                    # packs weights, warms the allocator, validates shapes
@@ -333,6 +366,8 @@ class RecordingRunner:
                 g.offsets = torch.tensor([int(self.sample_offsets[r]) + s * SPF for r, s in grp], dtype=torch.int64, device=dev)
                 g.seed_segs = ops.segment_table([(self.rank[r], j, 1) for j, (r, _s) in enumerate(grp)], n_rec, g.n, dev)[0]
                 g.code_segs = ops.segment_table([(j * t, self.rank[r] * lmax + s, t) for j, (r, s) in enumerate(grp)], g.n * t, n_rec * lmax, dev)[0]
+                g.ranks = torch.tensor([self.rank[r] for r, _s in grp], dtype=torch.long, device=dev)
+                g.ids = torch.zeros(g.n, 1, dtype=torch.long, device=dev)               # the members' speaker ids (`set_speaker_ids`)
                 self.tails.append(g)
         self.decodes = []
         k = 0
@@ -365,12 +400,25 @@ class RecordingRunner:
             ops.count_nonfinite_multi(list(pending), self.nonfinite)
             del pending[:]
 
-    def _sliced_tables(self, tables, n):
+    def _sliced_tables(self, tables, lo, n):
+        """Rows of the speaker / positional tables for the recordings [lo, lo + n) the tables were built over."""
         from .modeling_emage_audio import _X
-        m = n * self.window
+        m0, m1 = lo * self.window, (lo + n) * self.window
         f0 = tables["face0"]
-        face0 = _X(f0.a[:m], f0.a[:m] if f0.r is f0.a else f0.r[:m], f0.h2r, f0.ln)
-        return dict(spk_body=tables["spk_body"][:m], face0=face0, pos_spk=tables["pos_spk"][:m], t=self.window)
+        face0 = _X(f0.a[m0:m1], f0.a[m0:m1] if f0.r is f0.a else f0.r[m0:m1], f0.h2r, f0.ln)
+        return dict(spk_body=tables["spk_body"][m0:m1], face0=face0, pos_spk=tables["pos_spk"][m0:m1], t=self.window)
+
+    def set_speaker_ids(self, ids):
+        """One speaker-table row per recording (input order; an int: the same for all) into the static id buffers — stream-ordered copies
+        into fixed addresses, so a captured pass reads them at its next replay.  Checked on the host against the model's `speaker_dims`."""
+        ids = _host_ids(ids, len(self.order), "RecordingRunner", int(self.model.config.speaker_dims))
+        if not self.per_recording_ids and bool((ids != ids[0]).any()):
+            raise ValueError("RecordingRunner: this runner was built with equal speaker ids (its pass shares one speaker table); build one with "
+                             "the ids that differ (RecordingRunner(..., speaker_id=[...]) / for_set) to run per-recording ids")
+        self.speaker_id.copy_(ids[self.order].reshape(-1, 1), non_blocking=True)
+        if self.per_recording_ids:
+            for g in self.tails:
+                g.ids.copy_(self.speaker_id.index_select(0, g.ranks))
 
     def _pass(self):
         """The three phases in order; the tool times them one by one."""
@@ -387,7 +435,9 @@ class RecordingRunner:
         try:
             tables = None
             if self.units:
-                nmax = max(u.hi - u.lo for u in self.units)
+                # equal ids: the table of the widest unit, a prefix of it for every unit; ids that differ: the table of every recording that
+                # runs a full window (a prefix of the sorted order), each unit reads the rows of its own recordings
+                nmax = max(u.hi for u in self.units) if self.per_recording_ids else max(u.hi - u.lo for u in self.units)
                 tables = model._speaker_tables(_Ctx(model._engine()), self.speaker_id[:nmax], nmax, w)
             for s0, cnt, units in self.chunks:
                 win = self.win_audio[:cnt]
@@ -404,8 +454,9 @@ class RecordingRunner:
                     if feats is not None:
                         ta = feats["ta"]
                         f = dict(memcat=feats["memcat"][k0 * w:(k0 + n) * w], ta=ta, bk=feats["bk"][k0 * ta:(k0 + n) * ta], bvt=feats["bvt"][k0:k0 + n])
-                    net = model.forward(win[k0:k0 + n], self.speaker_id[:n], self.tmpl_motion[:n], self.tmpl_mask[:n], use_audio=True,
-                                        _audio_feats=f, _tables=self._sliced_tables(tables, n), _lean=True, _seed=self.seeds[u.lo:u.hi])
+                    row0 = u.lo if self.per_recording_ids else 0
+                    net = model.forward(win[k0:k0 + n], self.speaker_id[row0:row0 + n], self.tmpl_motion[:n], self.tmpl_mask[:n], use_audio=True,
+                                        _audio_feats=f, _tables=self._sliced_tables(tables, row0, n), _lean=True, _seed=self.seeds[u.lo:u.hi])
                     codes = {p: v[u.lo:u.hi] for p, v in self.codes.items()}
                     model._window_codes(net, vq, codes, u.start, n, w)
                     self._flush_health(pending)
@@ -427,7 +478,7 @@ class RecordingRunner:
                 a = self.tail_audio[:n * t * SPF].view(n, t * SPF)
                 ops.gather_windows(self.audio, g.offsets, a, self.status)
                 ops.copy_segments(self.seeds, self.tail_seed, g.seed_segs, pre * SEED_DIMS * 4, 1, self.status)
-                net = model.forward(a, self.speaker_id[:n], self.tmpl_motion[:n, :t], self.tmpl_mask[:n, :t], use_audio=True, _lean=True,
+                net = model.forward(a, g.ids if self.per_recording_ids else self.speaker_id[:n], self.tmpl_motion[:n, :t], self.tmpl_mask[:n, :t], use_audio=True, _lean=True,
                                     _seed=self.tail_seed[:n])
                 model._window_codes(net, vq, {p: v[:n * t].view(n, t) for p, v in self.tail_codes.items()}, 0, n, t)
                 self._flush_health(pending)
@@ -463,13 +514,15 @@ class RecordingRunner:
 
     # ---- one pass end to end ------------------------------------------------------------------------------------------------------------
     def load(self, recording_set):
-        """Copy a set's audio (and, when `seeded`, its seeds and `ref_trans`) into the runner's input buffers (stream-ordered)."""
+        """Copy a set's audio and speaker ids (and, when `seeded`, its seeds and `ref_trans`) into the runner's input buffers (stream-ordered)."""
         rs = recording_set
         if list(rs.sample_counts) != self.sample_counts:
             raise ValueError("RecordingRunner: this runner was built for other recording lengths (one runner, one graph, per tuple of lengths)")
         if rs.audio.dtype != self.audio.dtype:
             raise ValueError(f"RecordingRunner: the set's audio is {rs.audio.dtype}, the runner was built with audio_dtype={self.audio.dtype}")
         self.audio.copy_(rs.audio, non_blocking=True)
+        if rs.speaker_ids is not None:
+            self.set_speaker_ids(rs.speaker_ids)
         if self.seeded:
             self.seed0.copy_(rs.seeds.to(self.device).index_select(0, self._order_dev))
             self.ref_trans.copy_(rs.ref_trans.to(self.device).index_select(0, self._order_dev).view(-1, 1, 3))
@@ -513,6 +566,8 @@ class RecordingRunner:
     @classmethod
     def for_set(cls, model, vq_model, recording_set, **kw):
         kw.setdefault("seeded", recording_set.seeded)
+        if recording_set.speaker_ids is not None:
+            kw.setdefault("speaker_id", recording_set.speaker_ids)
         return cls(model, vq_model, recording_set.sample_counts, audio_dtype=recording_set.audio.dtype, **kw)
 
 
@@ -526,13 +581,14 @@ def _save_outputs(results, names, audio_paths, save_path, pose_fps):
     return save_list
 
 
-def test_pass(model, vq, meta_paths, save_path, runner=None, pose_fps=None, device=None):
+def test_pass(model, vq, meta_paths, save_path, runner=None, pose_fps=None, device=None, speakers=None):
     """`inference_fn` (T:33-102): generate every test recording of the index JSONs and write `<video_id>_output.npz`
     -> (test_list, save_list) with the reference's keys.  runner: a `RecordingRunner` built for these recordings (the periodic test pass of
-    a training run keeps one and replays its graph) or any callable `recording_set -> [(poses, expressions, trans)]`; None builds one."""
+    a training run keeps one and replays its graph) or any callable `recording_set -> [(poses, expressions, trans)]`; None builds one.
+    speakers: where each recording's speaker-table row comes from (`RecordingSet.from_index`; None: speaker 0, as the reference)."""
     if device is None:
         device = getattr(runner, "device", None) or model.device
-    rs = RecordingSet.from_index(meta_paths, "test", device)
+    rs = RecordingSet.from_index(meta_paths, "test", device, speakers=speakers)
     if runner is None:
         runner = RecordingRunner.for_set(model, vq, rs)
     if pose_fps is None:
@@ -545,13 +601,15 @@ def test_pass(model, vq, meta_paths, save_path, runner=None, pose_fps=None, devi
 test_pass.__test__ = False                               # a library function, not a pytest case
 
 
-def generate_folder(model, vq, audio_folder, save_folder, runner=None, pose_fps=None):
+def generate_folder(model, vq, audio_folder, save_folder, runner=None, pose_fps=None, speaker_id=0):
     """test_emage_audio.py:96-105: every `*.wav` of `audio_folder` (sorted) -> `<stem>_output.npz` in `save_folder`, no seed and zero
-    `ref_trans` -> save_list."""
+    `ref_trans` -> save_list.  speaker_id: the speaker-table row of every file (an int) or a callable `path -> row`; 0 (the default, what
+    the reference passes) names no speakers: a `runner` handed in keeps the ids it was built with."""
     paths = sorted(glob.glob(os.path.join(audio_folder, "*.wav")))
     if not paths:
         raise ValueError(f"generate_folder: no *.wav in {audio_folder}")
-    rs = RecordingSet.from_audio(paths, getattr(runner, "device", None) or model.device)
+    ids = [int(speaker_id(p)) for p in paths] if callable(speaker_id) else (int(speaker_id) or None)
+    rs = RecordingSet.from_audio(paths, getattr(runner, "device", None) or model.device, speaker_ids=ids)
     if runner is None:
         runner = RecordingRunner.for_set(model, vq, rs)
     if pose_fps is None:

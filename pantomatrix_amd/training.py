@@ -1066,9 +1066,11 @@ class TrainForward:
                 g = self.tape.get(rows)
                 if g is None:
                     return
-                if cx.pk.w[key].shape[0] != 1:
-                    raise NotImplementedError("speaker-embedding gradient for more than one speaker row")
-                self._param_grad(name, slice(None), ops.col_sum(g))
+                n_rows = cx.pk.w[key].shape[0]
+                if n_rows == 1:                           # one speaker: every clip read row 0
+                    self._param_grad(name, slice(None), ops.col_sum(g))
+                else:                                     # per-clip ids: each table row takes the clips that read it (clamped as the gather clamps)
+                    self._param_grad(name, slice(None), ops.embedding_backward(g, sid[:, 0], n_rows))
             self.tape.node(bw)
         return rows
 
@@ -1335,14 +1337,34 @@ def losses(cfg, pred, index_gt, latent_gt, workspace=None):
     return rec, cls
 
 
-def step_losses(fwd: TrainForward, vq, batch, iteration, dropout_masks, random_mask):
+def speaker_ids(speaker_id, bs, device, speaker_dims=None):
+    """The (B, 1) int64 device tensor of per-clip speaker-table rows a step's forwards read.  None: zeros (the reference's scripts,
+    T:146).  A (B, 1) / (B,) int64 tensor already on the device is used IN PLACE (a captured step reads the caller's buffer at every
+    replay).  speaker_dims: a host-visible tensor is checked against it (ValueError for a row outside [0, speaker_dims)); device tensors
+    are not read back — the store that produced them validated its rows (`data.ClipLoader(speaker_dims=...)`), and the kernels clamp."""
+    device = torch.device(device)
+    if speaker_id is None:
+        return torch.zeros(bs, 1, dtype=torch.long, device=device)
+    if not torch.is_tensor(speaker_id):
+        speaker_id = torch.as_tensor(speaker_id)
+    if speaker_id.dtype != torch.int64 or speaker_id.numel() != bs or speaker_id.dim() not in (1, 2) or (speaker_id.dim() == 2 and speaker_id.shape[1] != 1):
+        raise ValueError(f"speaker_id must be a (B, 1) or (B,) int64 tensor with B = {bs}, not {tuple(speaker_id.shape)} {speaker_id.dtype}")
+    if speaker_dims is not None and not speaker_id.is_cuda and bs:
+        lo, hi = int(speaker_id.min()), int(speaker_id.max())
+        if lo < 0 or hi >= speaker_dims:
+            raise ValueError(f"speaker_id holds rows in [{lo}, {hi}]; the model's speaker tables have {speaker_dims} rows (speaker_dims)")
+    return speaker_id.to(device).reshape(bs, 1)
+
+
+def step_losses(fwd: TrainForward, vq, batch, iteration, dropout_masks, random_mask, speaker_id=None):
     """The seed / audio / mask forwards of one step (T:132-172) -> (dict of the six losses + "all" as Python floats, BatchNorm
     buffers after the three forwards).  dropout_masks: three mask lists (one per forward); random_mask: the (B, T, 337)
-    {0, 1} motion mask of forwards 2 and 3, `torch.rand(...) < mask_ratio` in the reference (T:163-165)."""
+    {0, 1} motion mask of forwards 2 and 3, `torch.rand(...) < mask_ratio` in the reference (T:163-165).  speaker_id: per-clip rows of
+    the speaker tables (`speaker_ids`); None = zeros."""
     cfg = fwd.model.config
     index, latent, masked_motion = targets(vq, batch["motion"], batch["expressions"], batch["trans"], batch["foot_contact"])
     bs, t = masked_motion.shape[:2]
-    speaker_id = torch.zeros(bs, 1, dtype=torch.long, device=masked_motion.device)
+    speaker_id = speaker_ids(speaker_id, bs, masked_motion.device, cfg.speaker_dims)
     seed_mask = torch.ones_like(masked_motion)
     seed_mask[:, :cfg.seed_frames] = 0
     stats, out = {}, {}
@@ -1499,14 +1521,14 @@ class Trainer:
     def _rng(self, forward_index, step):
         return (self.seed, step, 128 * forward_index)
 
-    def _device_step(self, batch, dropout_masks, random_mask, grad_hook=None, step_counter=None):
+    def _device_step(self, batch, dropout_masks, random_mask, grad_hook=None, step_counter=None, speaker_id=None):
         """Everything of a step that runs on the device; returns (dict of float64 device loss scalars, loss workspace).  With
         `step_counter` (one int32 on the device) Adam and the mask generator read the step count from it — what a captured graph needs."""
         fwd, model = self.fwd, self.fwd.model
         cfg = model.config
         index, latent, masked_motion = targets(self.vq, batch["motion"], batch["expressions"], batch["trans"], batch["foot_contact"])
         bs = masked_motion.shape[0]
-        speaker_id = torch.zeros(bs, 1, dtype=torch.long, device=masked_motion.device)
+        speaker_id = speaker_ids(speaker_id, bs, masked_motion.device, cfg.speaker_dims)
         seed_mask = torch.ones_like(masked_motion)
         seed_mask[:, :cfg.seed_frames] = 0
         fwd.param_grads = {}
@@ -1684,11 +1706,13 @@ class Trainer:
             res["grad_norm"] = grad_norm
         return res, recapture
 
-    def step(self, batch, iteration=0, dropout_masks=None, random_mask=None, grad_hook=None):
+    def step(self, batch, iteration=0, dropout_masks=None, random_mask=None, grad_hook=None, speaker_id=None):
         """One optimisation step -> dict of the six losses + "all".  `iteration` is accepted for signature compatibility with the
-        reference's train_val_fn (T:132) and unused: the caller computes the mask ratio and passes `random_mask` (T:163-165)."""
+        reference's train_val_fn (T:132) and unused: the caller computes the mask ratio and passes `random_mask` (T:163-165).
+        speaker_id: (B, 1) or (B,) int64 rows of the speaker tables, one per clip (None: zeros, the reference's scripts); a host tensor is
+        checked against `speaker_dims` (ValueError)."""
         with self._deferred_range_check():                # the operand-scale flags are read HERE with the losses, not at packing time
-            out, ws = self._device_step(batch, dropout_masks, random_mask, grad_hook)
+            out, ws = self._device_step(batch, dropout_masks, random_mask, grad_hook, speaker_id=speaker_id)
         try:
             res, _ = self._finish(out, ws)
         finally:
@@ -1706,7 +1730,7 @@ class Trainer:
         self.fwd._pcache = None
 
     # ---- the step as ONE hipGraph -------------------------------------------------------------------------------------------------
-    def capture(self, batch, random_mask, dropout_masks=None, prologue=None):
+    def capture(self, batch, random_mask, dropout_masks=None, prologue=None, speaker_id=None):
         """Capture the whole step — re-packing the MFMA operands from the current parameters, targets, three forwards with their
         backward passes, the dropout masks (drawn on the device from the in-graph step counter unless `dropout_masks` buffers are
         given), Adam, BatchNorm buffers — into one hipGraph over the GIVEN tensors: `batch` and `random_mask` (and `dropout_masks`)
@@ -1720,6 +1744,10 @@ class Trainer:
         only host call per step is `replay()`.  It also runs in front of the warm-up step's body; the device tensors it advances (its
         owner's `prologue_state()`: the loader's cursor and iteration) are put back with the optimiser state, so the first replay trains on
         the batch the counters pointed at when `capture` was called.  None (the default): the graph is what it was without the argument.
+
+        speaker_id: a (B, 1) or (B,) int64 DEVICE tensor of per-clip speaker-table rows; it becomes an input buffer of the graph like `batch`
+        (refill it in place between replays; `data.ClipLoader.speaker_id` is refilled by the loader's `fill`).  Replays do not read it back:
+        the rows are trusted as the store validated them (the kernels clamp).  None: zeros, the graph of a one-speaker step.
 
         Multi-process runs (round 5): the step is captured WITH its collectives — the four bucket all-reduces (started mid-backward on the
         backend's own stream: they become parallel branches of the graph), SyncBatchNorm's all-gathers and small all-reduces — when the
@@ -1738,6 +1766,9 @@ class Trainer:
             if not (torch.is_tensor(t) and t.is_cuda and t.device == dev and t.dtype == torch.float32):
                 raise RuntimeError(f"Trainer.capture: {name} must be a float32 tensor on {dev} (it becomes an input buffer of the graph; a host "
                                    "tensor would be copied once at capture time and never again)")
+        if speaker_id is not None and not (torch.is_tensor(speaker_id) and speaker_id.is_cuda and speaker_id.device == dev and speaker_id.dtype == torch.int64
+                                           and speaker_id.is_contiguous()):
+            raise RuntimeError(f"Trainer.capture: speaker_id must be a contiguous int64 tensor on {dev} (it becomes an input buffer of the graph)")
         for fm in (dropout_masks or ()):
             for mk in fm:
                 if not (mk.is_cuda and mk.dtype == torch.float32 and mk.is_contiguous()):
@@ -1753,7 +1784,7 @@ class Trainer:
         with self._deferred_range_check():
             if prologue is not None:
                 prologue()
-            self._device_step(batch, dropout_masks, random_mask)      # warm-up: lazy initialisation inside the library / the allocator, the exchange schedule
+            self._device_step(batch, dropout_masks, random_mask, speaker_id=speaker_id)      # warm-up: lazy initialisation inside the library / the allocator, the exchange schedule
         torch.cuda.synchronize(dev)
         for k, v in saved.items():
             params[k].copy_(v)
@@ -1769,7 +1800,7 @@ class Trainer:
             t.copy_(v)
         self.steps_done = done
         self._step_counter = torch.full((1,), done, dtype=torch.int32, device=dev)
-        self._graph_inputs = (batch, random_mask, dropout_masks, prologue)       # the graph reads these buffers at every replay: keep them alive
+        self._graph_inputs = (batch, random_mask, dropout_masks, prologue, speaker_id)       # the graph reads these buffers at every replay: keep them alive
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph, capture_error_mode="thread_local"):
             model.invalidate_packed()                                  # so that the packing of the current parameters is part of the graph
@@ -1777,7 +1808,7 @@ class Trainer:
             if prologue is not None:
                 prologue()
             self._step_counter.add_(1)
-            self._graph_out, self._graph_ws = self._device_step(batch, dropout_masks, random_mask, step_counter=self._step_counter)
+            self._graph_out, self._graph_ws = self._device_step(batch, dropout_masks, random_mask, step_counter=self._step_counter, speaker_id=speaker_id)
         self._graph, self._recapture_pending = graph, False
         self._graph_operands = model._packed                           # what the captured launches read (and re-write at every replay)
         model.invalidate_packed()                                      # ... and nobody else: they hold the weights BEFORE the replay's update

@@ -38,7 +38,7 @@ ENTRIES = tuple((f, p) for f in range(len(TAGS)) for p in ENTRY_PARTS)          
 
 
 class Validator:
-    """See the module docstring.  `step(batch, random_mask, n_valid=None)` runs one batch eagerly and returns its seven losses and twelve
+    """See the module docstring.  `step(batch, random_mask, n_valid=None, speaker_id=None)` runs one batch eagerly and returns its seven losses and twelve
     `acc_<tag>_<part>` as floats; `capture(...)` + `replay()` run it as one hipGraph; `reset()` / `result()` frame a pass over the loader.
     `decoded` / `target_rot6d` ((B, T, 330) static buffers) hold the last step's decoded prediction and its ground truth;
     `codes[tag][part]` ((B, T) int64) every forward's arg-max codes — the decode takes those of the first.  on_decoded(pred, gt): called at
@@ -78,7 +78,7 @@ class Validator:
         buf.copy_(like)
         return buf
 
-    def _device_step(self, batch, random_mask, n_valid):
+    def _device_step(self, batch, random_mask, n_valid, speaker_id=None):
         model, vq = self.model, self.vq
         cfg = model.config
         was_training = model.training
@@ -91,7 +91,7 @@ class Validator:
             m = bs * t
             self._frames = t
             n_valid = self._n_valid(n_valid, bs, dev)
-            speaker_id = torch.zeros(bs, 1, dtype=torch.long, device=dev)
+            speaker_id = training.speaker_ids(speaker_id, bs, dev, cfg.speaker_dims)      # None: zeros (T:146); the padding clips of a short batch carry the id of the clip they repeat
             seed_mask = torch.ones_like(masked_motion)
             seed_mask[:, :cfg.seed_frames] = 0
             audio = batch["audio"].to(device=dev, dtype=torch.float32)
@@ -156,12 +156,14 @@ class Validator:
         return bool(flag_value)
 
     # ---- eager ----------------------------------------------------------------------------------------------------------------------
-    def step(self, batch, random_mask, n_valid=None):
+    def step(self, batch, random_mask, n_valid=None, speaker_id=None):
         """One validation batch, eagerly -> dict of the seven losses (`rec_seed` ... `all`) and `acc_<tag>_<part>` of THIS batch; the meter
-        and the counters advance.  n_valid: the real clips of a padded batch — None (all), an int, or one int32 on the device."""
+        and the counters advance.  n_valid: the real clips of a padded batch — None (all), an int, or one int32 on the device.
+        speaker_id: (B, 1) or (B,) int64 rows of the speaker tables, one per clip, read by the three forwards and the shared speaker
+        tables (None: zeros); a host tensor is checked against `speaker_dims` (ValueError)."""
         packed_before = self.model._packed
         with self._deferred_range_check():
-            self._device_step(batch, random_mask, n_valid)
+            self._device_step(batch, random_mask, n_valid, speaker_id)
         r = ops.val_read(self.acc)                           # the step's ONE device-to-host copy
         pk = self.model._packed
         if pk is not None and pk is not packed_before and pk.range_flag is not None:      # a re-packing happened inside the step
@@ -178,14 +180,15 @@ class Validator:
         return out
 
     # ---- the step as ONE hipGraph ---------------------------------------------------------------------------------------------------
-    def capture(self, batch, random_mask, prologue=None, n_valid=None):
+    def capture(self, batch, random_mask, prologue=None, n_valid=None, speaker_id=None):
         """Capture the step — targets, the shared WavEncoder pass, the three forwards, `val_metrics`, the decode — into one hipGraph over the
         given tensors (`batch`, `random_mask`, `n_valid`: refill them in place between replays), and the packing of the eval operand set from
         the CURRENT parameters into a second one, as `Trainer.capture` packs inside its graph: a `replay()` after a training step validates
         the updated parameters, with the operand scales chosen when `capture` ran (checked on the device; `result()` reads the flag and
         schedules a re-capture), and nothing is read back.  prologue: a callable that refills the inputs on the device (`ClipLoader.fill`);
         it runs first inside the step's graph, and the device state it advances (`prologue_state()`) is put back behind the warm-up step,
-        as are the accumulators."""
+        as are the accumulators.  speaker_id: None (zeros) or a contiguous int64 DEVICE tensor, (B, 1) or (B,) — a graph input like `batch`
+        (`data.ClipLoader.speaker_id`, which the loader's `fill` rewrites)."""
         model = self.model
         dev = model.device
         for name, t in list(batch.items()) + [("random_mask", random_mask)]:
@@ -193,6 +196,9 @@ class Validator:
                 raise RuntimeError(f"Validator.capture: {name} must be a float32 tensor on {dev} (it becomes an input buffer of the graph)")
         if n_valid is not None and not torch.is_tensor(n_valid):
             raise RuntimeError("Validator.capture: n_valid must be None or an int32 device tensor (a graph input)")
+        if speaker_id is not None and not (torch.is_tensor(speaker_id) and speaker_id.is_cuda and speaker_id.device == dev and speaker_id.dtype == torch.int64
+                                           and speaker_id.is_contiguous()):
+            raise RuntimeError(f"Validator.capture: speaker_id must be a contiguous int64 tensor on {dev} (it becomes an input buffer of the graph)")
         owner = getattr(prologue, "__self__", None)
         advanced = list(owner.prologue_state()) if hasattr(owner, "prologue_state") else []
         rewind = [t.clone() for t in advanced] + [self.acc.clone()]
@@ -200,11 +206,11 @@ class Validator:
         with self._deferred_range_check():
             if prologue is not None:
                 prologue()
-            self._device_step(batch, random_mask, n_valid)      # warm-up: lazy initialisation, the static buffers, the operand scales
+            self._device_step(batch, random_mask, n_valid, speaker_id)      # warm-up: lazy initialisation, the static buffers, the operand scales
         torch.cuda.synchronize(dev)
         for t, v in zip(advanced + [self.acc], rewind):
             t.copy_(v)
-        self._graph_inputs = (batch, random_mask, prologue, n_valid)
+        self._graph_inputs = (batch, random_mask, prologue, n_valid, speaker_id)
         # two graphs over one memory pool: the PACKING of the eval operand set from the parameters as they stand when it is replayed, and
         # the step over that set.  Inside a validation pass the parameters stand still, so `replay()` runs the packing only when the
         # model's version stamp has moved (a training step since: `Trainer` advances the counters) — 3.5 ms of a 19 ms replay at 56 clips
@@ -215,7 +221,7 @@ class Validator:
         with torch.cuda.graph(graph, pool=pack_graph.pool(), capture_error_mode="thread_local"):
             if prologue is not None:
                 prologue()
-            self._device_step(batch, random_mask, n_valid)
+            self._device_step(batch, random_mask, n_valid, speaker_id)
         if model._packed is not packed:
             raise RuntimeError("Validator.capture: the step re-packed the operand set the packing graph had just built")
         self._pack_graph, self._graph, self._recapture_pending = pack_graph, graph, False

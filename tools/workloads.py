@@ -113,16 +113,42 @@ def lstm_oracle(kind, sd, audio, spk, motion=None):
         return fn(sd, LSTM_CFG, audio, spk, LSTM_CFG["seed_frames"], motion)
 
 
-def oracle_train_step_recorded(seed, iteration, bs=2, backward=False, batch=None):
+def _train_step_losses_with_ids(tro, speaker_id):
+    """oracle.emage_train_oracle.train_step_losses restated with the given per-clip speaker ids in place of its zeros: the same calls in
+    the same order (forward 1, `torch.rand` for the random mask, forward 2, forward 3), so the generator draws are the oracle's."""
+    def train_step_losses(sd, vq, cfg, batch, iteration, p=tro.DROPOUT_P):
+        index, latent, masked_motion = tro.targets(vq, batch["motion"], batch["expressions"], batch["trans"], batch["foot_contact"])
+        bs, t = masked_motion.shape[:2]
+        spk = torch.as_tensor(speaker_id, dtype=torch.long).reshape(bs, 1)
+        stats, loss = {}, {}
+        mask = torch.ones_like(masked_motion)
+        mask[:, :cfg.seed_frames] = 0
+        pred = tro.forward_train(sd, batch["audio"], spk, masked_motion, mask, True, p, stats)
+        loss["rec_seed"], loss["cls_seed"] = tro.rec_loss(pred, latent, cfg), tro.cls_loss(pred, index, cfg)
+        mask_ratio = (iteration / 135 * 400) * 0.95 + 0.05
+        mask = (torch.rand(bs, t, cfg.pose_dims + 3 + 4) < mask_ratio).float()
+        pred = tro.forward_train(sd, batch["audio"], spk, masked_motion, mask, True, p, stats)
+        loss["rec_audio"], loss["cls_audio"] = tro.rec_loss(pred, latent, cfg), tro.cls_loss(pred, index, cfg)
+        pred = tro.forward_train(sd, batch["audio"], spk, masked_motion, mask, False, p, stats)
+        loss["rec_mask"], loss["cls_mask"] = tro.rec_loss(pred, latent, cfg), tro.cls_loss(pred, index, cfg)
+        loss["all"] = sum(loss.values())
+        return loss, stats
+    return train_step_losses
+
+
+def oracle_train_step_recorded(seed, iteration, bs=2, backward=False, batch=None, speaker_id=None, speaker_dims=None):
     """One training step of the CPU oracle (oracle/emage_train_oracle.py: the reference's train_val_fn restated) with what a device run
     needs to REPEAT it recorded: every forward's dropout masks (the oracle issues the reference's generator draws; a recorded mask is
     exactly the tensor torch multiplies with — the oracle's result is unchanged bit for bit) and the random motion mask of forwards 2 / 3.
     backward=False: the three forwards and their losses (`train_step_losses`); True: the whole step (`train_step`: + gradients, Adam).
+    speaker_id: one speaker-table row per clip (the oracle's own step hard-codes zeros, so its lines are restated with the ids:
+    `_train_step_losses_with_ids`); None = the oracle's step itself.  speaker_dims: rows of the two speaker tables (None: the default
+    configuration's).
     -> dict(batch, losses {name: float}, masks [forward 1, 2, 3], random_mask, stats (BatchNorm buffers), grads, new_sd)."""
     import contextlib
     import torch.nn.functional as F
     from oracle import emage_train_oracle as tro
-    cfg = EmageAudioConfig(**cfg_dicts()[0])
+    cfg = EmageAudioConfig(**(cfg_dicts()[0] if speaker_dims is None else dict(cfg_dicts()[0], speaker_dims=int(speaker_dims))))
     _, vq = oracle_models()
     sd = synthetic.audio_model_state(cfg, 0)
     batch = train_batch(bs=bs) if batch is None else batch
@@ -156,6 +182,9 @@ def oracle_train_step_recorded(seed, iteration, bs=2, backward=False, batch=None
         return out
 
     tro.forward_train = spy
+    orig_losses = tro.train_step_losses
+    if speaker_id is not None:
+        tro.train_step_losses = _train_step_losses_with_ids(tro, speaker_id)
     grads, new_sd = None, None
     try:
         if backward:
@@ -166,6 +195,6 @@ def oracle_train_step_recorded(seed, iteration, bs=2, backward=False, batch=None
             with torch.no_grad():
                 losses, stats = tro.train_step_losses(sd, vq, cfg, batch, iteration)
     finally:
-        tro.forward_train = orig
+        tro.forward_train, tro.train_step_losses = orig, orig_losses
     return dict(batch=batch, losses={k: float(v) for k, v in losses.items()}, masks=per_forward, random_mask=motion_masks[1], stats=stats,
                 grads=grads, new_sd=new_sd, recorder=recorded)

@@ -261,26 +261,24 @@ class _EmageModule(torch.nn.Module):
             raise RuntimeError("the EMAGE model classes run only on an MI355X device: call .to('cuda') first "
                                "(there is no CPU fallback; the CPU oracle lives in oracle/ for tests only)")
 
-    def _engine(self, h2=None, train_only=False, lin_h2=False):
+    def _engine(self, h2=None, train_only=False):
         """The packed operand set of the current precision.  h2 (f16x3 only): pre-split EMAGE_H2 operands (default: `split_acts`);
         the training forward asks for h2=False (float32 activations, weights in the EMAGE_F16X3 packing) and train_only=True: `_pack` may
         then leave out operands only the eval-mode forward reads (a training step re-packs behind every update); such a set is never
-        handed to an eval-mode caller.  lin_h2 (f16x3, h2=False, train_only): the Linear / in_proj entries alone are EMAGE_H2 images —
-        the training forward hands those contractions pre-split operands (`training.TrainForward.h2_forward`) and keeps float32 storage."""
+        handed to an eval-mode caller."""
         dev = self.device
         self._require_device(dev)
         want_h2 = self._dt == F16X3 and self._supports_h2 and (self.split_acts if h2 is None else h2)
         dt = H2 if want_h2 else self._dt
-        lin_dt = H2 if (lin_h2 and train_only and dt == F16X3 and self._supports_h2) else dt
         stamp = self._version_stamp()
         if (self._packed is None or self._packed.device != dev or self._packed.dt != dt or self._packed.stamp != stamp
-                or self._packed.lin_dt != lin_dt or (self._packed.train_only and not train_only)):
+                or (self._packed.train_only and not train_only)):
             capturing = dev.type == "cuda" and torch.cuda.is_current_stream_capturing()
             for attempt in (0, 1):
                 # the scale cache is keyed by packing ORDER: a train-only set (fewer operands) keeps its own
-                ckey = (str(dev), dt, bool(train_only)) + ((lin_dt,) if lin_dt != dt else ())
+                ckey = (str(dev), dt, bool(train_only))
                 cache = self.__dict__.setdefault("_scale_caches", {}).setdefault(ckey, {})
-                pk = _Packed(self._flat_params(), dev, dt, cache, lin_dt=lin_dt)
+                pk = _Packed(self._flat_params(), dev, dt, cache)
                 pk.stamp, pk.train_only = stamp, bool(train_only)
                 self._pack(pk)
                 pk.finish_range_check()
@@ -307,10 +305,9 @@ class _EmageModule(torch.nn.Module):
 # packed weights: MFMA-operand dtype, K-contiguous rows, taps flattened, BatchNorm folded
 # ======================================================================================
 class _Packed:
-    def __init__(self, params, device, dt, scale_cache=None, lin_dt=None):
+    def __init__(self, params, device, dt, scale_cache=None):
         self.p, self.device, self.dt = params, device, dt
         self.act_shift = 0           # the owning module's `activation_shift` at the time the set was handed out (`_engine`): read by `_Ctx`
-        self.lin_dt = dt if lin_dt is None else lin_dt       # operand packing of the Linear / in_proj entries (`_engine(lin_h2=True)`: EMAGE_H2 beside F16X3)
         # split-fp16 operand scales by packing order: chosen (one read-back of max|w|) at the FIRST packing of a model's weights and kept for
         # every re-packing (after an optimiser step: a pure sequence of launches, capturable); cleared when a state dict is loaded
         self.scale_cache = {} if scale_cache is None else scale_cache
@@ -364,7 +361,7 @@ class _Packed:
         kp = _rup(k)
         if kp != k:
             w2d = torch.nn.functional.pad(w2d, (0, kp - k))
-        w, ws = self._operand(w2d, self.lin_dt)
+        w, ws = self._operand(w2d)
         return w, kp, ws
 
     def _fold_norm(self, wcat, bcat, norm):
@@ -413,7 +410,7 @@ class _Packed:
             wcat, bcat, c = self._fold_norm(wcat, bcat, fold)
             extra = dict(c=c, norm=fold)
         w, kp, wsc = self._pack_mat(wcat)
-        self.w[key] = dict(w=w, b=bcat, n=wcat.shape[0], cp=kp, taps=1, k_real=k_real, ws=wsc, dt=self.lin_dt, **extra)
+        self.w[key] = dict(w=w, b=bcat, n=wcat.shape[0], cp=kp, taps=1, k_real=k_real, ws=wsc, dt=self.dt, **extra)
         if fold is None:
             self.origin[key] = [(nm + ".weight", nm + ".bias", rows[i] if rows is not None else slice(0, self.p[nm + ".weight"].shape[0]))
                                 for i, nm in enumerate(names)]
@@ -440,7 +437,7 @@ class _Packed:
         else:
             self.origin[key] = origin
         w, kp, wsc = self._pack_mat(wcat)
-        self.w[key] = dict(w=w, b=bcat, n=wcat.shape[0], cp=kp, taps=1, k_real=k_real, ws=wsc, dt=self.lin_dt, **extra)
+        self.w[key] = dict(w=w, b=bcat, n=wcat.shape[0], cp=kp, taps=1, k_real=k_real, ws=wsc, dt=self.dt, **extra)
 
     def folded(self, cname, bn=None):
         """Raw Conv1d (weight (Cout,Cin,k), bias) with an eval-mode BatchNorm1d folded in:

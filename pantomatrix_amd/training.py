@@ -23,19 +23,16 @@ No CPU fallback: every arithmetic step is a launch into libemage_hip.so.  Backwa
 """
 from __future__ import annotations
 
+import contextlib
+
 import torch
 
 from . import ops, spec
 from ._lib import F32, H2
 from .modeling_emage_audio import OUT_KEYS, _Ctx, _WAV_TAPS, _rup
+from .tape import DROPOUT_P, TapeForward, _Masks, _Tape, _Token, _capturing, _check_max_norm, _param_grad_norms, clip_and_adam      # noqa: F401 (re-exports)
 
 BN_MOMENTUM = 0.1          # nn.BatchNorm1d default
-DROPOUT_P = 0.1            # PeriodicPositionalEncoding (P:329) and nn.Transformer*Layer defaults
-
-
-def _capturing(device=None):
-    """True while the current stream of `device` is recording a hipGraph (no host read-back, no blocking collective result)."""
-    return bool(torch.cuda.is_available() and torch.cuda.is_current_stream_capturing())
 
 
 def dropout_mask_count():
@@ -44,169 +41,6 @@ def dropout_mask_count():
 
 
 _ZERO_LONG = torch.zeros((), dtype=torch.long)           # stands for a missing `num_batches_tracked` buffer
-
-
-class _Masks:
-    """The dropout masks of one forward: a given list (the parity tests: the reference's recorded draws), or — masks None — drawn on
-    the device as they are needed (`ops.dropout_mask`: Philox keyed by rng = (seed, step, first mask id); step may be a device scalar)."""
-
-    def __init__(self, masks, dev, rng=None, lazy=True):
-        self.masks, self.i, self.dev, self.rng, self.lazy = (None if masks is None else list(masks)), 0, dev, rng, lazy
-        if masks is None and rng is None:
-            raise RuntimeError("train-mode forward: pass dropout_masks or an rng (seed, step, first mask id)")
-
-    def consumed_all(self):
-        return self.masks is None or self.i == len(self.masks)
-
-    def take(self, shape, lazy=False):
-        """The next mask of the forward, of logical shape `shape`.  lazy (device-drawn masks only): the caller consumes it through
-        `ops.mul_add` alone, which draws the mask inside its kernel — return the key (`ops.PhiloxMask`) instead of a tensor."""
-        if self.masks is None:
-            seed, step, base = self.rng
-            if lazy and self.lazy and shape[-1] % 4 == 0:
-                self.i += 1
-                return ops.PhiloxMask(shape, DROPOUT_P, seed, base + self.i - 1, step, self.dev)
-            m = torch.empty(tuple(shape), dtype=torch.float32, device=self.dev)
-            ops.dropout_mask(m, DROPOUT_P, seed, base + self.i, step)
-            self.i += 1
-            return m
-        if self.i >= len(self.masks):
-            raise RuntimeError(f"dropout_masks: {len(self.masks)} masks given, the forward needs {dropout_mask_count()}")
-        m = self.masks[self.i]
-        self.i += 1
-        if tuple(m.shape) != tuple(shape):
-            raise RuntimeError(f"dropout mask {self.i - 1}: shape {tuple(m.shape)}, the reference draws {tuple(shape)} here")
-        return m.to(device=self.dev, dtype=torch.float32).contiguous()
-
-
-class _Token:
-    """Stands for a logical (rows, cols) tensor that exists only in pieces (a projection whose V columns are stored transposed)."""
-
-    def __init__(self, shape):
-        self.shape = shape
-
-
-def _accumulate(dst, g, out=None):
-    """out (default dst) = dst + g on fp32 (rows, cols) views: emage_add where its 16-byte granularity allows, torch otherwise
-    (the 337-column motion rows)."""
-    out = dst if out is None else out
-    if g.shape[1] % 4 == 0 and all(t.stride(0) % 4 == 0 and t.data_ptr() % 8 == 0 for t in (dst, g, out)):
-        ops.add(F32, dst, g, out=out)
-    else:
-        torch.add(dst, g, out=out)
-
-
-class _Tape:
-    """Reverse-mode bookkeeping of one forward: backward closures in launch order, gradient buffers keyed by the forward tensor
-    (or token) they belong to, column-slice views routed into their parent's buffer.  Gradients are fp32 (rows, cols).
-    Memory: a gradient buffer lives from its first contribution until the node that PRODUCED its tensor has run (every consumer of a
-    tensor runs before its producer in reverse order, and a tensor has one producer); a closure — and with it the activations it saved —
-    is dropped as soon as it has run.  So the live set shrinks as the backward walks instead of doubling until its end."""
-
-    def __init__(self, dev):
-        self.dev, self.nodes, self.g, self.views, self.keep, self.kids, self.pos = dev, [], {}, {}, {}, {}, -1
-        self._fetched = None            # ids whose gradient the running node has taken (dropped behind the node)
-        self.pinned = set()
-
-    def node(self, fn):
-        self.nodes.append(fn)
-
-    def view(self, parent, view, c0, written=False):
-        """`view` = parent[:, c0:c0 + width] takes part in the forward under its own identity.  written: the view is the OUTPUT of a node
-        (the parent is assembled in pieces, so it has several producers): its gradient buffer then stays until the tape is dropped."""
-        self.views[id(view)] = (parent, c0, view.shape[1])
-        self.keep[id(view)] = view                       # ids are keys: the objects must stay alive while their entries exist
-        self.kids.setdefault(id(parent), []).append(id(view))
-        if written:
-            self.pinned.add(id(parent))
-
-    def buffer(self, t, zero=True):
-        """The zero-initialised, tape-owned gradient buffer of `t` (created on first use).  zero=False: the caller (and its siblings)
-        OVERWRITE every column block before anyone reads the buffer — the attention backward's dQ / dK / dV blocks of a projection."""
-        e = self.g.get(id(t))
-        if e is None:
-            alloc = torch.zeros if zero else torch.empty
-            e = [alloc(tuple(t.shape), dtype=torch.float32, device=self.dev), True]
-            self.g[id(t)] = e
-            self.keep[id(t)] = t
-        elif not e[1]:
-            e[0], e[1] = e[0].clone(), True
-        return e[0]
-
-    def add(self, t, g, cols=None):
-        """grad(t)[:, :cols] += g.  The first gradient of a tensor is kept by reference (never modified in place afterwards)."""
-        if id(t) in self.views:
-            parent, c0, n = self.views[id(t)]
-            dst = self.buffer(parent)[:, c0:c0 + (n if cols is None else cols)]
-            _accumulate(dst, g)
-            return
-        e = self.g.get(id(t))
-        if cols is not None and cols != t.shape[1]:
-            dst = self.buffer(t)[:, :cols]
-            _accumulate(dst, g)
-        elif e is None:
-            self.g[id(t)] = [g, False]
-            self.keep[id(t)] = t
-        elif e[1]:
-            _accumulate(e[0], g)
-        else:
-            s = torch.empty(tuple(e[0].shape), dtype=torch.float32, device=self.dev)
-            _accumulate(e[0], g, out=s)
-            e[0], e[1] = s, True
-
-    def add_through(self, t, make, cols=None):
-        """grad(t)[:, :cols] += c for a contribution that a contraction produces: `make(prev)` launches it and returns `c` (prev None) or
-        `prev + c` as a NEW tensor (prev: the gradient so far, handed to the launch as its float32 residual — the add rides in the
-        epilogue instead of being a launch of its own; the same bits: fl(prev + fl(c)))."""
-        e = None if id(t) in self.views or (cols is not None and cols != t.shape[1]) else self.g.get(id(t))
-        if e is None:
-            self.add(t, make(None), cols)
-        else:
-            e[0], e[1] = make(e[0]), True
-
-    def get(self, t):
-        if id(t) in self.views:                          # a column block of its parent's gradient
-            parent, c0, n = self.views[id(t)]
-            e = self.g.get(id(parent))
-            return None if e is None else e[0][:, c0:c0 + n]
-        e = self.g.get(id(t))
-        if e is None:
-            return None
-        if self._fetched is not None:
-            self._fetched.append(id(t))
-        return e[0]
-
-    def _drop(self, i):
-        if i in self.pinned:
-            return
-        self.g.pop(i, None)
-        self.keep.pop(i, None)
-        for v in self.kids.pop(i, ()):
-            self.views.pop(v, None)
-            self.keep.pop(v, None)
-
-    def run(self, progress=None, base=0):
-        """Run the recorded closures in reverse; `pos` counts the executed nodes (what `TrainForward._param_grad` stamps a parameter's
-        last contribution with); progress(pos) is called behind each node (the overlapped gradient exchange hangs on it).  base: position
-        of the first node (a tape run as the continuation of another one: the step-shared WavEncoder pass behind the third backward)."""
-        self.pos = base - 1
-        if progress is not None and base == 0:
-            progress(-1)
-        k = 0
-        while self.nodes:
-            fn = self.nodes.pop()
-            self.pos = base + k
-            self._fetched = []
-            try:
-                fn()
-            finally:
-                fetched, self._fetched = self._fetched, None
-            del fn
-            for i in fetched:
-                self._drop(i)
-            if progress is not None:
-                progress(base + k)
-            k += 1
 
 
 class StepShare:
@@ -221,60 +55,21 @@ class StepShare:
         self.feats, self.tape, self.bn_log = None, None, []
 
 
-class TrainForward:
+class TrainForward(TapeForward):
     """Callable train-mode forward of an `EmageAudioModel` (f16x3 or fp32 precision), with `backward()` for the part of the
-    network behind the convolutional front ends."""
+    network behind the convolutional front ends.  The tape-aware layer wrappers, the parameter-gradient accumulation and the backward
+    operand scales are `tape.TapeForward`'s."""
 
     def __init__(self, model, sync_bn=False, group=None):
         """sync_bn: BatchNorm statistics (forward) and their gradient sums (backward) are taken over all ranks of `group`, the
         behaviour of nn.SyncBatchNorm the reference converts its model to (train_emage_audio.py:248); torch.distributed must be
         initialised."""
-        if model.precision == "bf16":
-            raise ValueError("the training forward runs in the fp32-storage precisions (f16x3 / fp32)")
-        self.model = model
+        super().__init__(model)
         self.sync_bn, self.group, self._bn_count = sync_bn, group, {}
         self._clips = {}                # local clip count -> clips of all ranks (sync_bn: exchanged at the first BatchNorm of EVERY eager forward, see `_clip_total`)
         self._bn_log = None             # list collecting (name, mean, var, rows) of a WavEncoder pass that later forwards of the step replay
-        # f16x3 precision: the backward contractions run as split-fp16 MFMA on pre-split (EMAGE_H2) operands — gradients pre-scaled by
-        # a power of two so that their fp16 planes stay normal (the loss-scaling of mixed-precision training, undone exactly in the
-        # GEMM epilogue); fp32 precision keeps the exact-fp32 MFMA contractions
-        self.h2_backward = model.precision == "f16x3"
-        # h2_forward (round 6, A/B switch, OFF: measured 89.7-90.1 vs 87.5-89.3 ms per step): the forward's Linear contractions on EMAGE_H2 operands too —
-        # weights packed as H2 images (`_engine(lin_h2=True)`), a LayerNorm writes the image of its result beside the float32 tensor, every other
-        # operand is split by one `h2_cast` launch in front of its contraction; the float32 tensors the backward reads are unchanged.  The H2
-        # contractions save 2.5 ms per step against the in-kernel split of EMAGE_F16X3, the 237 cast launches cost 3.5 (profiles/r06_train_h2_forward_ab.txt)
-        self.h2_forward = False
-        self._h2img = {}                # id(float32 operand) -> (operand, its EMAGE_H2 image), filled by the producers that write one
-        self.grad_scale = 1024.0
-        self.conv_backward_rows = 1 << 17                 # output rows per piece of a long convolution's backward (_conv_backward_h2)
-        self._w_scale, self._wt_cache = {}, {}
-        self.fuse_grad_adds = True      # a Linear's input gradient is added to what its input has collected so far by the contraction's own epilogue (A/B switch; same bits)
-        self.direct_conv_dx = True      # stride-1 convolutions: the input gradient as ONE implicit-GEMM convolution of dY (A/B switch; False: dcol = dY W + col2im)
-        self.accumulate_dw = True       # Linear weight gradients are added into the gradient rows by their contraction (A/B switch; False: a temporary + a queued add)
-        self.defer_finalize = True      # bias / affine-gradient reductions end in batched finalize launches (`ops.FinalizeQueue`; A/B switch: False = one each)
-        self._fin = ops.FinalizeQueue()
-        self.splitk_workspace_bytes = 32 << 20            # scratch of the two-pass split-K weight-gradient contractions (emage_gemm_ws: K-slices as planes, added
-        self._splitk_buf = None                           # in slice order — bit-reproducible gradients); 0: the fp32-atomic form of emage_gemm
         self.lazy_masks = True          # device-drawn (T, B, d) dropout masks live as Philox keys: drawn inside `mul_add`, forward and backward (-0.9 GB per forward)
-        self._wt_keep = False           # True inside `Trainer._device_step`: the transposed weight images (`_weight_t_h2`) serve all three forwards
-        self.range_flag = None          # int32 device counter: transposed-weight operands (backward dX) whose cached scale no longer fits
-        self._range_pending, self._range_seen = [], set()
-        self.tape = None
-        self._pgrads = {}               # name -> gradient accumulator (`param_grads` is the flushed view of it)
-        self._pg_dst, self._pg_src, self._pg_spans, self._pg_bytes = [], [], {}, 0       # queued parameter-gradient contributions (_param_grad)
-        self.grad_views = None          # name -> preallocated fp32 gradient tensor (views of the exchange buckets, training.Trainer)
-        self.touch = None               # dict filled with name -> tape position of the parameter's last contribution of a backward
         self._shared, self.last_run_nodes = None, 0
-        self._pcache = None
-
-    def _splitk_ws(self, dev=None):
-        """The workspace of the weight-gradient contractions (one buffer per trainer: the launches of a step run in stream order)."""
-        if not self.splitk_workspace_bytes:
-            return None
-        dev = self.model.device if dev is None else dev
-        if self._splitk_buf is None or self._splitk_buf.device != dev or self._splitk_buf.numel() * 4 != self.splitk_workspace_bytes:
-            self._splitk_buf = torch.empty(self.splitk_workspace_bytes // 4, dtype=torch.float32, device=dev)
-        return self._splitk_buf
 
     # ---- packing of what the inference pack does not hold: un-folded WavEncoder convolutions ----------------------------
     def _train_pack(self, pk):
@@ -311,6 +106,19 @@ class TrainForward:
         forgotten, so the step's first BatchNorm exchanges it afresh (`_clip_total`)."""
         if self.sync_bn and not _capturing(self.model.device):
             self._clips.clear()
+
+    @contextlib.contextmanager
+    def step(self):
+        """One optimisation step: `begin_step`, then the step's forwards and backwards inside.  The parameters move at the END of the step,
+        so ONE set of transposed weight images, built afresh, serves all of them and is dropped behind the step; a step that dies takes what
+        it had queued for the gradient accumulators with it (its float64 partials would otherwise land in the NEXT step's buckets)."""
+        self.begin_step()
+        with self.scales.keep_images():
+            try:
+                yield self
+            except BaseException:
+                self.grads.discard()
+                raise
 
     def _clip_total(self, b):
         """Clips of all ranks for a local batch of b clips (sync_bn).  Exchanged — one small all-reduce with a host read-back — at the first
@@ -364,9 +172,6 @@ class TrainForward:
                 self._bn_log.append((name, stats[0], stats[1], n))
             out.append(stats)
         return out
-
-    def _bn(self, cx, name, x, new_stats, b=None):
-        return self._bn_many(cx, [(name, x)], x.shape[0] if b is None else b, new_stats)[0]
 
     def _replay_bn(self, log, new_stats):
         """The running-buffer updates of a forward whose WavEncoder pass is SHARED with an earlier forward of the step (same audio, same
@@ -452,115 +257,6 @@ class TrainForward:
         xs, ta = self._wav_encoders(cx, [(enc, e)], audio, b, new_stats)
         return xs[0], ta
 
-    def _conv_backward(self, cx, x, cin, origins, dy, taps, stride, pad, lin, lout, nseq, need_dx):
-        """Conv1d backward on channels-last rows through emage_gemm (exact fp32): x (nseq*lin, >= cin) the layer input, dy (nseq*lout, N)
-        the gradient of its pre-activation output; origins = [(weight name, bias name)] of the convolutions stacked along N.
-        Accumulates the parameter gradients; returns dx (nseq*lin, cin) when asked."""
-        ws = [self._param(wn).float() for wn, _ in origins]                      # (Cout_i, Cin, k)
-        n = sum(w.shape[0] for w in ws)
-        m = dy.shape[0]
-        mp = _rup(m)
-        if self.h2_backward:
-            return self._conv_backward_h2(cx, x, cin, origins, ws, dy, n, m, mp, taps, stride, pad, lin, lout, nseq, need_dx)
-        dy_t = torch.zeros(n, mp, dtype=torch.float32, device=cx.dev)
-        ops.transpose(dy, dy_t)
-        col_t = ops.im2col_t(x, cin, taps, stride, pad, lin, lout, nseq, mp)     # (taps*cin, mp)
-        kc = taps * cin
-        dw = torch.empty(n, _rup(kc, 4), dtype=torch.float32, device=cx.dev)[:, :kc]          # 16-byte row pitch for emage_gemm's stores
-        ops.gemm(F32, dy_t, col_t, None, None, None, dw, None, None, n=kc, cp=mp)
-        db = ops.col_sum(dy)
-        r0 = 0
-        for (wn, bn), w in zip(origins, ws):
-            rows = w.shape[0]
-            self._param_grad(wn, slice(None), dw[r0:r0 + rows].reshape(rows, taps, cin).permute(0, 2, 1))
-            self._param_grad(bn, slice(None), db[r0:r0 + rows])
-            r0 += rows
-        if not need_dx:
-            return None
-        wflat = torch.cat([w.permute(0, 2, 1).reshape(w.shape[0], taps * cin) for w in ws], 0).contiguous()        # (N, taps*cin), taps major
-        np_ = _rup(n)
-        if np_ != n:                           # the contraction length is a multiple of 64: zero channels (the tokenizers' 106 / 78 / 180 / 61 / 240-wide layers)
-            dy = torch.nn.functional.pad(dy, (0, np_ - n))
-            wflat = torch.nn.functional.pad(wflat, (0, 0, 0, np_ - n))
-        dcol = torch.empty(m, _rup(kc, 4), dtype=torch.float32, device=cx.dev)[:, :kc]
-        ops.gemm(F32, dy, ops.transpose(wflat), None, None, None, dcol, None, None, n=kc, cp=np_)
-        return ops.col2im(dcol, cin, taps, stride, pad, lin, lout, nseq)
-
-    def _conv_backward_h2(self, cx, x, cin, origins, ws, dy, n, m, mp, taps, stride, pad, lin, lout, nseq, need_dx):
-        """`_conv_backward` with both contractions as split-fp16 MFMA on EMAGE_H2 operands: dW = (gs dY)^T im2col(X) with the im2col matrix
-        written directly as an H2 image, dcol = (gs dY) W with the flattened weights converted once per forward.  Long inputs (the first
-        WavEncoder blocks: 56 clips x 6 827 positions) are walked in pieces of whole sequences of about `conv_backward_rows` output rows, so
-        the im2col image, the transposed dY and dcol exist for one piece at a time (0.5 GB instead of 1.5 GB each); dW is summed over the pieces."""
-        gs = self.grad_scale
-        kc = taps * cin
-        per = max(1, self.conv_backward_rows // max(lout, 1))
-        pieces = [(s0, min(s0 + per, nseq)) for s0 in range(0, nseq, per)]
-        w_t = wsc = None
-        np_ = _rup(n)
-        # stride-1 'same' convolutions (every conv2 of the WavEncoder blocks, the motion encoder): dX is itself a convolution of dY with the
-        # flipped, transposed filters — ONE implicit-GEMM launch per piece writing dX, instead of dcol = dY W (M x taps*Cin float32: 1.5 GB for
-        # the first block at 56 clips) + col2im
-        direct = need_dx and self.direct_conv_dx and stride == 1 and lin == lout and 2 * pad == taps - 1 and cin % 8 == 0
-        if direct:
-            key = ("conv^T",) + tuple(wn for wn, _ in origins)
-            hit = self._wt_cache.get(key)
-            if hit is None:
-                wcat = torch.cat(ws, 0) if len(ws) > 1 else ws[0]                                                      # (N, Cin, k)
-                wrev = torch.nn.functional.pad(wcat.flip(2).permute(1, 2, 0), (0, np_ - n)).reshape(cin, taps * np_).contiguous()   # [ci][k-1-tap][co], co padded
-                wsc = self._backward_scale(key, wcat)
-                hit = self._wt_cache[key] = (ops.h2_cast(wrev, taps * np_, scale=wsc / 16.0), wsc)
-            w_t, wsc = hit
-        elif need_dx:
-            key = ("conv",) + tuple(wn for wn, _ in origins)
-            hit = self._wt_cache.get(key)
-            if hit is None:
-                wflat = torch.cat([w.permute(0, 2, 1).reshape(w.shape[0], kc) for w in ws], 0).contiguous()          # (N, taps*cin), taps major
-                wsc = self._backward_scale(key, wflat)
-                hit = self._wt_cache[key] = (ops.h2_cast(wflat, np_, scale=wsc / 16.0, transpose=True), wsc)           # (taps*cin, rup64(N))
-            w_t, wsc = hit
-        dw = dx = None
-        for s0, s1 in pieces:
-            whole = len(pieces) == 1
-            xs = x if whole else x[s0 * lin:s1 * lin]
-            dys = dy if whole else dy[s0 * lout:s1 * lout]
-            ms = (s1 - s0) * lout
-            mps = _rup(ms)
-            dy_t = ops.h2_cast(dys, mps, scale=gs, transpose=True)                          # (N, mps)
-            col_t = ops.im2col_t_h2(xs, cin, taps, stride, pad, lin, lout, s1 - s0, mps)    # (taps*cin, mps)
-            dwp = torch.empty(n, _rup(kc, 4), dtype=torch.float32, device=cx.dev)[:, :kc]
-            ops.gemm(H2, dy_t, col_t, None, None, None, None, dwp, None, n=kc, cp=mps, w_scale=16.0, a_scale=16.0 * gs, workspace=self._splitk_ws(cx.dev))
-            del col_t, dy_t
-            dw = dwp if dw is None else dw.add_(dwp)
-            if direct:
-                dy_h = ops.h2_cast(dys, np_, scale=gs)
-                if dx is None:
-                    dx = torch.empty(nseq * lin, cin, dtype=torch.float32, device=cx.dev)
-                ops.gemm(H2, dy_h, w_t, None, None, None, None, dx if whole else dx[s0 * lin:s1 * lin], None, n=cin, cp=np_, taps=taps, stride=1, pad=taps - 1 - pad,
-                         lin=lout, lout=lin, m=(s1 - s0) * lin, w_scale=wsc, a_scale=16.0 * gs)
-                del dy_h
-            elif need_dx:
-                dy_h = ops.h2_cast(dys, np_, scale=gs)
-                dcol = torch.empty(ms, _rup(kc, 4), dtype=torch.float32, device=cx.dev)[:, :kc]
-                ops.gemm(H2, dy_h, w_t, None, None, None, None, dcol, None, n=kc, cp=np_, w_scale=wsc, a_scale=16.0 * gs, workspace=self._splitk_ws(cx.dev))
-                del dy_h
-                part = ops.col2im(dcol, cin, taps, stride, pad, lin, lout, s1 - s0)
-                del dcol
-                if whole:
-                    dx = part
-                else:
-                    if dx is None:
-                        dx = torch.empty(nseq * lin, cin, dtype=torch.float32, device=cx.dev)
-                    dx[s0 * lin:s1 * lin].copy_(part)
-                del part
-        db = ops.col_sum(dy)
-        r0 = 0
-        for (wn, bn), w in zip(origins, ws):
-            rows = w.shape[0]
-            self._param_grad(wn, slice(None), dw[r0:r0 + rows].reshape(rows, taps, cin).permute(0, 2, 1))
-            self._param_grad(bn, slice(None), db[r0:r0 + rows])
-            r0 += rows
-        return dx
-
     def _bn_backward_many(self, items):
         """Training-mode BatchNorm backward of several INDEPENDENT BatchNorms: items = [(name, x, stats, dy)] -> [dx]; parameter gradients
         are accumulated.  sync_bn: the per-channel sums of ALL items are summed over the ranks in ONE all-reduce (local sums -> parameter
@@ -581,9 +277,6 @@ class TrainForward:
             self._param_grad(name + ".bias", slice(None), db)
             out.append(dx)
         return out
-
-    def _bn_backward(self, name, x, stats, dy):
-        return self._bn_backward_many([(name, x, stats, dy)])[0]
 
     def _wav_blocks_backward(self, cx, svs):
         """BasicBlock.forward (P:283-294) backwards for the same block of several encoders in lock step: LeakyReLU, [bn2 and the
@@ -645,351 +338,10 @@ class TrainForward:
         else:
             tape.add(sv["x_prev"], self._conv_backward(cx, sv["x_prev"], cin, origins, dys, k, stride, pad, lin, lout, b, True), cols=cin)
 
-    # ---- Conv1d(k=3) + LeakyReLU + ResBlock stacks (VQEncoderV5 / V6, VQDecoderV5: P:178-261), tape-aware --------------------------------
-    def _conv3(self, cx, x, key, t, b, cin, slope=None, res=None, need_dx=True):
-        """y (M, rup64(n)) = act(conv3(x) + bias) (+ res); columns [n, rup64(n)) are zero.  need_dx False: x is the network's input."""
-        n = cx.pk.w[key]["n"]
-        y, _ = cx.conv3(x, key, t, slope=slope, res=res, n_store=_rup(n))
-        if self.tape is not None:
-            def bw():
-                g = self.tape.get(y)
-                if g is None:
-                    return
-                if res is not None:
-                    self.tape.add(res, g)
-                yv = y
-                if g.shape[1] != n:                      # a width that is not a multiple of 64: the padding columns carry no gradient
-                    g, yv = g[:, :n].contiguous(), y[:, :n]
-                dpre = g if slope is None else ops.act_backward(g, yv, slope)
-                dx = self._conv_backward(cx, x, cin, [(key + ".weight", key + ".bias")], dpre, 3, 1, 1, t, t, b, need_dx)
-                if need_dx:
-                    self.tape.add(x, dx, cols=cin)
-            self.tape.node(bw)
-        return y
-
-    def _conv_encoder(self, cx, prefix, x0, t, b, cin0, n_layer, need_dx=True):
-        """VQEncoderV5 / V6 (P:189-235): n_layer x [conv + LeakyReLU(0.2) + ResBlock].  need_dx False: no gradient for x0."""
-        h, cin = x0, cin0
-        for i in range(n_layer):
-            p = f"{prefix}.main.{3 * i}"
-            h = self._conv3(cx, h, p, t, b, cin, slope=0.2, need_dx=need_dx or i > 0)
-            cin = cx.pk.w[p]["n"]
-            r = self._conv3(cx, h, f"{prefix}.main.{3 * i + 2}.model.0", t, b, cin, slope=0.2)
-            h = self._conv3(cx, r, f"{prefix}.main.{3 * i + 2}.model.2", t, b, cin, res=h)
-        return h
-
-    def _conv_decoder(self, cx, prefix, z, t, b, length, n_layer):
-        """VQDecoderV5 (P:237-261): two ResBlocks, n_layer x [conv + LeakyReLU(0.2)], a bare conv -> (M, rup64(out_dim))."""
-        h, cin = z, length
-        for i in range(2):
-            r = self._conv3(cx, h, f"{prefix}.main.{i}.model.0", t, b, cin, slope=0.2)
-            h = self._conv3(cx, r, f"{prefix}.main.{i}.model.2", t, b, cin, res=h)
-        for i in range(n_layer):
-            key = f"{prefix}.main.{2 + 2 * i}"
-            h = self._conv3(cx, h, key, t, b, cin, slope=0.2)
-            cin = cx.pk.w[key]["n"]
-        return self._conv3(cx, h, f"{prefix}.main.{2 + 2 * n_layer}", t, b, cin)
-
     def _motion_encoder(self, cx, x0, t, b, cin0):
         return self._conv_encoder(cx, "motion_encoder", x0, t, b, cin0, spec.MOTION_ENC_LAYERS)
 
     # ---- differentiable pieces: each wrapper launches the forward op and, when a tape is attached, records its backward -----------
-    def _image(self, x, e):
-        """The EMAGE_H2 image of the float32 operand x for the packed Linear entry e: the one its producer wrote (`_layernorm`), else one cast launch."""
-        hit = self._h2img.pop(id(x), None)
-        if hit is not None and hit[0] is x and hit[1].shape[1] >= e["cp"]:
-            return hit[1]
-        k = e["k_real"]
-        return ops.h2_cast(x if x.shape[1] == k else x[:, :k], e["cp"])
-
-    def _gemm_fwd(self, cx, x, key, slope=None, out=None, **kw):
-        """One forward Linear: float32 in, float32 out; on pre-split operands when the entry is an EMAGE_H2 packing (`h2_forward`)."""
-        e = cx.pk.w[key]
-        if e.get("dt") != H2:
-            return cx.gemm(x, key, slope=slope, out=out, **kw)[0]
-        if out is None and kw.get("out_t") is None:
-            out = cx.f32(x.shape[0], e["n"])
-        cx.gemm(self._image(x, e), key, slope=slope, out_f32=out, want=None, **kw)
-        return out
-
-    def _lin(self, cx, x, key, slope=None, out=None, need_dx=True):
-        """y = act(x W^T + b) through emage_gemm (one fp32 output used both as the next operand and as the result)."""
-        y = self._gemm_fwd(cx, x, key, slope=slope, out=out)
-        if self.tape is not None:
-            self.tape.node(lambda: self._lin_backward(cx, x, key, slope, y, y, need_dx))
-        return y
-
-    def _lin_kv(self, cx, x, key, n_first, t_rows, b):
-        """A projection whose last columns are emitted transposed (V^T for emage_attention): returns (first n_first columns as
-        rows, the V^T buffer, a token standing for the logical (M, N) output in the tape)."""
-        n = cx.pk.w[key]["n"]
-        first = cx.lo(x.shape[0], n_first)
-        vt = cx.vt_buffer(b, n - n_first, t_rows)
-        self._gemm_fwd(cx, x, key, out=first, out_t=vt, t_col0=n_first, t_rows=t_rows)
-        token = _Token((x.shape[0], n))
-        if self.tape is not None:
-            self.tape.node(lambda: self._lin_backward(cx, x, key, None, token, None, True))
-        return first, vt, token
-
-    def _lin_backward(self, cx, x, key, slope, y_id, y, need_dx):
-        tape = self.tape
-        dy = tape.get(y_id)
-        if dy is None:
-            return
-        ent = cx.pk.w[key]
-        n, k = ent["n"], ent["k_real"]
-        m = dy.shape[0]
-        if dy.shape[1] != n or dy.stride(1) != 1:
-            raise RuntimeError(f"{key}: gradient of shape {tuple(dy.shape)} for an output of {n} columns")
-        if self.h2_backward:
-            self._lin_backward_h2(cx, x, key, dy, y if slope is not None else None, slope, n, k, m, need_dx)
-            return
-        dpre = dy if slope is None else ops.act_backward(dy, y, slope)
-        w32 = torch.cat([self._param(wn)[rs] for wn, _bn, rs in cx.pk.origin[key]], 0).float().contiguous()            # (N, K)
-        mp = _rup(m)
-        dpre_t = torch.zeros(n, mp, dtype=torch.float32, device=cx.dev)
-        ops.transpose(dpre, dpre_t)
-        x_t = torch.zeros(k, mp, dtype=torch.float32, device=cx.dev)
-        ops.transpose(x[:, :k], x_t)
-        dw = torch.empty(n, k, dtype=torch.float32, device=cx.dev)
-        ops.gemm(F32, dpre_t, x_t, None, None, None, dw, None, None, n=k, cp=mp)                                          # dW = dpre^T x
-        self._lin_param_grads(cx, key, dw, dpre)
-        if need_dx:
-            np_ = _rup(n)
-            if np_ != n:
-                raise RuntimeError(f"{key}: {n} output columns (not a multiple of 64) — pad before the backward contraction")
-            w_t = ops.transpose(w32)                                                                                    # (K, N)
-            dx = torch.empty(m, k, dtype=torch.float32, device=cx.dev)
-            ops.gemm(F32, dpre, w_t, None, None, None, dx, None, None, n=k, cp=n)                                        # dX = dpre W
-            tape.add(x, dx, cols=k)
-
-    def _lin_param_grads(self, cx, key, dw, dpre):
-        """Hand dW (N, K) and the bias gradient (column sums of dpre) of the packed Linear `key` to the parameters it stacks."""
-        origin = cx.pk.origin[key]
-        if len(origin) == 1:                              # the usual case: the reduction's finalize adds into the gradient rows itself
-            wn, bn, rs = origin[0]
-            self._param_grad(wn, rs, dw)
-            self._param_grad_colsum(bn, rs, dpre)
-            return
-        db = ops.col_sum(dpre)
-        r0 = 0
-        for wn, bn, rs in origin:
-            rows = rs.stop - rs.start
-            self._param_grad(wn, rs, dw[r0:r0 + rows])
-            self._param_grad(bn, rs, db[r0:r0 + rows])
-            r0 += rows
-
-    def _backward_scale(self, key, w):
-        """Power-of-two scale of a backward weight operand: chosen at the first use of `key` (one read-back: max |w| into [2^11, 2^12)) and
-        kept, so that later steps — and a captured step — convert without a host round trip.  Every later use checks ON THE DEVICE that
-        max |w| * scale is still inside [2^10, 2^14) (`ops.f16_scale_out_of_range`; the fp16 hi plane overflows at 2^16) and counts a
-        miss in `range_flag`, which `Trainer` reads with the losses and answers by re-deriving the scales (`reset_scales`)."""
-        ws = self._w_scale.get(key)
-        if ws is None:
-            import math
-            mx = float(w.abs().max())
-            ws = self._w_scale[key] = 2.0 ** (11 - math.floor(math.log2(mx))) if mx > 0 and math.isfinite(mx) else 1.0
-        elif w.numel() and key not in self._range_seen:     # once per key and step, all keys in a few launches (`flush_range_checks`)
-            self._range_seen.add(key)
-            self._range_pending.append((w, ws))
-        return ws
-
-    def flush_range_checks(self, new_step=False):
-        """Fold the backward operands queued by `_backward_scale` into `range_flag`; new_step: forget which keys this step has seen."""
-        if self._range_pending:
-            ws, scales = zip(*self._range_pending)
-            self._range_pending = []
-            bad = ops.f16_scales_out_of_range(list(ws), list(scales))
-            self.range_flag = bad if self.range_flag is None else self.range_flag + bad
-        if new_step:
-            self._range_seen = set()
-
-    def reset_scales(self):
-        """Forget the cached operand scales (backward weight operands here, the forward's packed operands in the model): the next
-        forward chooses them afresh from the current weights."""
-        self._w_scale, self._wt_cache, self.range_flag = {}, {}, None
-        self._range_pending, self._range_seen = [], set()
-        self.model.invalidate_packed(reset_scales=True)
-        self._pcache = None
-
-    def _weight_t_h2(self, cx, key, n, k):
-        """The transposed weight of a Linear as an EMAGE_H2 operand, (K, rup64(N)) holding w * w_scale: (image, w_scale); built once per
-        forward and key, scale from `_backward_scale`."""
-        hit = self._wt_cache.get(key)
-        if hit is not None:
-            return hit
-        rows = [self._param(wn)[rs] for wn, _bn, rs in cx.pk.origin[key]]
-        w32 = (torch.cat(rows, 0) if len(rows) > 1 else rows[0]).float().contiguous()                                    # (N, K); one source: no copy
-        ws = self._backward_scale(key, w32)
-        img = ops.h2_cast(w32, _rup(n), scale=ws / 16.0, transpose=True)              # h2 images carry a fixed x16: the rest of the scale goes in front
-        self._wt_cache[key] = (img, ws)
-        return img, ws
-
-    def _lin_backward_h2(self, cx, x, key, dy, y, slope, n, k, m, need_dx):
-        """dW = dpre^T x, db = colsum(dpre), dX = dpre W as split-fp16 MFMA contractions (emage_gemm, EMAGE_H2).  dpre = dy through the
-        activation's backward (y: the layer's saved output, None = no activation).  ONE pass over dy (`ops.grad_prep`) yields both
-        gradient operands — pre-scaled by `grad_scale`, undone by the GEMM's output scale — and the bias gradient, which the reduction's
-        finalize launch adds straight into the parameter's gradient rows when the packed key holds one Linear."""
-        gs = self.grad_scale
-        mp = _rup(m)
-        origin = cx.pk.origin[key]
-        single = len(origin) == 1
-        bias_dst = self._grad_rows(origin[0][1], origin[0][2])[0] if single else None
-        dpre_h, dpre_t, db = ops.grad_prep(dy, y, 0.0 if slope is None else slope, gs, n_store=_rup(n) if need_dx else None, m_store=mp,
-                                           bias_grad=bias_dst, accumulate=single,                # (M, rup64(N)), (N, mp)
-                                           defer=self._fin if (single and self.defer_finalize) else None)
-        x_t = ops.h2_cast(x[:, :k], mp, scale=1.0, transpose=True)                    # (K, mp)
-        wdst = self._grad_rows(origin[0][0], origin[0][2])[0] if single else None
-        if self.accumulate_dw and wdst is not None and wdst.dim() == 2 and wdst.stride(1) == 1 and wdst.stride(0) % 4 == 0 and wdst.data_ptr() % 16 == 0:
-            # dW added by the contraction itself (res == out_f32: the epilogue's residual add in place, or split-K atomics onto the contents)
-            ops.gemm(H2, dpre_t, x_t, None, None, wdst, None, wdst, None, n=k, cp=mp, w_scale=16.0, a_scale=16.0 * gs, workspace=self._splitk_ws())
-        else:
-            dw = torch.empty(n, k, dtype=torch.float32, device=cx.dev)
-            ops.gemm(H2, dpre_t, x_t, None, None, None, None, dw, None, n=k, cp=mp, w_scale=16.0, a_scale=16.0 * gs, workspace=self._splitk_ws(cx.dev))
-            r0 = 0
-            for wn, bn, rs in origin:
-                rows = rs.stop - rs.start
-                self._param_grad(wn, rs, dw[r0:r0 + rows])
-                r0 += rows
-        if not single:
-            r0 = 0
-            for wn, bn, rs in origin:
-                rows = rs.stop - rs.start
-                self._param_grad(bn, rs, db[r0:r0 + rows])
-                r0 += rows
-        if need_dx:
-            w_t, ws = self._weight_t_h2(cx, key, n, k)
-
-            def make(prev):                            # prev: the gradient x has collected so far (its residual path) — added by this launch's epilogue
-                dx = torch.empty(m, k, dtype=torch.float32, device=cx.dev)
-                if prev is not None and not (self.fuse_grad_adds and prev.shape == dx.shape and prev.stride(1) == 1 and prev.stride(0) % 4 == 0 and prev.data_ptr() % 16 == 0):
-                    ops.gemm(H2, dpre_h, w_t, None, None, None, None, dx, None, n=k, cp=_rup(n), w_scale=ws, a_scale=16.0 * gs, workspace=self._splitk_ws(cx.dev))
-                    out = torch.empty_like(dx)
-                    _accumulate(prev, dx, out=out)
-                    return out
-                ops.gemm(H2, dpre_h, w_t, None, None, prev, None, dx, None, n=k, cp=_rup(n), w_scale=ws, a_scale=16.0 * gs, workspace=self._splitk_ws(cx.dev))
-                return dx
-            self.tape.add_through(x, make, cols=k)
-
-    def _params(self):
-        """name -> detached parameter / buffer view, built once per forward (walking the module tree per lookup costs more than
-        the launches it feeds)."""
-        if self._pcache is None:
-            dev = self.model.device
-            self._pcache = {k: v.detach().to(dev) for k, v in self.model._flat_params().items()}
-        return self._pcache
-
-    def _param(self, name):
-        return self._params()[name]
-
-    @property
-    def param_grads(self):
-        """name -> fp32 gradient accumulated so far (queued contributions applied first: reading is always consistent)."""
-        self.flush_param_grads()
-        return self._pgrads
-
-    @param_grads.setter
-    def param_grads(self, value):
-        self.flush_param_grads()          # contributions queued for the previous accumulators belong to them
-        self._pgrads = value
-
-    def _grad_rows(self, name, rows):
-        """The rows `rows` of parameter `name`'s gradient accumulator (the exchange bucket's view under a `Trainer`) as the destination of
-        one more contribution: a queued contribution to overlapping rows is applied first; the tape position is stamped."""
-        full = self._pgrads.get(name)
-        if full is None:
-            full = self.grad_views[name] if self.grad_views is not None else torch.zeros_like(self._param(name), dtype=torch.float32)
-            self._pgrads[name] = full
-        n0 = full.shape[0] if full.dim() else 1
-        lo, hi = (0 if rows.start is None else rows.start), (n0 if rows.stop is None else rows.stop)
-        spans = self._pg_spans.get(name)
-        if spans is not None and any(lo < b and a < hi for a, b in spans):
-            self.flush_param_grads()
-        if self.touch is not None:
-            self.touch[name] = self.tape.pos
-        return full[rows], (lo, hi)
-
-    def _param_grad(self, name, rows, g):
-        """grad(name)[rows] += g — parameter-sized accumulation across the forwards of a step.  The contributions are QUEUED and applied
-        in batches (`flush_param_grads`: one multi-tensor add for up to 256 of them instead of one small launch each, ~1 200 per step);
-        every element still receives its contributions one by one in issue order, so the sums are the same bits."""
-        dst, span = self._grad_rows(name, rows)
-        g = g.reshape(dst.shape)
-        self._pg_spans.setdefault(name, []).append(span)
-        self._pg_dst.append(dst)
-        self._pg_src.append(g)
-        self._pg_bytes += g.numel() * 4
-        if len(self._pg_dst) >= 256 or self._pg_bytes >= (96 << 20):
-            self.flush_param_grads()
-
-    def _param_grad_colsum(self, name, rows, x, y=None):
-        """grad(name)[rows] += column sums of x (* y): the bias / affine gradients, accumulated by the reduction's own finalize launch."""
-        dst, _span = self._grad_rows(name, rows)
-        ops.col_sum(x, y, out=dst, accumulate=True, defer=self._fin if self.defer_finalize else None)
-
-    def flush_param_grads(self):
-        """Apply the queued parameter-gradient contributions (call before anything reads or exchanges the accumulators)."""
-        self._fin.flush()                 # the queued finalize steps of the column reductions (bias / affine gradients)
-        if self._pg_dst:
-            # ONE pair that is not dense with equal strides (the convolutions' weight gradients arrive as permuted (Cout, taps, Cin) views) sends the
-            # WHOLE multi-tensor add down torch's one-launch-per-tensor path (~440 launches per step): those pairs go in a call of their own.  The
-            # queued destinations never overlap (`_grad_rows` flushes first), so the order between the two calls does not matter
-            plain = [d.stride() == g.stride() and d.is_contiguous() for d, g in zip(self._pg_dst, self._pg_src)]
-            for want in (True, False):
-                dst = [d for d, ok in zip(self._pg_dst, plain) if ok == want]
-                if dst:
-                    torch._foreach_add_(dst, [g for g, ok in zip(self._pg_src, plain) if ok == want])
-        self._pg_dst, self._pg_src, self._pg_spans, self._pg_bytes = [], [], {}, 0
-
-    def _add(self, cx, a, bb, mod_b=0, grad_b=True):
-        out = cx.lo(*a.shape)
-        ops.add(cx.dt, a, bb, out=out, mod_b=mod_b)
-        if self.tape is not None:
-            def bw():
-                g = self.tape.get(out)
-                if g is None:
-                    return
-                self.tape.add(a, g)
-                if grad_b and not mod_b:
-                    self.tape.add(bb, g)
-            self.tape.node(bw)
-        return out
-
-    def _mul_add(self, a, mask, res=None, t_rows=0):
-        out = ops.mul_add(a, mask, res, mask_t_rows=t_rows)
-        if self.tape is not None:
-            def bw():
-                g = self.tape.get(out)
-                if g is None:
-                    return
-                self.tape.add(a, ops.mul_add(g, mask, None, mask_t_rows=t_rows))
-                if res is not None:
-                    self.tape.add(res, g)
-            self.tape.node(bw)
-        return out
-
-    def _layernorm(self, cx, key, s_in):
-        n = cx.pk.w[key]
-        y = cx.lo(*s_in.shape)
-        if self.h2_forward and s_in.shape[1] % 64 == 0:      # the result feeds a Linear: its EMAGE_H2 image leaves the same launch
-            img = cx.f32(*s_in.shape)
-            ops.layernorm(H2, s_in, n["g"], n["b"], 1e-5, None, y, img)
-            self._h2img[id(y)] = (y, img)
-        else:
-            ops.layernorm(cx.dt, s_in, n["g"], n["b"], 1e-5, None, None, y)
-        if self.tape is not None:
-            def bw():
-                g = self.tape.get(y)
-                if g is None:
-                    return
-                dg, _ = self._grad_rows(key + ".weight", slice(None))
-                db, _ = self._grad_rows(key + ".bias", slice(None))
-                dx, _, _ = ops.layernorm_backward(s_in, n["g"], g, dgamma=dg, dbeta=db,      # d gamma / d beta += inside
-                                                  defer=self._fin if self.defer_finalize else None)
-                self.tape.add(s_in, dx)
-            self.tape.node(bw)
-        return y
-
     def _drop_add(self, cx, o, masks, t, res=None):
         """res + dropout(o) with the mask the reference draws on the (T, B, C) tensor."""
         m, c = o.shape
@@ -1085,19 +437,14 @@ class TrainForward:
         c = model.config
         # the training forward keeps float32 activations (split inside the GEMMs in f16x3); train_only: the operand set leaves out what
         # only the eval-mode forward reads (the WavEncoder convolutions with their BatchNorms folded in)
-        cx = _Ctx(model._engine(h2=False, train_only=True, lin_h2=self.h2_forward))
+        cx = _Ctx(model._engine(h2=False, train_only=True))
         pk, dev = cx.pk, cx.dev
-        self._h2img = {}
         self._train_pack(pk)
-        self.tape = _Tape(dev) if tape else None
-        self._cx = cx
-        self._pcache = None
-        if not self._wt_keep:                    # inside a `Trainer` step the weights are those of the step's first forward: keep the images
-            self._wt_cache = {}
+        self._begin_forward(cx, tape)            # (inside a `Trainer` step the weights are those of the step's first forward: the images stay)
         new_stats = {} if new_stats is None else new_stats
         if self.sync_bn and share is None and not _capturing(dev):      # a forward outside a `Trainer` step (the class API): the global clip
             self._clips.clear()                                         # count is exchanged afresh (see `_clip_total`; a step: `begin_step`)
-        masks = _Masks(dropout_masks, dev, rng, lazy=self.lazy_masks)
+        masks = _Masks(dropout_masks, dev, rng, lazy=self.lazy_masks, needs=dropout_mask_count())
         b, t, cm = masked_motion.shape
         m = b * t
         d, mf, af = c.hidden_size, c.motion_f, c.audio_f
@@ -1249,18 +596,17 @@ class TrainForward:
     def backward_from(self, tape, out2d, grad_outputs):
         """Backward of ONE recorded forward from the gradients of its outputs (the autograd bridge of the model classes' train-mode
         forward: torch computes d loss / d output, this runs the rest): returns {parameter name: gradient} of that forward alone."""
-        self.tape, saved = tape, self.param_grads
-        self.param_grads = {}
+        self.tape = tape
         try:
-            for key, g in grad_outputs.items():
-                if g is not None:
-                    t = out2d[key]
-                    tape.add(t, g.reshape(t.shape).to(torch.float32).contiguous())
-            tape.run()
-            return self.param_grads
+            with self.grads.alone() as own:              # (an exception mid-walk: what was queued is dropped)
+                for key, g in grad_outputs.items():
+                    if g is not None:
+                        t = out2d[key]
+                        tape.add(t, g.reshape(t.shape).to(torch.float32).contiguous())
+                tape.run()
+            return own
         finally:
-            self._pg_dst, self._pg_src, self._pg_spans, self._pg_bytes = [], [], {}, 0       # (an exception mid-walk: drop what was queued)
-            self._pgrads, self.tape = saved, None
+            self.tape = None
 
 
 # ======================================================================================
@@ -1377,21 +723,6 @@ def step_losses(fwd: TrainForward, vq, batch, iteration, dropout_masks, random_m
     ops.loss_check(ws)
     res["all"] = sum(res.values())
     return res, stats
-
-
-def _check_max_norm(value):
-    if value is None:
-        return None
-    value = float(value)
-    if not value > 0:
-        raise ValueError("max_grad_norm must be positive (None: no clipping)")
-    return value
-
-
-def _param_grad_norms(gn, names, pre_scale):
-    if gn is None:
-        raise RuntimeError("param_grad_norms: no step has run with max_grad_norm / track_grad_norm set")
-    return {n: pre_scale * v ** 0.5 for n, v in zip(names, gn.tensor_sumsq.tolist())}
 
 
 _CLIP_TABLES = {}                                         # ((gradient pointer, n), ...) -> ops.AdamTable: valid exactly as long as the key matches
@@ -1532,18 +863,13 @@ class Trainer:
         seed_mask = torch.ones_like(masked_motion)
         seed_mask[:, :cfg.seed_frames] = 0
         fwd.param_grads = {}
-        fwd.begin_step()
-        fwd._wt_cache, fwd._wt_keep = {}, True            # the parameters move at the END of the step: one set of transposed weight images
         try:
-            return self._device_step_body(batch, dropout_masks, random_mask, grad_hook, step_counter, index, latent, masked_motion, speaker_id, seed_mask)
+            with fwd.step():                              # a step that dies mid-backward: its queued contributions die with it
+                return self._device_step_body(batch, dropout_masks, random_mask, grad_hook, step_counter, index, latent, masked_motion, speaker_id, seed_mask)
         except BaseException:
-            fwd._pg_dst, fwd._pg_src, fwd._pg_spans, fwd._pg_bytes = [], [], {}, 0       # a step that died mid-backward: its queued contributions die with it
-            fwd._fin.entries = []                         # ... and its queued finalize launches (their float64 partials would land in the NEXT step's buckets)
             for flat in self.buckets.flat:                # Adam's zero_grad never ran for the dead step
                 flat.zero_()
             raise
-        finally:
-            fwd._wt_cache, fwd._wt_keep = {}, False
 
     def _device_step_body(self, batch, dropout_masks, random_mask, grad_hook, step_counter, index, latent, masked_motion, speaker_id, seed_mask):
         fwd, model = self.fwd, self.fwd.model
@@ -1565,7 +891,7 @@ class Trainer:
             progress = None
             if f == 2:
                 if learning:
-                    fwd.touch = {}
+                    fwd.grads.touch = {}
                 elif exchanging:
                     ready = {}
                     for i, pos in self.schedule.items():
@@ -1588,11 +914,11 @@ class Trainer:
             tdist.all_reduce(self.loss_health, op=tdist.ReduceOp.MAX, group=self.group)
         if learning:
             last = {}
-            for name, pos in fwd.touch.items():
+            for name, pos in fwd.grads.touch.items():
                 i = self.bucket_of[name]
                 last[i] = max(last.get(i, -1), pos)
             self.schedule = {i: last.get(i, -1) for i in range(len(buckets.flat))}      # -1: complete before the third backward starts
-            fwd.touch = None
+            fwd.grads.touch = None
             if exchanging:
                 for i in range(len(buckets.flat)):
                     log.append(("reduce", i, None))
@@ -1617,17 +943,13 @@ class Trainer:
                 quads.append((p, g, st["exp_avg"], st["exp_avg_sq"]))
             self._adam = ops.AdamTable(quads, model.device)
             self._adam_names = list(buckets.grads)
-        clip = {}
-        if self._max_grad_norm is not None or self.track_grad_norm:
-            # global norm of the exchanged gradient SUM times 1 / world = the norm of the average; the coefficient rides into Adam on the device
-            self._grad_norm = ops.grad_norm(self._adam, pre_scale=1.0 / world, max_norm=self._max_grad_norm)
-            if self._max_grad_norm is not None:
-                clip = dict(grad_scale_dev=self._grad_norm.coef)
         self.steps_done += 1
         for st in self.state.values():
             st["step"] = self.steps_done
-        ops.adam_multi(self._adam, self.steps_done if step_counter is None else step_counter, self.lr, self.betas[0], self.betas[1], self.eps,
-                       self.weight_decay, grad_scale=1.0 / world, zero_grad=True, skip=self.health, **clip)
+        norm = clip_and_adam(self._adam, self.steps_done if step_counter is None else step_counter, self.lr, self.betas, self.eps, self.weight_decay,
+                             self.health, max_norm=self._max_grad_norm, track=self.track_grad_norm, world=world)
+        if norm is not None:
+            self._grad_norm = norm
         skipped = self.health[0] > 0                      # device scalar: the buffers below keep their values in a skipped step
         by_dtype = {}
         for name, v in stats.items():                     # BatchNorm running statistics after the three forwards
@@ -1641,20 +963,16 @@ class Trainer:
             step_counter.sub_(skipped.to(step_counter.dtype))
         return out, ws
 
+    @contextlib.contextmanager
     def _deferred_range_check(self):
         """Context: `model._engine()` leaves the operand-scale flags of a re-packing unread (no host synchronisation in front of a step);
         `_finish` reads them with the losses."""
-        import contextlib
         model = self.fwd.model
-
-        @contextlib.contextmanager
-        def cm():
-            model.__dict__["_defer_range_check"] = True
-            try:
-                yield
-            finally:
-                model.__dict__["_defer_range_check"] = False
-        return cm()
+        model.__dict__["_defer_range_check"] = True
+        try:
+            yield
+        finally:
+            model.__dict__["_defer_range_check"] = False
 
     def _range_flags(self):
         """The device counters of weight operands whose cached power-of-two scale no longer fits (forward packing, backward operands)."""
@@ -1727,7 +1045,7 @@ class Trainer:
         model = self.fwd.model
         model.bump_versions([p for p in model.parameters() if p.requires_grad])
         model.invalidate_packed()
-        self.fwd._pcache = None
+        self.fwd.parameters_moved()
 
     # ---- the step as ONE hipGraph -------------------------------------------------------------------------------------------------
     def capture(self, batch, random_mask, dropout_masks=None, prologue=None, speaker_id=None):
@@ -1804,7 +1122,7 @@ class Trainer:
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph, capture_error_mode="thread_local"):
             model.invalidate_packed()                                  # so that the packing of the current parameters is part of the graph
-            fwd._pcache = None
+            fwd.parameters_moved()
             if prologue is not None:
                 prologue()
             self._step_counter.add_(1)

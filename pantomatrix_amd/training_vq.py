@@ -1,7 +1,7 @@
 """The motion tokenizers in TRAIN mode on the MI355X kernels: `EmageVQVAEConv` (encoder -> Quantizer -> decoder, M:34-46) and
 `EmageVAEConv` (encoder -> decoder, M:19-32) of the reference's models/emage_audio/modeling_emage_audio.py, differentiable.
 
-The conv stacks are `training.TrainForward`'s tape-aware `_conv3` (the same Conv1d(k=3) + LeakyReLU(0.2) + ResBlock layers the EMAGE
+The conv stacks are `tape.TapeForward`'s tape-aware `_conv3` (the same Conv1d(k=3) + LeakyReLU(0.2) + ResBlock layers the EMAGE
 training forward runs for its motion pre-encoder, with the same backward contractions); the quantiser (P:144-156) is
 `emage_vq_argmin_f32` (the one kernel pinned to the reference's association and tie rule) followed by `emage_vq_quantize_train`
 (codebook rows, histogram, embedding_loss and perplexity as device scalars), and on the way back `emage_vq_quantize_backward`
@@ -18,12 +18,12 @@ import torch
 
 from . import ops
 from .modeling_emage_audio import _Ctx, _rup
-from .training import TrainForward, _Tape, _check_max_norm, _param_grad_norms
+from .tape import TapeForward, _check_max_norm, _param_grad_norms, clip_and_adam
 
 CODEBOOK = "quantizer.embedding.weight"
 
 
-class TokenizerForward(TrainForward):
+class TokenizerForward(TapeForward):
     """Callable train-mode forward of an `EmageVQVAEConv` / `EmageVAEConv` with a tape; `backward()` runs it from output gradients."""
 
     def __init__(self, model):
@@ -38,8 +38,7 @@ class TokenizerForward(TrainForward):
         model, c = self.model, self.model.config
         cx = _Ctx(model._engine(h2=False, train_only=True))
         dev = cx.dev
-        self.tape = _Tape(dev) if tape else None
-        self._cx, self._pcache, self._wt_cache = cx, None, {}
+        self._begin_forward(cx, tape)
         b, t, d = inputs.shape
         length = c.vae_length
         x = ops.cast_pad(cx.dt, inputs.reshape(b * t, d).to(device=dev, dtype=torch.float32).contiguous(), _rup(d))
@@ -130,15 +129,11 @@ class _TokenizerFn(torch.autograd.Function):
         fwd = ctx.fwd
         fwd.tape, fwd._rec, fwd._zq = ctx.saved
         ctx.saved = None
-        saved, fwd.param_grads = fwd.param_grads, {}
-        try:
+        with fwd.grads.alone():                           # the gradients of this node alone; the caller's accumulators are back behind it
             grads = fwd.backward(g_rec, g_feat, g_loss)
             fwd.flush_range_checks(new_step=True)
             if fwd.range_flag is not None and int(fwd.range_flag) != 0:      # a weight left the band its cached operand scale was chosen for
                 fwd.reset_scales()
-        finally:
-            fwd._pg_dst, fwd._pg_src, fwd._pg_spans, fwd._pg_bytes = [], [], {}, 0
-            fwd._pgrads = saved
         return (None, None, None) + tuple(grads.get(n) for n in ctx.names)
 
 
@@ -211,13 +206,11 @@ class TokenizerTrainer:
         self.health.zero_()
         ops.count_nonfinite_multi(list(self.grads.values()), self.health)
         self.step_counter.add_(1)
-        clip, max_norm = {}, _check_max_norm(self.max_grad_norm)
-        tracking = max_norm is not None or self.track_grad_norm
+        norm = clip_and_adam(self._adam, self.step_counter, self.lr, self.betas, self.eps, 0.0, self.health,
+                             max_norm=_check_max_norm(self.max_grad_norm), track=self.track_grad_norm)
+        tracking = norm is not None
         if tracking:
-            self._grad_norm = ops.grad_norm(self._adam, max_norm=max_norm)
-            if max_norm is not None:
-                clip = dict(grad_scale_dev=self._grad_norm.coef)
-        ops.adam_multi(self._adam, self.step_counter, self.lr, self.betas[0], self.betas[1], self.eps, 0.0, zero_grad=True, skip=self.health, **clip)
+            self._grad_norm = norm
         self.step_counter.sub_((self.health > 0).to(torch.int32))       # a skipped step does not count
         self.model.bump_versions(self._params)                  # updated through raw pointers: the next `_engine()` re-packs
         res = {"rec": float(rec_loss)}

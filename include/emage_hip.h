@@ -383,6 +383,29 @@ int emage_q_attention(int dtype, const emage_q_attention_problem* problem, int T
 int emage_q_attention_grouped(int dtype, const emage_q_attention_problem* problems, int n_problems, int T, int Tk, int d, int H, void* stream);
 
 /*
+ * The same site when the layer's memory K / V^T are a Linear projection of a feature image that nothing else reads (the two decoder stacks:
+ * their memory projection composed with the K / V projections at packing time, K = (a Wp^T + bp) Wk^T + bk = a (Wk Wp)^T + (Wk bp + bk)): the
+ * workgroup of (clip, head) computes K_h / V_h of its 64 memory frames itself, then q_h, then the attention.  `out` is bit for bit
+ *     emage_gemm(dtype, mem, ldm, Wkv, bias_kv, out_f32 = K (B Tk, kv_layers d), out_t = V^T (B, kv_layers d, 64), t_col0 = kv_layers d, t_rows = 64,
+ *                M = B Tk, N = 2 kv_layers d, Cp = km, a_scale, wkv_scale)
+ *     emage_q_attention(... k = K + kv_layer d, ldk = kv_layers d, vt = V^T + kv_layer d 64, vt_rows = kv_layers d ...)
+ * A, W, bias, ln_stats / ln_c / ln_eps, out, lda, ldo, B, a_scale, w_scale: as for emage_q_attention.
+ * mem:  (B Tk, ldm) EMAGE_H2 image of the memory features, km columns used; ldm % 8 == 0, ldm >= km; km % 32 == 0, 32 <= km <= d.
+ * Wkv:  (2 kv_layers d, km) packed image times wkv_scale, rows [K_0 .. K_n | V_0 .. V_n] (d rows per layer); bias_kv (2 kv_layers d) fp32.
+ * kv_layer: the layer of the stack this site belongs to, 0 <= kv_layer < kv_layers <= 64.
+ * Only T = Tk = 64, d = 768, H = 4 and dtype EMAGE_H2 (with any activation shift); anything else is EMAGE_EINVAL.  Pointers 16-byte aligned.
+ * The grouped form runs 1..4 independent problems in one launch (the two stacks in lock step).
+ */
+typedef struct emage_qm_attention_problem {
+    const void* A; const void* W; const float* bias; const float* ln_stats; const float* ln_c;
+    const void* mem; const void* Wkv; const float* bias_kv; void* out;
+    int lda, ldm, km, kv_layers, kv_layer, ldo, B;
+    float a_scale, w_scale, wkv_scale, ln_eps;
+} emage_qm_attention_problem;
+int emage_qm_attention(int dtype, const emage_qm_attention_problem* problem, int T, int Tk, int d, int H, void* stream);
+int emage_qm_attention_grouped(int dtype, const emage_qm_attention_problem* problems, int n_problems, int T, int Tk, int d, int H, void* stream);
+
+/*
  * K5 — LayerNorm(C, eps) over rows (post-norm of every transformer sub-layer):
  *   y = (x - mean) * rsqrt(var + eps) * gamma + beta (+ add[m][:])
  * x: (M, ldx) `dtype` — the residual stream is stored in the compute dtype (fp32 in parity mode, bf16 in bf16

@@ -41,6 +41,13 @@ class QAttentionProblem(C.Structure):
                 + [(n, _f) for n in ("a_scale", "w_scale", "ln_eps")])
 
 
+class QmAttentionProblem(C.Structure):
+    """`emage_qm_attention_problem` of include/emage_hip.h (emage_qm_attention takes one, emage_qm_attention_grouped an array of them)."""
+    _fields_ = ([(n, _p) for n in ("A", "W", "bias", "ln_stats", "ln_c", "mem", "Wkv", "bias_kv", "out")]
+                + [(n, _i) for n in ("lda", "ldm", "km", "kv_layers", "kv_layer", "ldo", "B")]
+                + [(n, _f) for n in ("a_scale", "w_scale", "wkv_scale", "ln_eps")])
+
+
 class FinalizeEntry(C.Structure):
     """`emage_finalize_entry` of include/emage_hip.h (emage_col_sum_finalize_multi takes a host array of them)."""
     _fields_ = [("partial", _p), ("out", _p), ("chunks", _i), ("C", _i), ("accumulate", _i)]
@@ -83,6 +90,8 @@ SIGNATURES = {
     "emage_qkv_attention_grouped": [_i, C.POINTER(QkvAttentionProblem), _i, _i, _i, _i, _p],
     "emage_q_attention": [_i, C.POINTER(QAttentionProblem), _i, _i, _i, _i, _p],
     "emage_q_attention_grouped": [_i, C.POINTER(QAttentionProblem), _i, _i, _i, _i, _i, _p],
+    "emage_qm_attention": [_i, C.POINTER(QmAttentionProblem), _i, _i, _i, _i, _p],
+    "emage_qm_attention_grouped": [_i, C.POINTER(QmAttentionProblem), _i, _i, _i, _i, _i, _p],
     "emage_bn_stats_workspace_bytes": [_i, _i],
     "emage_bn_stats": [_p, _i, _i, _i, _p, _l, _p, _p, _p, _p, _f, _p],
     "emage_bn_apply": [_p, _i, _p, _p, _p, _p, _p, _i, _p, _p, _p, _p, _f, _f, _p, _i, _i, _i, _p],

@@ -360,10 +360,11 @@ __device__ __forceinline__ void h2_tile_epilogue(const GemmArgs& p, f32x4 (&acc)
 // accumulator is that of KPB = 1, so the result is the same bits.  Not with DILV.
 // LNF: the instantiation carries the LayerNorm-fold paths (GemmArgs::ln_stats / rs_stats / st_out); the plain one ignores those fields
 // SKF: the instantiation carries the in-kernel split-K fix-up (GemmArgs::sk_ws / sk_count)
-// SEG3 (qkv_attention.hip): the BN tile rows are three slices of BN / 3 W rows, p.N / 3 rows apart (q, k, v of one head of a packed in_proj)
+// SEGS (qkv_attention.hip: 3, q_attention.hip's k|v projection: 2): the BN tile rows are SEGS slices of BN / SEGS W rows, p.N / SEGS rows apart
+// (q, k, v of one head of a packed in_proj; k, v of one head of one layer of a stacked memory projection)
 // EPI: a callable that replaces the epilogue — epi(acc, first row of the wave tile, wm, wn, fr, fg, ln_mu, ln_rs), with every wave
 // past the K-loop (the operand ring is still being read by other waves: the callable synchronises before it reuses it)
-template <int BM, int BN, int WM, int WN, int NS, bool DILV = false, bool TRACE = false, int KPB = 1, bool LNF = false, bool SKF = false, bool SEG3 = false,
+template <int BM, int BN, int WM, int WN, int NS, bool DILV = false, bool TRACE = false, int KPB = 1, bool LNF = false, bool SKF = false, int SEGS = 1,
           typename EPI = std::nullptr_t>
 __device__ __forceinline__ void gemm_h2_tile(const GemmArgs& p, const int m0, const int n0, unsigned char* smem, const int split = 0, EPI epi = nullptr) {
     constexpr int ES = 4, BK = 32, RB = 128, RPI = 8;
@@ -427,7 +428,7 @@ __device__ __forceinline__ void gemm_h2_tile(const GemmArgs& p, const int m0, co
 #pragma unroll
     for (int j = 0; j < GB; ++j) {
         const int row = (wave + NW * j) * RPI + lrow;
-        const int n = n0 + row + (SEG3 ? (row / (BN / 3)) * (p.N / 3 - BN / 3) : 0);
+        const int n = n0 + row + (SEGS > 1 ? (row / (BN / SEGS)) * (p.N / SEGS - BN / SEGS) : 0);
         const int lc = lslot ^ swzW<8>(row);
         b_voff[j] = n < p.N ? (unsigned)n * (unsigned)(p.K * ES) + (unsigned)((2 * (lc & 3) + (lc >> 2)) * 16) : OOB;
     }

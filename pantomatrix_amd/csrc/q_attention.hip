@@ -12,6 +12,7 @@
 //   * attention: attn_tile on LDS fragments (QLDS), four waves of 16 queries; `att` is written as the EMAGE_H2 image.
 // Every q value, every split plane and the order of every MFMA over its contraction are those of the two-launch sequence: the output is
 // the same bits (tests/test_q_attention_gpu.py).
+// emage_qm_attention (second kernel below): the same site computing the layer's memory K / V^T itself, for the two decoder stacks.
 #include "common.h"
 #include <math.h>
 #include "h2_tile.h"
@@ -33,6 +34,16 @@ struct QAttnArgs {
 };
 using QAttnGroup = SiteGroup<QAttnArgs, CA_MAXG>;
 
+// emage_qm_attention: the site computes its memory K / V^T itself (see the kernel below)
+constexpr int QM_BN = 2 * CA_HD, QM_NS = 2;
+struct QmAttnArgs {
+    GemmArgs g;                              // the q projection, as in QAttnArgs
+    GemmArgs kv;                             // the stacked k|v projection of the memory features as emage_gemm runs it (M = B Tk, N = 2 layers d, K = km)
+    int layer;                               // this site's layer in the stack: W rows [layer d, (layer + 1) d) are its keys, those N / 2 further on its values
+    void* out; int ldo;                      // att: (B T, ldo) EMAGE_H2 image
+};
+using QmAttnGroup = SiteGroup<QmAttnArgs, CA_MAXG>;
+
 }  // namespace emage_dev
 
 namespace {
@@ -43,8 +54,77 @@ constexpr int CA_LDS = L::BYTES + L::K_BYTES;            // K | V^T | Q planes
 
 static_assert(h2_smem_bytes<CA_BM, CA_BN, CA_NS>() <= CA_LDS && CA_LDS <= 160 * 1024, "the operand ring lies inside the staged planes: one block per CU");
 
-__global__ __launch_bounds__(CA_THREADS, 1) void q_attn_kernel(QAttnGroup g) {
+// The q projection's epilogue: q of this wave's 32 frames x WTN columns of head h -> split planes in LDS, K's row layout at smem + L::BYTES.
+// Synchronises the workgroup before its first LDS store (the operand ring lies under the planes).
+template <class Acc, class Stat>
+__device__ __forceinline__ void q_planes(const GemmArgs& p, const int h, unsigned char* smem, Acc& acc, const int wm, const int wn, const int fr, const int fg,
+                                         const Stat& ln_mu, const Stat& ln_rs) {
     constexpr int WTN = CA_BN / CA_WN, FN = WTN / 16;
+    constexpr int NP = FN / 2;                     // fragment pairs (8 consecutive columns per lane); an odd FN leaves a lone fragment (4 columns)
+    constexpr bool LONE = (FN & 1) != 0;
+    // every bias / c value of the lane is requested before the barrier: one memory latency, not one per fragment
+    const bool fold = p.ln_stats != nullptr;
+    const int n0 = h * CA_HD + wn * WTN + fg * 8, nl = h * CA_HD + wn * WTN + (FN - 1) * 16 + fg * 4;
+    float cv[NP][8], bv[NP][8];
+    float4 cl = make_float4(0.f, 0.f, 0.f, 0.f), bl = cl;
+    static_for<NP>([&](auto jc) {
+        constexpr int JP = decltype(jc)::value;
+        if (fold) load8<float>(p.ln_c + n0 + JP * 32, cv[JP]);
+        load8<float>(p.bias + n0 + JP * 32, bv[JP]);
+    });
+    if constexpr (LONE) {
+        if (fold) cl = *(const float4*)(p.ln_c + nl);
+        bl = *(const float4*)(p.bias + nl);
+    }
+    __syncthreads();                               // every wave has read its last fragments of the ring
+    const float os = p.o_scale;
+    // the row-major epilogue's float32 value of one accumulator (o_scale, the LayerNorm fold, bias; no slope, no residual: leaky(., 1), + 0)
+    auto value = [&](const float accv, const float c, const float bias, const float mu, const float rs) {
+        float x = accv * os;
+        if (fold) x = rs * (x - mu * c);
+        float y = x + bias;
+        y = leaky(y, 1.f);
+        y += 0.f;
+        return y;
+    };
+    // K's row layout: row fm, cell (cc / 32, (cc % 16) / 4) holds columns 32 s + 4 g + r (planes [0, 4)) and 32 s + 16 + 4 g + r ([4, 8))
+    auto cell = [&](const int fm, const int cc) { return smem + L::BYTES + fm * L::KROW + (cc >> 5) * 128 + ((cc & 15) >> 2) * 32 + ((cc & 31) >> 4) * 8; };
+    static_for<2 * NP>([&](auto ic) {
+        constexpr int I = decltype(ic)::value / NP, JP = decltype(ic)::value % NP;
+        const int fm = wm * 32 + I * 16 + fr;      // frame of this lane's row
+        const int cc = wn * WTN + JP * 32 + fg * 8;             // this lane's 8 columns inside the head: cc .. cc + 7
+        float v[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[e] = value(e < 4 ? acc[I][2 * JP][e] : acc[I][2 * JP + 1][e - 4], cv[JP][e], bv[JP][e], ln_mu[I], ln_rs[I]);
+        uint4 hi, lo;
+        h2_split8(v, hi, lo, p.h2s);               // split as attn_tile splits them
+        // columns cc .. cc + 3 and cc + 4 .. cc + 7 fill the same half of two neighbouring cells
+        unsigned char* dst = cell(fm, cc);
+        *(uint2*)dst = make_uint2(hi.x, hi.y);
+        *(uint2*)(dst + 16) = make_uint2(lo.x, lo.y);
+        *(uint2*)(dst + 32) = make_uint2(hi.z, hi.w);
+        *(uint2*)(dst + 48) = make_uint2(lo.z, lo.w);
+    });
+    if constexpr (LONE) {
+        // the lone fragment (natural W row order): 4 consecutive columns per lane, one half of one cell
+        static_for<2>([&](auto ic) {
+            constexpr int I = decltype(ic)::value;
+            const int fm = wm * 32 + I * 16 + fr;
+            const int cc = wn * WTN + (FN - 1) * 16 + fg * 4;
+            const float c4[4] = {cl.x, cl.y, cl.z, cl.w}, b4[4] = {bl.x, bl.y, bl.z, bl.w};
+            float v[4];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[e] = value(acc[I][FN - 1][e], c4[e], b4[e], ln_mu[I], ln_rs[I]);
+            uint2 hi, lo;
+            h2_split4(v, hi, lo, p.h2s);
+            unsigned char* dst = cell(fm, cc);
+            *(uint2*)dst = hi;
+            *(uint2*)(dst + 16) = lo;
+        });
+    }
+}
+
+__global__ __launch_bounds__(CA_THREADS, 1) void q_attn_kernel(QAttnGroup g) {
     __shared__ __attribute__((aligned(128))) unsigned char smem[CA_LDS];
     // XCD-aware order over the whole grid: each XCD walks a contiguous run of (clip, head) blocks, heads fastest (the four heads of a clip share A)
     const int bid = xcd_run_order((int)blockIdx.x, g.total);
@@ -58,76 +138,104 @@ __global__ __launch_bounds__(CA_THREADS, 1) void q_attn_kernel(QAttnGroup g) {
     const int b = t / CA_H, h = t - b * CA_H;
     const AttnArgs a{nullptr, q.k, q.vt, q.out, 0, q.ldk, q.ldvt, q.vt_rows, q.ldo, p.M / CA_T, CA_H, CA_T, CA_T, 1.0f / sqrtf((float)CA_HD), nullptr, p.h2s, p.h2i};
 
-    // the epilogue: q of this wave's 32 frames x WTN columns -> split planes in LDS, K's row layout at smem + L::BYTES
     auto epi = [&](auto& acc, const int, const int wm, const int wn, const int fr, const int fg, const auto& ln_mu, const auto& ln_rs) {
-        constexpr int NP = FN / 2;                     // fragment pairs (8 consecutive columns per lane); an odd FN leaves a lone fragment (4 columns)
-        constexpr bool LONE = (FN & 1) != 0;
-        // every bias / c value of the lane is requested before the barrier: one memory latency, not one per fragment
-        const bool fold = p.ln_stats != nullptr;
-        const int n0 = h * CA_HD + wn * WTN + fg * 8, nl = h * CA_HD + wn * WTN + (FN - 1) * 16 + fg * 4;
-        float cv[NP][8], bv[NP][8];
-        float4 cl = make_float4(0.f, 0.f, 0.f, 0.f), bl = cl;
-        static_for<NP>([&](auto jc) {
-            constexpr int JP = decltype(jc)::value;
-            if (fold) load8<float>(p.ln_c + n0 + JP * 32, cv[JP]);
-            load8<float>(p.bias + n0 + JP * 32, bv[JP]);
-        });
-        if constexpr (LONE) {
-            if (fold) cl = *(const float4*)(p.ln_c + nl);
-            bl = *(const float4*)(p.bias + nl);
-        }
-        __syncthreads();                               // every wave has read its last fragments of the ring
-        const float os = p.o_scale;
-        // the row-major epilogue's float32 value of one accumulator (o_scale, the LayerNorm fold, bias; no slope, no residual: leaky(., 1), + 0)
-        auto value = [&](const float accv, const float c, const float bias, const float mu, const float rs) {
-            float x = accv * os;
-            if (fold) x = rs * (x - mu * c);
-            float y = x + bias;
-            y = leaky(y, 1.f);
-            y += 0.f;
-            return y;
-        };
-        // K's row layout: row fm, cell (cc / 32, (cc % 16) / 4) holds columns 32 s + 4 g + r (planes [0, 4)) and 32 s + 16 + 4 g + r ([4, 8))
-        auto cell = [&](const int fm, const int cc) { return smem + L::BYTES + fm * L::KROW + (cc >> 5) * 128 + ((cc & 15) >> 2) * 32 + ((cc & 31) >> 4) * 8; };
-        static_for<2 * NP>([&](auto ic) {
-            constexpr int I = decltype(ic)::value / NP, JP = decltype(ic)::value % NP;
-            const int fm = wm * 32 + I * 16 + fr;      // frame of this lane's row
-            const int cc = wn * WTN + JP * 32 + fg * 8;             // this lane's 8 columns inside the head: cc .. cc + 7
-            float v[8];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) v[e] = value(e < 4 ? acc[I][2 * JP][e] : acc[I][2 * JP + 1][e - 4], cv[JP][e], bv[JP][e], ln_mu[I], ln_rs[I]);
-            uint4 hi, lo;
-            h2_split8(v, hi, lo, p.h2s);               // split as attn_tile splits them
-            // columns cc .. cc + 3 and cc + 4 .. cc + 7 fill the same half of two neighbouring cells
-            unsigned char* dst = cell(fm, cc);
-            *(uint2*)dst = make_uint2(hi.x, hi.y);
-            *(uint2*)(dst + 16) = make_uint2(lo.x, lo.y);
-            *(uint2*)(dst + 32) = make_uint2(hi.z, hi.w);
-            *(uint2*)(dst + 48) = make_uint2(lo.z, lo.w);
-        });
-        if constexpr (LONE) {
-            // the lone fragment (natural W row order): 4 consecutive columns per lane, one half of one cell
-            static_for<2>([&](auto ic) {
-                constexpr int I = decltype(ic)::value;
-                const int fm = wm * 32 + I * 16 + fr;
-                const int cc = wn * WTN + (FN - 1) * 16 + fg * 4;
-                const float c4[4] = {cl.x, cl.y, cl.z, cl.w}, b4[4] = {bl.x, bl.y, bl.z, bl.w};
-                float v[4];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = value(acc[I][FN - 1][e], c4[e], b4[e], ln_mu[I], ln_rs[I]);
-                uint2 hi, lo;
-                h2_split4(v, hi, lo, p.h2s);
-                unsigned char* dst = cell(fm, cc);
-                *(uint2*)dst = hi;
-                *(uint2*)(dst + 16) = lo;
-            });
-        }
+        q_planes(p, h, smem, acc, wm, wn, fr, fg, ln_mu, ln_rs);
     };
-    gemm_h2_tile<CA_BM, CA_BN, CA_WM, CA_WN, CA_NS, false, false, 1, true, false, false>(p, b * CA_T, h * CA_HD, smem, 0, epi);
+    gemm_h2_tile<CA_BM, CA_BN, CA_WM, CA_WN, CA_NS, false, false, 1, true, false, 1>(p, b * CA_T, h * CA_HD, smem, 0, epi);
     attn_stage_kv<CA_HD, 4, true, CA_THREADS>(a, b, h, smem);      // the ring is free: every wave passed the epilogue's barrier
     __syncthreads();
     const int wave = (int)(threadIdx.x >> 6);
     if (wave >= CA_T / 16) return;
+    attn_tile<float, CA_HD, 4, 1, true, true, true, true>(a, b, h, wave, 0, smem);
+}
+
+// emage_qm_attention — the same site when the layer's memory K / V^T are themselves a projection of a narrow feature image (the audio features of the
+// two decoder stacks, whose memory projection is composed with the K / V projections at packing time): the workgroup computes K_h / V_h of its clip
+// itself instead of reading float32 K / V^T that one large emage_gemm wrote for every layer.
+//   * k|v K-loop: gemm_h2_tile on a 64 x 384 block tile (SEGS = 2: the 192 key rows and the 192 value rows of head h of layer `layer` in the stacked
+//     [K_0 .. K_n | V_0 .. V_n] operand), eight waves of 32 x 96 on a ring of 2 (112 KiB), K = km (256 / 512); the accumulators stay in registers;
+//   * q K-loop and the q planes: q_attn_kernel's;
+//   * k / v planes: the arithmetic of emage_gemm's float32 row-major (k) and V^T (v) epilogues, split as attn_stage_kv splits the float32 values it
+//     reads, into the layout it gives them (qkv_attention.hip does the same for its own k / v);
+//   * attention: as above.
+// `att` is the same bits as emage_gemm (K float32, V^T float32) + emage_q_attention (tests/test_qm_attention_gpu.py).
+static_assert(h2_smem_bytes<CA_BM, QM_BN, QM_NS>() <= CA_LDS, "the k|v operand ring lies inside the staged planes");
+static_assert(sizeof(QmAttnGroup) <= 4096, "the argument block travels in the kernarg segment");
+
+__global__ __launch_bounds__(CA_THREADS, 1) void qm_attn_kernel(QmAttnGroup g) {
+    constexpr int KWTN = QM_BN / CA_WN, KFN = KWTN / 16, KNP = KFN / 2;
+    static_assert(KFN % 2 == 0 && CA_HD % KWTN == 0, "a wave's k|v columns are whole fragment pairs of k or of v");
+    __shared__ __attribute__((aligned(128))) unsigned char smem[CA_LDS];
+    const int bid = xcd_run_order((int)blockIdx.x, g.total);
+    int pi = 0;
+#pragma unroll
+    for (int i = 0; i < CA_MAXG - 1; ++i) pi += (i + 1 < g.n && bid >= g.blk_end[i]) ? 1 : 0;
+    pi = __builtin_amdgcn_readfirstlane(pi);
+    const int t = bid - (pi ? g.blk_end[pi - 1] : 0);
+    const QmAttnArgs& q = g.p[pi];
+    const GemmArgs& p = q.g;
+    const GemmArgs& kv = q.kv;
+    const int b = t / CA_H, h = t - b * CA_H;
+    const int nkv0 = q.layer * CA_D + h * CA_HD;       // first key row of this head in the stacked operand; its values lie kv.N / 2 rows further on
+
+    // k|v of this wave's 32 memory frames x 96 columns: kept until the q projection has run
+    f32x4 kva[CA_BM / CA_WM / 16][KFN];
+    auto keep = [&](auto& acc, const int, const int, const int, const int, const int, const auto&, const auto&) {
+        static_for<CA_BM / CA_WM / 16>([&](auto ic) { static_for<KFN>([&](auto jc) { kva[decltype(ic)::value][decltype(jc)::value] = acc[decltype(ic)::value][decltype(jc)::value]; }); });
+        __syncthreads();                               // every wave has read its last fragments: the q projection's DMA may overwrite the ring
+    };
+    gemm_h2_tile<CA_BM, QM_BN, CA_WM, CA_WN, QM_NS, false, false, 1, false, false, 2>(kv, b * CA_T, nkv0, smem, 0, keep);
+
+    auto epi = [&](auto& acc, const int, const int wm, const int wn, const int fr, const int fg, const auto& ln_mu, const auto& ln_rs) {
+        const int seg = wn * KWTN >= CA_HD ? 1 : 0;    // this wave holds keys / values (wave-uniform)
+        const int c0 = wn * KWTN - seg * CA_HD + fg * 8;       // this lane's first column inside the head
+        float kb[KNP][8];
+        static_for<KNP>([&](auto jc) { load8<float>(kv.bias + seg * (kv.N / 2) + nkv0 + c0 + decltype(jc)::value * 32, kb[decltype(jc)::value]); });
+        q_planes(p, h, smem, acc, wm, wn, fr, fg, ln_mu, ln_rs);         // (synchronises: the ring is free)
+        const float os = kv.o_scale;
+        static_for<2 * KNP>([&](auto ic) {
+            constexpr int I = decltype(ic)::value / KNP, JP = decltype(ic)::value % KNP;
+            const int fm = wm * 32 + I * 16 + fr;      // memory frame of this lane's row
+            const int cc = c0 + JP * 32;               // this lane's 8 columns inside the head: cc .. cc + 7
+            float v[8];
+            uint4 hi, lo;
+            if (seg == 0) {
+                // k: the row-major epilogue's float32 values (no slope, no residual: leaky(., 1), + 0), in K's row layout at smem
+#pragma unroll
+                for (int e = 0; e < 8; ++e) {
+                    float y = (e < 4 ? kva[I][2 * JP][e] : kva[I][2 * JP + 1][e - 4]) * os + kb[JP][e];
+                    y = leaky(y, 1.f);
+                    y += 0.f;
+                    v[e] = y;
+                }
+                h2_split8(v, hi, lo, p.h2s);
+                unsigned char* dst = smem + fm * L::KROW + (cc >> 5) * 128 + ((cc & 15) >> 2) * 32 + ((cc & 31) >> 4) * 8;
+                *(uint2*)dst = make_uint2(hi.x, hi.y);
+                *(uint2*)(dst + 16) = make_uint2(lo.x, lo.y);
+                *(uint2*)(dst + 32) = make_uint2(hi.z, hi.w);
+                *(uint2*)(dst + 48) = make_uint2(lo.z, lo.w);
+            } else {
+                // v: the V^T epilogue's values (leaky(acc + b, 1)) in attn_stage_kv's V^T layout (H2OUT row order; qkv_attention.hip): d row
+                // 32 (dt >> 1) + 4 (dt & 1) + 8 (f >> 2) + (f & 3) is staged row 16 dt + f; key fm sits in cell (fm / 32, (fm % 16) / 4), slot 4 ((fm % 32) / 16) + fm % 4
+#pragma unroll
+                for (int e = 0; e < 8; ++e) v[e] = leaky((e < 4 ? kva[I][2 * JP][e] : kva[I][2 * JP + 1][e - 4]) * os + kb[JP][e], 1.f);
+                h2_split8(v, hi, lo, p.h2s);
+                const h2f16x8 hv = __builtin_bit_cast(h2f16x8, hi), lv = __builtin_bit_cast(h2f16x8, lo);
+                unsigned char* col = smem + L::K_BYTES + ((fm >> 5) * 4 + ((fm & 15) >> 2)) * 32 + (((fm & 31) >> 4) * 4 + (fm & 3)) * 2;
+#pragma unroll
+                for (int e = 0; e < 8; ++e) {
+                    const int j = 16 * (2 * (cc >> 5) + (e >> 2)) + 4 * ((cc & 31) >> 3) + (e & 3);
+                    *(_Float16*)(col + j * L::VROW) = hv[e];
+                    *(_Float16*)(col + j * L::VROW + 16) = lv[e];
+                }
+            }
+        });
+    };
+    gemm_h2_tile<CA_BM, CA_BN, CA_WM, CA_WN, CA_NS, false, false, 1, true, false, 1>(p, b * CA_T, h * CA_HD, smem, 0, epi);
+    __syncthreads();
+    const int wave = (int)(threadIdx.x >> 6);
+    if (wave >= CA_T / 16) return;
+    const AttnArgs a{nullptr, nullptr, nullptr, q.out, 0, 0, 0, 0, q.ldo, p.M / CA_T, CA_H, CA_T, CA_T, 1.0f / sqrtf((float)CA_HD), nullptr, p.h2s, p.h2i};
     attn_tile<float, CA_HD, 4, 1, true, true, true, true>(a, b, h, wave, 0, smem);
 }
 
@@ -150,6 +258,33 @@ int q_attention_impl(int dtype, const emage_q_attention_problem* problems, int n
     return launch_sites(dtype, problems, n, H, make, q_attn_kernel, CA_THREADS, s);
 }
 
+// emage_qm_attention: the memory feature image and the stacked k|v operand in place of K / V^T
+int make_problem(int dtype, const emage_qm_attention_problem& q, int T, int Tk, int d, int H, const H2Scale& hs, QmAttnArgs& r) {
+    if (T != CA_T || Tk != CA_T || d != CA_D || H != CA_H) return EMAGE_EINVAL;
+    const int rc = site_check(dtype, q, T, d);
+    if (rc) return rc;
+    if (!q.mem || !q.Wkv || !q.bias_kv || (((uintptr_t)q.mem | (uintptr_t)q.Wkv | (uintptr_t)q.bias_kv) & 15)) return EMAGE_EINVAL;
+    if (q.km < 32 || q.km % 32 || q.km > d || q.ldm % 8 || q.ldm < q.km || !(q.wkv_scale > 0.f)) return EMAGE_EINVAL;
+    if (q.kv_layers < 1 || q.kv_layers > 64 || q.kv_layer < 0 || q.kv_layer >= q.kv_layers) return EMAGE_EINVAL;
+    if ((long)q.B * Tk * q.ldm * 4 >= (1L << 31)) return EMAGE_EINVAL;
+    r.g = site_projection(q, T, d, d, hs);
+    r.kv = r.g;                                        // the same launch-wide fields; its own operands, contraction length and scale; no LayerNorm fold
+    r.kv.A = q.mem; r.kv.W = q.Wkv; r.kv.bias = q.bias_kv;
+    r.kv.lda = q.ldm;
+    r.kv.N = 2 * q.kv_layers * d; r.kv.K = q.km; r.kv.Cp = q.km;
+    r.kv.t_col0 = r.kv.N;
+    r.kv.o_scale = 1.f / (q.a_scale * q.wkv_scale);
+    r.kv.ln_stats = nullptr; r.kv.ln_np = 0; r.kv.ln_c = nullptr;
+    r.layer = q.kv_layer;
+    r.out = q.out; r.ldo = q.ldo;
+    return 0;
+}
+
+int qm_attention_impl(int dtype, const emage_qm_attention_problem* problems, int n, int T, int Tk, int d, int H, hipStream_t s) {
+    const auto make = [=](int dt, const emage_qm_attention_problem& q, const H2Scale& hs, QmAttnArgs& r) { return make_problem(dt, q, T, Tk, d, H, hs, r); };
+    return launch_sites(dtype, problems, n, H, make, qm_attn_kernel, CA_THREADS, s);
+}
+
 }  // namespace
 
 extern "C" int emage_q_attention(int dtype, const emage_q_attention_problem* problem, int T, int Tk, int d, int H, void* stream) {
@@ -158,4 +293,12 @@ extern "C" int emage_q_attention(int dtype, const emage_q_attention_problem* pro
 
 extern "C" int emage_q_attention_grouped(int dtype, const emage_q_attention_problem* problems, int n_problems, int T, int Tk, int d, int H, void* stream) {
     return q_attention_impl(dtype, problems, n_problems, T, Tk, d, H, (hipStream_t)stream);
+}
+
+extern "C" int emage_qm_attention(int dtype, const emage_qm_attention_problem* problem, int T, int Tk, int d, int H, void* stream) {
+    return qm_attention_impl(dtype, problem, problem ? 1 : 0, T, Tk, d, H, (hipStream_t)stream);
+}
+
+extern "C" int emage_qm_attention_grouped(int dtype, const emage_qm_attention_problem* problems, int n_problems, int T, int Tk, int d, int H, void* stream) {
+    return qm_attention_impl(dtype, problems, n_problems, T, Tk, d, H, (hipStream_t)stream);
 }

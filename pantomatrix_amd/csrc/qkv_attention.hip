@@ -3,7 +3,7 @@
 // (which reads them back).  One workgroup per (clip, head): at T = 64 the projection's row tile IS one clip, and everything the attention
 // of head h needs are the 3 x 192 output columns q_h, k_h, v_h of those 64 rows.
 //   * K-loop: gemm_h2_tile (h2_tile.h) unchanged on a 64 x 576 block tile — the 576 W rows are the three 192-row slices of head h
-//     (SEG3) — 8 waves of 16 x 288 (WTM = 16 as in config 100, so the folded LayerNorm's statistics merge in the same order);
+//     (SEGS = 3) — 8 waves of 16 x 288 (WTM = 16 as in config 100, so the folded LayerNorm's statistics merge in the same order);
 //   * epilogue: the arithmetic of h2_tile_epilogue for these columns (o_scale, the LayerNorm fold, bias; q / k as the row-major float32
 //     path computes them, v as the V^T path does), then split into fp16 planes straight into the operand ring, in the layout
 //     attn_stage_kv gives K / V^T (and K's layout for Q);
@@ -110,7 +110,7 @@ __global__ __launch_bounds__(QA_THREADS, 1) void qkv_attn_kernel(QkvAttnGroup g)
             }
         });
     };
-    gemm_h2_tile<QA_BM, QA_BN, QA_WM, QA_WN, QA_NS, false, false, 1, true, false, true>(p, b * QA_T, h * QA_HD, smem, 0, epi);
+    gemm_h2_tile<QA_BM, QA_BN, QA_WM, QA_WN, QA_NS, false, false, 1, true, false, 3>(p, b * QA_T, h * QA_HD, smem, 0, epi);
     __syncthreads();
     const int wave = (int)(threadIdx.x >> 6);
     if (wave >= QA_T / 16) return;

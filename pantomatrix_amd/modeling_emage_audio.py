@@ -98,6 +98,12 @@ class _EmageModule(torch.nn.Module):
                                                # False = the two launches (same bits)
         self.fuse_cross_attention = True       # the same for the cross-attention sites: the q projection and the attention on the layer's memory
                                                # K / V^T run as ONE launch (ops.q_attention: q never leaves the chip); False = the two launches (same bits)
+        self.compose_memory = True             # EMAGE_H2 eval forward (ignored elsewhere): each decoder stack's memory projection (`audio_body_motion_proj`,
+                                               # `audio_face_motion_proj`) is COMPOSED with the stack's K / V projections at packing time (`_Packed._compose`):
+                                               # the K / V contraction runs on the 256 / 512 feature columns and the projected memory is never computed;
+                                               # False = the two Linear layers one after the other (re-associates the arithmetic: parity-green on every golden)
+        self.fuse_memory_kv = True             # ... and each stack cross-attention site that `fuse_cross_attention` fuses computes its K / V^T itself from
+                                               # the feature image (ops.qm_attention: no K / V^T tensor); False = one composed K / V launch per stack (same bits)
         self.group_face_body = False           # forward(): the 4 face decoder layers walk in lock step with the first 4 audio cross-attention
                                                # layers of the body (same shapes, different weights: 6 contractions per layer pair share
                                                # launches) instead of running on two stream lanes; same bits (A/B switch)
@@ -271,15 +277,16 @@ class _EmageModule(torch.nn.Module):
         want_h2 = self._dt == F16X3 and self._supports_h2 and (self.split_acts if h2 is None else h2)
         dt = H2 if want_h2 else self._dt
         stamp = self._version_stamp()
+        compose = bool(self.compose_memory) and dt == H2 and not train_only        # eval sets only: a training forward never reads the composed operands
         if (self._packed is None or self._packed.device != dev or self._packed.dt != dt or self._packed.stamp != stamp
-                or (self._packed.train_only and not train_only)):
+                or (not train_only and (self._packed.train_only or self._packed.compose != compose))):
             capturing = dev.type == "cuda" and torch.cuda.is_current_stream_capturing()
             for attempt in (0, 1):
                 # the scale cache is keyed by packing ORDER: a train-only set (fewer operands) keeps its own
                 ckey = (str(dev), dt, bool(train_only))
                 cache = self.__dict__.setdefault("_scale_caches", {}).setdefault(ckey, {})
                 pk = _Packed(self._flat_params(), dev, dt, cache)
-                pk.stamp, pk.train_only = stamp, bool(train_only)
+                pk.stamp, pk.train_only, pk.compose = stamp, bool(train_only), compose
                 self._pack(pk)
                 pk.finish_range_check()
                 # a weight that left the range its cached power-of-two scale was chosen for (it grew / shrank 4x since the first packing, or
@@ -313,6 +320,7 @@ class _Packed:
         self.scale_cache = {} if scale_cache is None else scale_cache
         self._n_operands = 0
         self.stamp = None            # `_EmageModule._version_stamp()` of the parameters this set was packed from
+        self.compose = False         # the set holds the composed memory operands (`_EmageModule.compose_memory`; EMAGE_H2 eval sets only)
         self.train_only = False      # packed for the training forward alone (`_engine(train_only=True)`): eval-only operands may be missing
         # int32 device counter of operands packed with a CACHED scale whose max |w * scale| has left [2^10, 2^14) (chosen into
         # [2^12, 2^13): the fp16 hi plane overflows at 2^16); None until such a packing happens
@@ -371,6 +379,12 @@ class _Packed:
         w2 = wcat * g[None, :]
         return w2, (bcat.double() + wcat.double() @ be.double()).float(), w2.double().sum(dim=1).float().contiguous()
 
+    def _compose(self, wcat, bcat, proj):
+        """The Linear `proj` in front of this one with nothing between them, composed into it: (a Wp^T + bp) W^T + b = a (W Wp)^T + (W bp + b)
+        -> (W Wp, W bp + b), both products in float64 from the float32 parameters and rounded to float32 once."""
+        wp, bp = self.p[proj + ".weight"].double(), self.p[proj + ".bias"].double()
+        return (wcat.double() @ wp).float().contiguous(), (wcat.double() @ bp + bcat.double()).float().contiguous()
+
     @staticmethod
     def _stack(ts):
         """torch.cat(ts, 0) — or, when the pieces are consecutive row blocks of ONE contiguous tensor in memory order (the q / k / v blocks of an
@@ -415,9 +429,10 @@ class _Packed:
             self.origin[key] = [(nm + ".weight", nm + ".bias", rows[i] if rows is not None else slice(0, self.p[nm + ".weight"].shape[0]))
                                 for i, nm in enumerate(names)]
 
-    def in_proj(self, key, names, parts, fold=None):
+    def in_proj(self, key, names, parts, fold=None, compose=None):
         """Row blocks of packed in_proj weights: parts e.g. "qkv", "q", "kv"; several layers stack as
-        [K_0..K_n | V_0..V_n] so that one GEMM emits every layer's K and V^T (V columns last).  fold: see `linear`."""
+        [K_0..K_n | V_0..V_n] so that one GEMM emits every layer's K and V^T (V columns last).  fold: see `linear`.  compose: the name of the
+        Linear whose output is this projection's ONLY consumer-side operand — the entry then contracts that Linear's input (`_compose`); eval only."""
         d = self.p[names[0] + ".in_proj_weight"].shape[1]
         sl = {"q": slice(0, d), "k": slice(d, 2 * d), "v": slice(2 * d, 3 * d)}
         ws, bs = [], []
@@ -431,7 +446,11 @@ class _Packed:
         wcat = self._stack(ws).float()
         bcat = self._bias(bs)
         extra = {}
-        if fold is not None:
+        if compose is not None:
+            assert fold is None
+            wcat, bcat = self._compose(wcat, bcat, compose)
+            k_real = wcat.shape[1]
+        elif fold is not None:
             wcat, bcat, c = self._fold_norm(wcat, bcat, fold)
             extra = dict(c=c, norm=fold)
         else:
@@ -529,6 +548,8 @@ class _Ctx:
         # fold_ln (EMAGE_H2 with H2 residuals; `model.fold_layernorm`): interior LayerNorms of the post-norm layers are FOLDED into the
         # contractions around them (include/emage_hip.h: emage_gemm_problem) — no LayerNorm launch, no normalised tensor
         self.fold_ln = bool(fold_ln) and self.h2res
+        # compose (`model.compose_memory`): the set holds the stacks' composed memory K / V operands — the forward contracts the feature images
+        self.compose = bool(pk.compose) and self.h2
 
     def lo(self, m, n):
         return torch.empty(m, n, dtype=self.tdt, device=self.dev)
@@ -1130,6 +1151,10 @@ class _WavEncoderMixin:
 # ======================================================================================
 # EmageAudioModel  (M:207-490)
 # ======================================================================================
+# the stacks' memory K / V operands composed with the memory projection in front of them (`compose_memory`): key "<kv entry>@<projection>"
+_BODY_KV, _FACE_KV = "cross.kv_all@audio_body_motion_proj", "face.kv_all@audio_face_motion_proj"
+
+
 class EmageAudioModel(_WavEncoderMixin, _EmageModule):
     config_class = EmageAudioConfig
     base_model_prefix = "emage_audio"
@@ -1174,6 +1199,9 @@ class EmageAudioModel(_WavEncoderMixin, _EmageModule):
             self._pack_folds(pk, f"body_motion_decoder_{p}.layers.0", cross=True)
         if not pk.train_only:        # eval-mode WavEncoders (BatchNorms folded into the convolutions); training packs the raw ones (`_train_pack`)
             self._pack_wav_encoders(pk, ("audio_encoder_face", "audio_encoder_body"))
+        if pk.compose:               # behind every other operand, as the folds: the packing order of the plain entries (the scale cache's key) does not move
+            pk.in_proj(_BODY_KV, [n + ".multihead_attn" for n in cross], "kv", compose="audio_body_motion_proj")
+            pk.in_proj(_FACE_KV, [n + ".multihead_attn" for n in face], "kv", compose="audio_face_motion_proj")
         pk.w["pe"] = pk.f32("position_embeddings.pe")[0].contiguous()                 # (2*pose_length, d)
         pk.w["spk_body"] = pk.f32("speaker_embedding_body.weight")
         pk.w["spk_face"] = pk.f32("speaker_embedding_face.weight")
@@ -1278,15 +1306,34 @@ class EmageAudioModel(_WavEncoderMixin, _EmageModule):
         x = self._ln(cx, name + ".norm1", self._self_attn(cx, name, x, b, t, stats=cx.fold_ln))
         return self._ln(cx, name + ".norm2", self._ffn(cx, name, x), add=post_add, want_f32=want_f32)
 
-    def _decoder_layer(self, cx, name, x, b, t, mem_k, mem_vt, vt_rows, tk, post_add=None, fold_out=False):
+    def _memory_site(self, cx, b, t, tk):
+        """Whether the cross-attention sites of the two decoder stacks compute their memory K / V^T themselves (`ops.qm_attention`): the composed
+        operands are packed, the site is one that `_fused_cross_attn` fuses, and the feature widths are ones the kernel takes."""
+        d, h = self.config.hidden_size, spec.N_HEAD
+        if not (cx.compose and self.fuse_memory_kv and cx.dev.type == "cuda" and self._fused_cross_attn(cx, b, t, tk, d, h)):
+            return False
+        return all(cx.pk.w[k]["cp"] <= d for k in (_BODY_KV, _FACE_KV))
+
+    def _decoder_layer(self, cx, name, x, b, t, mem_k, mem_vt, vt_rows, tk, post_add=None, fold_out=False, mem_site=None):
         """nn.TransformerDecoderLayer, post-norm, ReLU, no masks.  x: _X; mem_k: (B*Tk, ld) view of this
         layer's projected memory keys; mem_vt: view at this layer's first row of a (B, vt_rows, Tp) V^T buffer.
         `fold_ln`: norm1 / norm2 are folded into the contractions around them; fold_out: norm3 too — the result is then an `_X` with
-        `.ln` set, which only the next layer of the same stack can take."""
+        `.ln` set, which only the next layer of the same stack can take.
+        mem_site (`_memory_site`; mem_k / mem_vt are then None): (memory feature image, key of the stack's composed K / V operand, layers in it,
+        this layer's index) — the site computes its K / V^T itself."""
         d, h = self.config.hidden_size, spec.N_HEAD
         fold = cx.fold_ln
         x = self._ln(cx, name + ".norm1", self._self_attn(cx, name, x, b, t, stats=fold))
-        if self._fused_cross_attn(cx, b, t, tk, d, h):
+        if mem_site is not None:
+            att = cx.lo(b * t, d)
+            key = name + ".ca.q"
+            e = cx.pk.w[key] if x.ln is None else cx.pk.w[key + "@" + x.ln[1]]
+            mem, kv_key, n_layers, layer = mem_site
+            kv = cx.pk.w[kv_key]
+            assert e["cp"] == d and e["n"] == d and kv["n"] == 2 * n_layers * d
+            ops.qm_attention(cx.h2dt, x.a, e["w"], e["b"], mem, kv["w"], kv["b"], n_layers, layer, att, b, w_scale=e.get("ws", 1.0),
+                             wkv_scale=kv.get("ws", 1.0), ln=None if x.ln is None else (x.ln[0], e["c"]))
+        elif self._fused_cross_attn(cx, b, t, tk, d, h):
             att = cx.lo(b * t, d)
             key = name + ".ca.q"
             e = cx.pk.w[key] if x.ln is None else cx.pk.w[key + "@" + x.ln[1]]
@@ -1317,7 +1364,8 @@ class EmageAudioModel(_WavEncoderMixin, _EmageModule):
     def _audio_features(self, cx, audio, b, t, use_audio, fk, lane_face, lane_body, nwin=1, hop=0, win_len=None):
         """Everything that depends on the waveform only (M:275-281, 303 and the cross-attention K/V projections):
         both WavEncoders, `audio_body_motion_proj` and the 8 layers' memory K / V^T.  Returns a dict
-        {memcat (B*T, audio_f+motion_f) with the face features in its first audio_f columns, bk, bvt, ta}.
+        {memcat (B*T, audio_f+motion_f) with the face features in its first audio_f columns, bk, bvt, abody, ta}; `compose_memory`: abody is the
+        image of the body features, and bk / bvt stay None where the sites compute their own (`_memory_site`).
         Runs on two stream lanes of `fk`; `inference()` calls it once for ALL full windows of a batch: `audio` is then
         the whole-clip tensor, `nwin` windows of `win_len` samples every `hop` samples, b = nwin * clips sequences."""
         c = self.config
@@ -1327,7 +1375,7 @@ class EmageAudioModel(_WavEncoderMixin, _EmageModule):
         if ta < t:
             raise RuntimeError(f"Sizes of tensors must match: audio features {ta} frames vs motion {t} frames")
         m = b * t
-        feats = dict(memcat=cx.lo(m, af + mf), bk=None, bvt=None, ta=ta)            # [audio2face | body_hint_face] (M:288)
+        feats = dict(memcat=cx.lo(m, af + mf), bk=None, bvt=None, abody=None, ta=ta)            # [audio2face | body_hint_face] (M:288)
         fused0 = self._wav_block0_fused()
         wkw = dict(wav=audio, nwin=nwin, hop=hop, win_len=win_len) if fused0 else {}
         y0 = None
@@ -1346,10 +1394,22 @@ class EmageAudioModel(_WavEncoderMixin, _EmageModule):
             if use_audio:
                 if cx.h2:
                     a_body = ops.cast_pad(cx.h2dt, a_body, a_body.shape[1])
-                mem_body, _ = cx.gemm(a_body, "audio_body_motion_proj")                 # M:303
-                feats["bk"], feats["bvt"] = self._memory_kv(cx, "cross.kv_all", mem_body, b, ta, nc)
+                if cx.compose:      # the projection (M:303) is part of the K / V operand: the sites, or one K / V launch, contract the features
+                    feats["abody"] = a_body
+                    if not self._memory_site(cx, b // nwin, t, ta):
+                        feats["bk"], feats["bvt"] = self._memory_kv(cx, _BODY_KV, a_body, b, ta, nc)
+                else:
+                    mem_body, _ = cx.gemm(a_body, "audio_body_motion_proj")             # M:303
+                    feats["bk"], feats["bvt"] = self._memory_kv(cx, "cross.kv_all", mem_body, b, ta, nc)
         feats["_keep"] = (y0, a_face, a_body)       # cross-lane operands stay alive until the caller's join
         return feats
+
+    @staticmethod
+    def _feats_of_clips(feats, clip0, n, t):
+        """The features `_audio_features` computed for many sequences, cut to sequences [clip0, clip0 + n) of t frames (row views)."""
+        ta = feats["ta"]
+        rows = lambda k, per: None if feats.get(k) is None else feats[k][clip0 * per:(clip0 + n) * per]
+        return dict(memcat=rows("memcat", t), ta=ta, bk=rows("bk", ta), bvt=rows("bvt", 1), abody=rows("abody", ta))
 
     def _speaker_tables(self, cx, speaker_id, b, t):
         """Speaker / positional tables of a (B,T) window (M:285-286, P:341-343): they depend on the speaker ids and T
@@ -1417,6 +1477,7 @@ class EmageAudioModel(_WavEncoderMixin, _EmageModule):
         with Fork(dev, 3, self.concurrent) as fk:
             feats = _audio_feats if _audio_feats is not None else self._audio_features(cx, audio, b, t, use_audio, fk, 1, 2)
             memcat, bk, bvt, ta = feats["memcat"], feats["bk"], feats["bvt"], feats["ta"]
+            site = use_audio and bk is None and self._memory_site(cx, b, t, ta)       # the stack sites compute their own K / V^T
 
             with fk.lane(0):
                 # masked motion -> spatial hints (M:267-273)
@@ -1432,19 +1493,30 @@ class EmageAudioModel(_WavEncoderMixin, _EmageModule):
             # face branch (M:288-294) on lane 1, once the hints (lane 0) are there
             fk.after(1, 0)
             def face_layer(i, face):
+                if site:
+                    return self._decoder_layer(cx, f"face_motion_decoder.layers.{i}", face, b, t, None, None, nf * d, t, fold_out=i < nf - 1,
+                                               mem_site=(memcat, _FACE_KV, nf, i))
                 return self._decoder_layer(cx, f"face_motion_decoder.layers.{i}", face, b, t,
                                            fkk[:, i * d:(i + 1) * d], fvt[:, i * d:], nf * d, t, fold_out=i < nf - 1)
 
             def cross_layer(i, x, base):
+                kw = dict(post_add=base.r if i == nc - 1 else None, fold_out=i < nc - 1)                      # motion_fea + cross
+                if site:
+                    return self._decoder_layer(cx, f"audio_motion_cross_attn.layers.{i}", x, b, t, None, None, nc * d, ta,
+                                               mem_site=(feats["abody"], _BODY_KV, nc, i), **kw)
                 return self._decoder_layer(cx, f"audio_motion_cross_attn.layers.{i}", x, b, t,
-                                           bk[:, i * d:(i + 1) * d], bvt[:, i * d:], nc * d, ta,
-                                           post_add=base.r if i == nc - 1 else None, fold_out=i < nc - 1)     # motion_fea + cross
+                                           bk[:, i * d:(i + 1) * d], bvt[:, i * d:], nc * d, ta, **kw)
 
             # the two decoder stacks side by side: lock step (one lane, shared launches) or two lanes
             paired = self.group_face_body and self.group_gemms and use_audio and dev.type == "cuda" and nf < nc
             with fk.lane(1):
-                mem_face, _ = cx.gemm(memcat, "audio_face_motion_proj")
-                fkk, fvt = self._memory_kv(cx, "face.kv_all", mem_face, b, t, nf)
+                if site:
+                    fkk = fvt = None
+                elif cx.compose:
+                    fkk, fvt = self._memory_kv(cx, _FACE_KV, memcat, b, t, nf)
+                else:
+                    mem_face, _ = cx.gemm(memcat, "audio_face_motion_proj")
+                    fkk, fvt = self._memory_kv(cx, "face.kv_all", mem_face, b, t, nf)
                 face = face0
                 if not paired:
                     for i in range(nf):
@@ -1460,6 +1532,9 @@ class EmageAudioModel(_WavEncoderMixin, _EmageModule):
             if use_audio:
                 fk.after(0, 2)
                 base = x
+                if bk is None and not site:     # features hoisted for a batch that takes the sites, consumed by one that does not: the composed K / V launch here
+                    with fk.lane(0):
+                        bk, bvt = self._memory_kv(cx, _BODY_KV, feats["abody"], b, ta, nc)
             if paired:
                 fk.after(0, 1)                  # the face memory (lane 1) feeds the lock-step walk on lane 0
                 pair = {}
@@ -1666,9 +1741,7 @@ class EmageAudioModel(_WavEncoderMixin, _EmageModule):
             def window_feats(i):
                 if hoisted is None:
                     return None
-                ta, mrows = hoisted["ta"], bs * window
-                return dict(memcat=hoisted["memcat"][i * mrows:(i + 1) * mrows], ta=ta,
-                            bk=hoisted["bk"][i * bs * ta:(i + 1) * bs * ta], bvt=hoisted["bvt"][i * bs:(i + 1) * bs])
+                return self._feats_of_clips(hoisted, i * bs, bs, window)
 
             def run_window(start, end, need_seed, feats=None):
                 nonlocal open_fork

@@ -61,9 +61,11 @@ class _PendingGuard(torch.utils._python_dispatch.TorchDispatchMode):
         return func(*args, **kwargs)
 
 
-def _entry(name, op, args):
+def _entry(name, op, args, operator=None):
     meta = dict(_META)
     _META.clear()
+    if operator is not None:
+        meta["op"] = operator
     tr = _TRACE[0]
     if tr is not None:
         meta["tag"] = tr.tag()
@@ -75,20 +77,29 @@ def _fire(kind, entries, launch):
     return tr.fire(kind, entries, launch) if tr is not None else launch()
 
 
-def _op(name, schema):
+def _operator(entry):
+    """The operator a recorded call belongs to: its own name, unless it was registered as a member of another operator's family."""
+    return entry[3].get("op", entry[0])
+
+
+def _op(name, schema, family=None):
     """Register `emage::name` with `schema`; the decorated function is its CUDA implementation.  Returns the callable the public
-    functions below use: the operator itself, or — inside a `lockstep()` chain — a recording of the call."""
+    functions below use: the operator itself, or — inside a `lockstep()` chain — a recording of the call.
+    family: the operator whose name this one's calls carry to the trace hook and the launch logs — a second form of the same kind of launch
+    (`qm_attention`: a cross-attention site, as `q_attention`); the entry keeps its own name in meta["op"] (`_operator`), which is what
+    selects its grouped twin."""
     def deco(fn):
         _LIBRARY.define(name + schema)
         _LIBRARY.impl(name, fn, "CUDA")
         op = getattr(torch.ops.emage, name)
+        shown = family or name
 
         def call(*args):
-            e = _entry(name, op, args)
+            e = _entry(shown, op, args, name if family else None)
             rec = _RECORDER[0]
             if rec is not None:
                 return rec.record(e)
-            return _fire(name, [e], lambda: op(*args))
+            return _fire(shown, [e], lambda: op(*args))
 
         call.op = op
         return call
@@ -139,14 +150,14 @@ class Lockstep:
 
     @staticmethod
     def _groupable(entry):
-        return entry[0] in _GROUPED and entry[2][0] & 0xff == H2
+        return _operator(entry) in _GROUPED and entry[2][0] & 0xff == H2
 
     def _issue(self, entry):
         _fire(entry[0], [entry], lambda: entry[1](*entry[2]))
         self.launches.append((entry[0], 1))
 
     def _issue_group(self, entries):
-        kind, issue = _GROUPED[entries[0][0]]
+        kind, issue = _GROUPED[_operator(entries[0])]
         _fire(kind, entries, lambda: issue(entries))
         self.launches.append(("group", len(entries)))
         self.groups.append(entries)
@@ -165,10 +176,10 @@ class Lockstep:
                     ptr[ci] += 1
             if not heads:
                 break
-            # heads of one kind (contractions / fused self-attention sites) share a grouped call, in the order of their first head
+            # heads of one operator (contractions / fused self-attention sites / ...) share a grouped call, in the order of their first head
             kinds = {}
             for e in heads:
-                kinds.setdefault(e[0], []).append(e)
+                kinds.setdefault(_operator(e), []).append(e)
             for same in kinds.values():
                 if len(same) == 1 or not self.enabled:
                     for e in same:
@@ -789,10 +800,50 @@ def q_attention(dtype, a, w, bias, k, vt, vt_rows, out, b, *, w_scale, a_scale=N
                  float(act_scale(dtype) if a_scale is None else a_scale), float(ln_eps) if ln is not None else 0.0)
 
 
+# The cross-attention site of a decoder STACK (include/emage_hip.h: emage_qm_attention): the layer's memory K / V^T are computed inside the launch
+# from the memory feature image and the stack's composed k|v operand — no K / V^T tensor exists
+_QM_TABLE = _ProblemTable(_lib.QmAttentionProblem)
+
+
+def _qm_fields(dtype, a, w, bias, ln_stats, ln_c, mem, wkv, bias_kv, out, b, km, kv_layers, kv_layer, w_scale, wkv_scale, a_scale, ln_eps):
+    return dict(A=_ptr(a), W=_ptr(w), bias=_ptr(bias), ln_stats=_ptr(ln_stats), ln_c=_ptr(ln_c), mem=_ptr(mem), Wkv=_ptr(wkv), bias_kv=_ptr(bias_kv),
+                out=_ptr(out), lda=_ld(a), ldm=_ld(mem), km=km, kv_layers=kv_layers, kv_layer=kv_layer, ldo=_ld(out), B=b,
+                a_scale=a_scale, w_scale=w_scale, wkv_scale=wkv_scale, ln_eps=ln_eps)
+
+
+@_op("qm_attention", "(int dtype, Tensor a, Tensor w, Tensor bias, Tensor? ln_stats, Tensor? ln_c, Tensor mem, Tensor wkv, Tensor bias_kv, Tensor(a!) out, "
+                     "int b, int km, int kv_layers, int kv_layer, float w_scale, float wkv_scale, float a_scale, float ln_eps) -> ()",
+     family="q_attention")           # a fused cross-attention site: traced and logged with the others
+def _qm_attention(dtype, *args):
+    arr, _ = _QM_TABLE.array(*_QM_TABLE.pack(_qm_fields(dtype, *args)))
+    check(_lib.load().emage_qm_attention(dtype, arr, _QKV_T, _QKV_T, _QKV_D, _QKV_H, _stream()), "qm_attention")
+
+
+@_op("qm_attention_grouped", "(int dtype, Tensor(a!)[] tensors, int[] desc, float[] scales) -> ()")
+def _qm_attention_grouped(dtype, tensors, desc, scales):
+    arr, n = _QM_TABLE.array(desc, scales)
+    check(_lib.load().emage_qm_attention_grouped(dtype, arr, n, _QKV_T, _QKV_T, _QKV_D, _QKV_H, _stream()), "qm_attention_grouped")
+
+
+def qm_attention(dtype, a, w, bias, mem, wkv, bias_kv, kv_layers, kv_layer, out, b, *, w_scale, wkv_scale, a_scale=None, ln=None, ln_eps=1e-5):
+    """One cross-attention site of a decoder stack in one launch (include/emage_hip.h: emage_qm_attention): as `q_attention`, with the layer's
+    memory keys / values computed inside the launch — `mem` (B*64, ldm) is the EMAGE_H2 image of the memory features (its first wkv.shape[1]
+    columns are contracted), `wkv` / `bias_kv` / `wkv_scale` the packed (2 * kv_layers * 768, km) operand [K_0 .. | V_0 ..] of the whole stack and
+    `kv_layer` this site's layer in it — bit-identical to `gemm` (K float32, V^T) on `mem` + `q_attention`.
+    Inside a `lockstep()` the sites at the heads of the chains share grouped launches."""
+    _dev(a)
+    ln_stats, ln_c = ln if ln is not None else (None, None)
+    km = int(wkv.shape[1])
+    assert wkv.shape[0] == 2 * kv_layers * _QKV_D and bias_kv.numel() == wkv.shape[0] and mem.shape[0] >= b * _QKV_T and mem.shape[1] >= km
+    _qm_attention(dtype, a, w, bias, ln_stats, ln_c, mem, wkv, bias_kv, out, int(b), km, int(kv_layers), int(kv_layer), float(w_scale), float(wkv_scale),
+                  float(act_scale(dtype) if a_scale is None else a_scale), float(ln_eps) if ln is not None else 0.0)
+
+
 # recorded operator -> (the kind its grouped calls carry to the trace hook, recorded entries -> those calls)
 _GROUPED = {"gemm": _grouped("gemm_grouped", _GEMM_TABLE, _gemm_fields, _gemm_grouped),
             "qkv_attention": _grouped("qkv_attention_grouped", _QKV_TABLE, _qkv_fields, _qkv_attention_grouped, _QKV_MAXG),
-            "q_attention": _grouped("q_attention_grouped", _QA_TABLE, _qa_fields, _q_attention_grouped, _QKV_MAXG)}
+            "q_attention": _grouped("q_attention_grouped", _QA_TABLE, _qa_fields, _q_attention_grouped, _QKV_MAXG),
+            "qm_attention": _grouped("qm_attention_grouped", _QM_TABLE, _qm_fields, _qm_attention_grouped, _QKV_MAXG)}
 
 
 @_op("wav_conv_in", "(int dtype, Tensor wav, Tensor w, Tensor? bias, Tensor? slope, Tensor(a!) out, int lout, int stride, int pad, "

@@ -452,8 +452,7 @@ class RecordingRunner:
                     n, k0 = u.hi - u.lo, u.seq - s0
                     f = None
                     if feats is not None:
-                        ta = feats["ta"]
-                        f = dict(memcat=feats["memcat"][k0 * w:(k0 + n) * w], ta=ta, bk=feats["bk"][k0 * ta:(k0 + n) * ta], bvt=feats["bvt"][k0:k0 + n])
+                        f = model._feats_of_clips(feats, k0, n, w)
                     row0 = u.lo if self.per_recording_ids else 0
                     net = model.forward(win[k0:k0 + n], self.speaker_id[row0:row0 + n], self.tmpl_motion[:n], self.tmpl_mask[:n], use_audio=True,
                                         _audio_feats=f, _tables=self._sliced_tables(tables, row0, n), _lean=True, _seed=self.seeds[u.lo:u.hi])

@@ -10,14 +10,45 @@
 namespace emage_dev {
 
 // the argument block of one launch, by value (kernarg segment): the sites' arguments and the running sum of their blocks (B H); the unused
-// entries repeat p[0].  A block finds its site by comparing its (XCD-remapped) id with blk_end — that scan is written out in each kernel
-// (gemm_h2.hip: gemm_h2_group_kernel)
+// entries repeat p[0].  A block finds its site with site_block.
 template <class P, int G> struct SiteGroup {
     static constexpr int MAXG = G;
     P p[G];
     int blk_end[G];
     int n, total;
 };
+
+// This block's site in the group, and its clip b and head h (of H) there.  XCD-aware order over the whole grid (gemm_h2.hip:
+// gemm_h2_group_kernel): each XCD walks a contiguous run of (clip, head) blocks, heads fastest — the heads of a clip share A.
+template <int H, class P, int G> __device__ __forceinline__ const P& site_block(const SiteGroup<P, G>& g, int& b, int& h) {
+    const int bid = xcd_run_order((int)blockIdx.x, g.total);
+    int pi = 0;
+#pragma unroll
+    for (int i = 0; i < G - 1; ++i) pi += (i + 1 < g.n && bid >= g.blk_end[i]) ? 1 : 0;
+    pi = __builtin_amdgcn_readfirstlane(pi);
+    const int t = bid - (pi ? g.blk_end[pi - 1] : 0);
+    b = t / H;
+    h = t - b * H;
+    return g.p[pi];
+}
+
+// What a site's epilogue stages for one accumulator: emage_gemm's float32 value of that column, operation for operation (no contraction of
+// a * b + c in this build), from operands the kernel has already loaded.  The projection's value in front of its bias: o_scale, then the
+// folded LayerNorm (fold: wave-uniform) ...
+__device__ __forceinline__ float site_x(const float acc, const float os, const bool fold, const float rs, const float mu, const float c) {
+    float x = acc * os;
+    if (fold) x = rs * (x - mu * c);
+    return x;
+}
+// ... as the row-major epilogue ends it (h2_tile_epilogue with no slope and no residual: leaky(., 1), + 0) — q, k
+__device__ __forceinline__ float site_row_value(const float x, const float bias) {
+    float y = x + bias;
+    y = leaky(y, 1.f);
+    y += 0.f;
+    return y;
+}
+// ... and as the V^T epilogue does — v
+__device__ __forceinline__ float site_vt_value(const float x, const float bias) { return leaky(x + bias, 1.f); }
 
 // The refusals every site shares, on the fields every site's problem struct carries (A, W, bias, out, lda, ldo, B, the scales, the LayerNorm
 // fold): EMAGE_H2 only (`dtype` after h2_dtype), operands present and 16-byte aligned, row pitches that hold d columns in whole h2 groups,

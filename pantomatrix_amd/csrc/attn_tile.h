@@ -83,7 +83,49 @@ template <int HD, int NT> struct AttnLds {
     static constexpr int VS = NT / 2;                     // contraction steps of P V (32 keys each)
     static constexpr int VROW = VS * 4 * 32 + 16;         // bytes per staged V^T row (one d)
     static constexpr int K_BYTES = NKEY * KROW, V_BYTES = HD * VROW, BYTES = K_BYTES + V_BYTES;
+
+    // THE layout — attn_stage_kv, attn_tile's fragment reads and the fused sites' epilogues (attn_store_*) all address the planes through these.
+    static constexpr int CELL = 32, LO = 16;              // a row is an array of cells [8 fp16 hi | 8 fp16 lo]; a value's lo half lies LO bytes behind its hi half
+    // byte offset inside a staged row of (the hi half of) contraction index x — a head column of a K / Q row, a key of a V^T row
+    static constexpr int cell_off(int x) { return (x >> 5) * 128 + ((x & 15) >> 2) * 32 + (((x & 31) >> 4) * 4 + (x & 3)) * 2; }
+    // ... of the cell lane group fg reads at contraction step `step` (cell 4 step + fg): x = 32 step + 4 fg + r, then 32 step + 16 + 4 fg + r
+    static constexpr int frag_off(int step, int fg) { return (step * 4 + fg) * CELL; }
+    // H2OUT order of the V^T rows: the d that staged row j (operand row fr of d tile dt) holds, and the staged row of d — a lane's
+    // accumulators of a PAIR of d tiles are then 8 consecutive d
+    static constexpr int d_of_row(int j) {
+        const int dt = j >> 4, fr = j & 15;
+        return 32 * (dt >> 1) + 4 * (dt & 1) + 8 * (fr >> 2) + (fr & 3);
+    }
+    static constexpr int row_of_d(int d) { return 16 * (2 * (d >> 5) + ((d >> 2) & 1)) + 4 * ((d & 31) >> 3) + (d & 3); }
 };
+
+// The proof, on the instantiation the fused sites use (a slip is a compile error, not wrong bits on the GPU)
+constexpr bool attn_layout_proof() {
+    using L = AttnLds<192, 4>;
+    bool ok = true;
+    // cell_off maps a row's n columns (a V^T row's n keys) one-to-one onto the 2-byte slots of the hi halves, inside the row's cells
+    auto one_to_one = [&](const int n, const int bytes) {
+        bool used[L::KROW / 2] = {};
+        for (int x = 0; x < n; ++x) {
+            const int o = L::cell_off(x);
+            ok = ok && o % 2 == 0 && (o & L::LO) == 0 && o + L::LO + 2 <= bytes && !used[o / 2];
+            used[o / 2] = true;
+        }
+    };
+    one_to_one(192, L::KROW - 16);
+    one_to_one(64, L::VROW - 16);
+    // ... and puts the eight values of a fragment into the cell that fragment's read takes, in operand order
+    for (int step = 0; step < L::KS; ++step)
+        for (int fg = 0; fg < 4; ++fg)
+            for (int r = 0; r < 8; ++r) ok = ok && L::cell_off(32 * step + 16 * (r >> 2) + 4 * fg + (r & 3)) == L::frag_off(step, fg) + 2 * r;
+    // what the stores of 8 consecutive columns rely on: the same half of two neighbouring cells; row_of_d adds over the low three bits
+    for (int x = 0; x < 192; x += 8)
+        for (int e = 0; e < 8; ++e) ok = ok && L::cell_off(x + 4) == L::cell_off(x) + L::CELL && L::row_of_d(x + e) == L::row_of_d(x) + L::row_of_d(e);
+    // the two d-row orders are inverses
+    for (int j = 0; j < 192; ++j) ok = ok && L::d_of_row(j) < 192 && L::row_of_d(L::d_of_row(j)) == j && L::d_of_row(L::row_of_d(j)) == j;
+    return ok;
+}
+static_assert(attn_layout_proof(), "AttnLds: cell_off / frag_off / d_of_row / row_of_d describe one layout");
 
 // all NTHR threads of the workgroup (256 in attention.hip); H2OUT selects the permuted d order of attn_tile's V^T rows.  Every global load of the thread is
 // issued before the first split (compile-time trip counts, fully unrolled): one memory latency per workgroup, not one per cell.
@@ -110,8 +152,7 @@ __device__ __forceinline__ void attn_stage_kv(const AttnArgs& p, const int b, co
     for (int i = 0; i < VU; ++i) {
         const int u = i * NTHR + tid;
         const int j = u / (L::VS * 4), cell = u - j * (L::VS * 4), c = cell >> 2, fg = cell & 3;
-        const int dt = j >> 4, fr = j & 15;               // staged row j = operand row fr of d tile dt
-        const int drow = H2OUT ? 32 * (dt >> 1) + 4 * (dt & 1) + 8 * (fr >> 2) + (fr & 3) : j;
+        const int drow = H2OUT ? L::d_of_row(j) : j;
         const float* src = V + ((long)b * p.vt_rows + h * HD + drow) * p.ldvt + 32 * c + 4 * fg;
         v0[i] = *(const uint4*)src;
         v1[i] = *(const uint4*)(src + 16);
@@ -133,18 +174,51 @@ __device__ __forceinline__ void attn_stage_kv(const AttnArgs& p, const int b, co
         const int u = i * NTHR + tid;
         const int key = u / (L::KS * 4), cell = u - key * (L::KS * 4);
         const SplitF16 f = split_chunks(k0[i], k1[i], p.h2s);
-        unsigned char* dst = smem + key * L::KROW + cell * 32;
+        unsigned char* dst = smem + key * L::KROW + cell * L::CELL;
         *(h16x8*)dst = f.hi;
-        *(h16x8*)(dst + 16) = f.lo;
+        *(h16x8*)(dst + L::LO) = f.lo;
     }
 #pragma unroll
     for (int i = 0; i < VU; ++i) {
         const int u = i * NTHR + tid;
         const int j = u / (L::VS * 4), cell = u - j * (L::VS * 4);
         const SplitF16 f = split_chunks(v0[i], v1[i], p.h2s);
-        unsigned char* dst = smem + L::K_BYTES + j * L::VROW + cell * 32;
+        unsigned char* dst = smem + L::K_BYTES + j * L::VROW + cell * L::CELL;
         *(h16x8*)dst = f.hi;
-        *(h16x8*)(dst + 16) = f.lo;
+        *(h16x8*)(dst + L::LO) = f.lo;
+    }
+}
+
+// The fused sites' epilogues stage what their projection computed instead of what attn_stage_kv reads: the same split (h2_split8 rounds as
+// split_chunks does) of the same float32 values into the same cells.  Eight values of row fm (a key at `planes` = smem, a query at
+// smem + BYTES), head columns cc .. cc + 7, cc % 8 == 0 — and four, cc % 4 == 0:
+template <class L> __device__ __forceinline__ void attn_store_row8(unsigned char* planes, const int fm, const int cc, const float (&v)[8], const float s) {
+    uint4 hi, lo;
+    h2_split8(v, hi, lo, s);
+    unsigned char* dst = planes + fm * L::KROW + L::cell_off(cc);
+    *(uint2*)dst = make_uint2(hi.x, hi.y);
+    *(uint2*)(dst + L::LO) = make_uint2(lo.x, lo.y);
+    *(uint2*)(dst + L::CELL) = make_uint2(hi.z, hi.w);
+    *(uint2*)(dst + L::CELL + L::LO) = make_uint2(lo.z, lo.w);
+}
+template <class L> __device__ __forceinline__ void attn_store_row4(unsigned char* planes, const int fm, const int cc, const float (&v)[4], const float s) {
+    uint2 hi, lo;
+    h2_split4(v, hi, lo, s);
+    unsigned char* dst = planes + fm * L::KROW + L::cell_off(cc);
+    *(uint2*)dst = hi;
+    *(uint2*)(dst + L::LO) = lo;
+}
+// Eight values of key fm, d columns cc .. cc + 7 (cc % 8 == 0) of V -> the V^T planes at smem + K_BYTES in the H2OUT row order
+template <class L> __device__ __forceinline__ void attn_store_vt8(unsigned char* smem, const int fm, const int cc, const float (&v)[8], const float s) {
+    uint4 hi, lo;
+    h2_split8(v, hi, lo, s);
+    const h2f16x8 hv = __builtin_bit_cast(h2f16x8, hi), lv = __builtin_bit_cast(h2f16x8, lo);
+    unsigned char* col = smem + L::K_BYTES + L::cell_off(fm);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        const int j = L::row_of_d(cc) + L::row_of_d(e);      // = row_of_d(cc + e): one address per lane, the eight rows in the stores' immediates
+        *(_Float16*)(col + j * L::VROW) = hv[e];
+        *(_Float16*)(col + j * L::VROW + L::LO) = lv[e];
     }
 }
 
@@ -195,10 +269,10 @@ __device__ __forceinline__ void attn_tile(const AttnArgs& p, const int b, const 
     uint4 kf[KT][NSTEP];
     // staged fragments (LDSKV): the cell of (row, step, fg) in the layout of attn_stage_kv
     auto lds_frag = [&](const unsigned char* base, int row_bytes, int row, int step) {
-        const unsigned char* c = base + row * row_bytes + (step * 4 + fg) * 32;
+        const unsigned char* c = base + row * row_bytes + AttnLds<HD, NT>::frag_off(step, fg);
         SplitF16 f;
         f.hi = *(const h16x8*)c;
-        f.lo = *(const h16x8*)(c + 16);
+        f.lo = *(const h16x8*)(c + AttnLds<HD, NT>::LO);
         return f;
     };
     auto load_k = [&](int nt, uint4 (&dst)[NSTEP]) {
@@ -213,11 +287,11 @@ __device__ __forceinline__ void attn_tile(const AttnArgs& p, const int b, const 
     }
     // V^T chunk c of d-tile dt: keys {32c + 4g + r} U {32c + 16 + 4g + r} (bf16) / {16c + 4g + r} (fp32), r = 0..3
     static_assert(!H2OUT || (X3 && DSP == 1 && (HD / 16) % 2 == 0), "h2 output: split-f16 form, one wave per query tile, d tiles pair up");
-    // d row of (d tile dt, operand row fr): natural 16 dt + fr; H2OUT: 32 (dt >> 1) + 8 (fr >> 2) + 4 (dt & 1) + (fr & 3)
-    const int vrow0 = H2OUT ? 8 * (fr >> 2) + (fr & 3) : fr;
+    // d row of (d tile dt, operand row fr): natural 16 dt + fr; H2OUT: AttnLds::d_of_row(16 dt + fr), which is d_of_row(16 dt) + d_of_row(fr)
+    const int vrow0 = H2OUT ? AttnLds<HD, NT>::d_of_row(fr) : fr;
     const int voff = ((b * p.vt_rows + h * HD + vrow0) * p.ldvt + fg * 4) * ES;
     const int vstep = 16 * p.ldvt * ES;
-    auto vsoff = [&](int dt) { return H2OUT ? (32 * (dt >> 1) + 4 * (dt & 1)) * p.ldvt * ES : dt * vstep; };
+    auto vsoff = [&](int dt) { return H2OUT ? AttnLds<HD, NT>::d_of_row(16 * dt) * p.ldvt * ES : dt * vstep; };
     static_assert(NDT % DSP == 0, "d tiles split evenly over the DSP waves");
     constexpr int NDW = NDT / DSP;            // d tiles per wave
     constexpr int VT_ = PRE ? NDW : 1;

@@ -78,17 +78,7 @@ __device__ __forceinline__ void q_planes(const GemmArgs& p, const int h, unsigne
     }
     __syncthreads();                               // every wave has read its last fragments of the ring
     const float os = p.o_scale;
-    // the row-major epilogue's float32 value of one accumulator (o_scale, the LayerNorm fold, bias; no slope, no residual: leaky(., 1), + 0)
-    auto value = [&](const float accv, const float c, const float bias, const float mu, const float rs) {
-        float x = accv * os;
-        if (fold) x = rs * (x - mu * c);
-        float y = x + bias;
-        y = leaky(y, 1.f);
-        y += 0.f;
-        return y;
-    };
-    // K's row layout: row fm, cell (cc / 32, (cc % 16) / 4) holds columns 32 s + 4 g + r (planes [0, 4)) and 32 s + 16 + 4 g + r ([4, 8))
-    auto cell = [&](const int fm, const int cc) { return smem + L::BYTES + fm * L::KROW + (cc >> 5) * 128 + ((cc & 15) >> 2) * 32 + ((cc & 31) >> 4) * 8; };
+    auto value = [&](const float accv, const float c, const float bias, const float mu, const float rs) { return site_row_value(site_x(accv, os, fold, rs, mu, c), bias); };
     static_for<2 * NP>([&](auto ic) {
         constexpr int I = decltype(ic)::value / NP, JP = decltype(ic)::value % NP;
         const int fm = wm * 32 + I * 16 + fr;      // frame of this lane's row
@@ -96,14 +86,7 @@ __device__ __forceinline__ void q_planes(const GemmArgs& p, const int h, unsigne
         float v[8];
 #pragma unroll
         for (int e = 0; e < 8; ++e) v[e] = value(e < 4 ? acc[I][2 * JP][e] : acc[I][2 * JP + 1][e - 4], cv[JP][e], bv[JP][e], ln_mu[I], ln_rs[I]);
-        uint4 hi, lo;
-        h2_split8(v, hi, lo, p.h2s);               // split as attn_tile splits them
-        // columns cc .. cc + 3 and cc + 4 .. cc + 7 fill the same half of two neighbouring cells
-        unsigned char* dst = cell(fm, cc);
-        *(uint2*)dst = make_uint2(hi.x, hi.y);
-        *(uint2*)(dst + 16) = make_uint2(lo.x, lo.y);
-        *(uint2*)(dst + 32) = make_uint2(hi.z, hi.w);
-        *(uint2*)(dst + 48) = make_uint2(lo.z, lo.w);
+        attn_store_row8<L>(smem + L::BYTES, fm, cc, v, p.h2s);
     });
     if constexpr (LONE) {
         // the lone fragment (natural W row order): 4 consecutive columns per lane, one half of one cell
@@ -115,27 +98,16 @@ __device__ __forceinline__ void q_planes(const GemmArgs& p, const int h, unsigne
             float v[4];
 #pragma unroll
             for (int e = 0; e < 4; ++e) v[e] = value(acc[I][FN - 1][e], c4[e], b4[e], ln_mu[I], ln_rs[I]);
-            uint2 hi, lo;
-            h2_split4(v, hi, lo, p.h2s);
-            unsigned char* dst = cell(fm, cc);
-            *(uint2*)dst = hi;
-            *(uint2*)(dst + 16) = lo;
+            attn_store_row4<L>(smem + L::BYTES, fm, cc, v, p.h2s);
         });
     }
 }
 
 __global__ __launch_bounds__(CA_THREADS, 1) void q_attn_kernel(QAttnGroup g) {
     __shared__ __attribute__((aligned(128))) unsigned char smem[CA_LDS];
-    // XCD-aware order over the whole grid: each XCD walks a contiguous run of (clip, head) blocks, heads fastest (the four heads of a clip share A)
-    const int bid = xcd_run_order((int)blockIdx.x, g.total);
-    int pi = 0;
-#pragma unroll
-    for (int i = 0; i < CA_MAXG - 1; ++i) pi += (i + 1 < g.n && bid >= g.blk_end[i]) ? 1 : 0;
-    pi = __builtin_amdgcn_readfirstlane(pi);
-    const int t = bid - (pi ? g.blk_end[pi - 1] : 0);
-    const QAttnArgs& q = g.p[pi];
+    int b, h;
+    const QAttnArgs& q = site_block<CA_H>(g, b, h);
     const GemmArgs& p = q.g;
-    const int b = t / CA_H, h = t - b * CA_H;
     const AttnArgs a{nullptr, q.k, q.vt, q.out, 0, q.ldk, q.ldvt, q.vt_rows, q.ldo, p.M / CA_T, CA_H, CA_T, CA_T, 1.0f / sqrtf((float)CA_HD), nullptr, p.h2s, p.h2i};
 
     auto epi = [&](auto& acc, const int, const int wm, const int wn, const int fr, const int fg, const auto& ln_mu, const auto& ln_rs) {
@@ -155,8 +127,8 @@ __global__ __launch_bounds__(CA_THREADS, 1) void q_attn_kernel(QAttnGroup g) {
 //   * k|v K-loop: gemm_h2_tile on a 64 x 384 block tile (SEGS = 2: the 192 key rows and the 192 value rows of head h of layer `layer` in the stacked
 //     [K_0 .. K_n | V_0 .. V_n] operand), eight waves of 32 x 96 on a ring of 2 (112 KiB), K = km (256 / 512); the accumulators stay in registers;
 //   * q K-loop and the q planes: q_attn_kernel's;
-//   * k / v planes: the arithmetic of emage_gemm's float32 row-major (k) and V^T (v) epilogues, split as attn_stage_kv splits the float32 values it
-//     reads, into the layout it gives them (qkv_attention.hip does the same for its own k / v);
+//   * k / v planes: the arithmetic of emage_gemm's float32 row-major (k) and V^T (v) epilogues (attn_site.h), split as attn_stage_kv splits the
+//     float32 values it reads, into the layout it gives them (attn_tile.h: attn_store_row8 / attn_store_vt8; qkv_attention.hip does the same);
 //   * attention: as above.
 // `att` is the same bits as emage_gemm (K float32, V^T float32) + emage_q_attention (tests/test_qm_attention_gpu.py).
 static_assert(h2_smem_bytes<CA_BM, QM_BN, QM_NS>() <= CA_LDS, "the k|v operand ring lies inside the staged planes");
@@ -166,16 +138,10 @@ __global__ __launch_bounds__(CA_THREADS, 1) void qm_attn_kernel(QmAttnGroup g) {
     constexpr int KWTN = QM_BN / CA_WN, KFN = KWTN / 16, KNP = KFN / 2;
     static_assert(KFN % 2 == 0 && CA_HD % KWTN == 0, "a wave's k|v columns are whole fragment pairs of k or of v");
     __shared__ __attribute__((aligned(128))) unsigned char smem[CA_LDS];
-    const int bid = xcd_run_order((int)blockIdx.x, g.total);
-    int pi = 0;
-#pragma unroll
-    for (int i = 0; i < CA_MAXG - 1; ++i) pi += (i + 1 < g.n && bid >= g.blk_end[i]) ? 1 : 0;
-    pi = __builtin_amdgcn_readfirstlane(pi);
-    const int t = bid - (pi ? g.blk_end[pi - 1] : 0);
-    const QmAttnArgs& q = g.p[pi];
+    int b, h;
+    const QmAttnArgs& q = site_block<CA_H>(g, b, h);
     const GemmArgs& p = q.g;
     const GemmArgs& kv = q.kv;
-    const int b = t / CA_H, h = t - b * CA_H;
     const int nkv0 = q.layer * CA_D + h * CA_HD;       // first key row of this head in the stacked operand; its values lie kv.N / 2 rows further on
 
     // k|v of this wave's 32 memory frames x 96 columns: kept until the q projection has run
@@ -198,36 +164,14 @@ __global__ __launch_bounds__(CA_THREADS, 1) void qm_attn_kernel(QmAttnGroup g) {
             const int fm = wm * 32 + I * 16 + fr;      // memory frame of this lane's row
             const int cc = c0 + JP * 32;               // this lane's 8 columns inside the head: cc .. cc + 7
             float v[8];
-            uint4 hi, lo;
-            if (seg == 0) {
-                // k: the row-major epilogue's float32 values (no slope, no residual: leaky(., 1), + 0), in K's row layout at smem
+            if (seg == 0) {                            // k: the row-major epilogue's values, K's rows
 #pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    float y = (e < 4 ? kva[I][2 * JP][e] : kva[I][2 * JP + 1][e - 4]) * os + kb[JP][e];
-                    y = leaky(y, 1.f);
-                    y += 0.f;
-                    v[e] = y;
-                }
-                h2_split8(v, hi, lo, p.h2s);
-                unsigned char* dst = smem + fm * L::KROW + (cc >> 5) * 128 + ((cc & 15) >> 2) * 32 + ((cc & 31) >> 4) * 8;
-                *(uint2*)dst = make_uint2(hi.x, hi.y);
-                *(uint2*)(dst + 16) = make_uint2(lo.x, lo.y);
-                *(uint2*)(dst + 32) = make_uint2(hi.z, hi.w);
-                *(uint2*)(dst + 48) = make_uint2(lo.z, lo.w);
-            } else {
-                // v: the V^T epilogue's values (leaky(acc + b, 1)) in attn_stage_kv's V^T layout (H2OUT row order; qkv_attention.hip): d row
-                // 32 (dt >> 1) + 4 (dt & 1) + 8 (f >> 2) + (f & 3) is staged row 16 dt + f; key fm sits in cell (fm / 32, (fm % 16) / 4), slot 4 ((fm % 32) / 16) + fm % 4
+                for (int e = 0; e < 8; ++e) v[e] = site_row_value(site_x(e < 4 ? kva[I][2 * JP][e] : kva[I][2 * JP + 1][e - 4], os, false, 0.f, 0.f, 0.f), kb[JP][e]);
+                attn_store_row8<L>(smem, fm, cc, v, p.h2s);
+            } else {                                   // v: the V^T epilogue's values, the V^T rows
 #pragma unroll
-                for (int e = 0; e < 8; ++e) v[e] = leaky((e < 4 ? kva[I][2 * JP][e] : kva[I][2 * JP + 1][e - 4]) * os + kb[JP][e], 1.f);
-                h2_split8(v, hi, lo, p.h2s);
-                const h2f16x8 hv = __builtin_bit_cast(h2f16x8, hi), lv = __builtin_bit_cast(h2f16x8, lo);
-                unsigned char* col = smem + L::K_BYTES + ((fm >> 5) * 4 + ((fm & 15) >> 2)) * 32 + (((fm & 31) >> 4) * 4 + (fm & 3)) * 2;
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    const int j = 16 * (2 * (cc >> 5) + (e >> 2)) + 4 * ((cc & 31) >> 3) + (e & 3);
-                    *(_Float16*)(col + j * L::VROW) = hv[e];
-                    *(_Float16*)(col + j * L::VROW + 16) = lv[e];
-                }
+                for (int e = 0; e < 8; ++e) v[e] = site_vt_value(site_x(e < 4 ? kva[I][2 * JP][e] : kva[I][2 * JP + 1][e - 4], os, false, 0.f, 0.f, 0.f), kb[JP][e]);
+                attn_store_vt8<L>(smem, fm, cc, v, p.h2s);
             }
         });
     };
@@ -253,11 +197,6 @@ int make_problem(int dtype, const emage_q_attention_problem& q, int T, int Tk, i
     return 0;
 }
 
-int q_attention_impl(int dtype, const emage_q_attention_problem* problems, int n, int T, int Tk, int d, int H, hipStream_t s) {
-    const auto make = [=](int dt, const emage_q_attention_problem& q, const H2Scale& hs, QAttnArgs& r) { return make_problem(dt, q, T, Tk, d, H, hs, r); };
-    return launch_sites(dtype, problems, n, H, make, q_attn_kernel, CA_THREADS, s);
-}
-
 // emage_qm_attention: the memory feature image and the stacked k|v operand in place of K / V^T
 int make_problem(int dtype, const emage_qm_attention_problem& q, int T, int Tk, int d, int H, const H2Scale& hs, QmAttnArgs& r) {
     if (T != CA_T || Tk != CA_T || d != CA_D || H != CA_H) return EMAGE_EINVAL;
@@ -280,25 +219,22 @@ int make_problem(int dtype, const emage_qm_attention_problem& q, int T, int Tk, 
     return 0;
 }
 
-int qm_attention_impl(int dtype, const emage_qm_attention_problem* problems, int n, int T, int Tk, int d, int H, hipStream_t s) {
-    const auto make = [=](int dt, const emage_qm_attention_problem& q, const H2Scale& hs, QmAttnArgs& r) { return make_problem(dt, q, T, Tk, d, H, hs, r); };
-    return launch_sites(dtype, problems, n, H, make, qm_attn_kernel, CA_THREADS, s);
-}
-
 }  // namespace
 
-extern "C" int emage_q_attention(int dtype, const emage_q_attention_problem* problem, int T, int Tk, int d, int H, void* stream) {
-    return q_attention_impl(dtype, problem, problem ? 1 : 0, T, Tk, d, H, (hipStream_t)stream);
-}
-
 extern "C" int emage_q_attention_grouped(int dtype, const emage_q_attention_problem* problems, int n_problems, int T, int Tk, int d, int H, void* stream) {
-    return q_attention_impl(dtype, problems, n_problems, T, Tk, d, H, (hipStream_t)stream);
+    const auto make = [=](int dt, const emage_q_attention_problem& q, const H2Scale& hs, QAttnArgs& r) { return make_problem(dt, q, T, Tk, d, H, hs, r); };
+    return launch_sites(dtype, problems, n_problems, H, make, q_attn_kernel, CA_THREADS, (hipStream_t)stream);
 }
 
-extern "C" int emage_qm_attention(int dtype, const emage_qm_attention_problem* problem, int T, int Tk, int d, int H, void* stream) {
-    return qm_attention_impl(dtype, problem, problem ? 1 : 0, T, Tk, d, H, (hipStream_t)stream);
+extern "C" int emage_q_attention(int dtype, const emage_q_attention_problem* problem, int T, int Tk, int d, int H, void* stream) {
+    return emage_q_attention_grouped(dtype, problem, problem ? 1 : 0, T, Tk, d, H, stream);
 }
 
 extern "C" int emage_qm_attention_grouped(int dtype, const emage_qm_attention_problem* problems, int n_problems, int T, int Tk, int d, int H, void* stream) {
-    return qm_attention_impl(dtype, problems, n_problems, T, Tk, d, H, (hipStream_t)stream);
+    const auto make = [=](int dt, const emage_qm_attention_problem& q, const H2Scale& hs, QmAttnArgs& r) { return make_problem(dt, q, T, Tk, d, H, hs, r); };
+    return launch_sites(dtype, problems, n_problems, H, make, qm_attn_kernel, CA_THREADS, (hipStream_t)stream);
+}
+
+extern "C" int emage_qm_attention(int dtype, const emage_qm_attention_problem* problem, int T, int Tk, int d, int H, void* stream) {
+    return emage_qm_attention_grouped(dtype, problem, problem ? 1 : 0, T, Tk, d, H, stream);
 }

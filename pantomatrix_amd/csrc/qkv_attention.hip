@@ -5,8 +5,8 @@
 //   * K-loop: gemm_h2_tile (h2_tile.h) unchanged on a 64 x 576 block tile — the 576 W rows are the three 192-row slices of head h
 //     (SEGS = 3) — 8 waves of 16 x 288 (WTM = 16 as in config 100, so the folded LayerNorm's statistics merge in the same order);
 //   * epilogue: the arithmetic of h2_tile_epilogue for these columns (o_scale, the LayerNorm fold, bias; q / k as the row-major float32
-//     path computes them, v as the V^T path does), then split into fp16 planes straight into the operand ring, in the layout
-//     attn_stage_kv gives K / V^T (and K's layout for Q);
+//     path computes them, v as the V^T path does: attn_site.h), then split into fp16 planes straight into the operand ring, in the layout
+//     attn_stage_kv gives K / V^T (and K's layout for Q) — AttnLds in attn_tile.h, through its attn_store_row8 / attn_store_vt8;
 //   * attention: attn_tile on LDS fragments (QLDS), four waves of 16 queries; `att` is written as the EMAGE_H2 image.
 // Every q / k / v value, every split plane and the order of every MFMA over its contraction are those of the two-launch sequence: the
 // output is the same bits (tests/test_qkv_attention_gpu.py).
@@ -40,16 +40,9 @@ static_assert(h2_smem_bytes<QA_BM, QA_BN, QA_NS>() <= 160 * 1024, "one block per
 
 __global__ __launch_bounds__(QA_THREADS, 1) void qkv_attn_kernel(QkvAttnGroup g) {
     __shared__ __attribute__((aligned(128))) unsigned char smem[h2_smem_bytes<QA_BM, QA_BN, QA_NS>()];
-    // XCD-aware order over the whole grid (gemm_h2_group_kernel): each XCD walks a contiguous run of (clip, head) blocks, heads fastest
-    const int bid = xcd_run_order((int)blockIdx.x, g.total);
-    int pi = 0;
-#pragma unroll
-    for (int i = 0; i < QA_MAXG - 1; ++i) pi += (i + 1 < g.n && bid >= g.blk_end[i]) ? 1 : 0;
-    pi = __builtin_amdgcn_readfirstlane(pi);
-    const int t = bid - (pi ? g.blk_end[pi - 1] : 0);
-    const QkvAttnArgs& q = g.p[pi];
+    int b, h;
+    const QkvAttnArgs& q = site_block<QA_H>(g, b, h);
     const GemmArgs& p = q.g;
-    const int b = t / QA_H, h = t - b * QA_H;
 
     // the epilogue: q / k / v of this wave's 16 frames x 288 columns -> split planes in LDS
     auto epi = [&](auto& acc, const int, const int wm, const int wn, const int fr, const int fg, const auto& ln_mu, const auto& ln_rs) {
@@ -62,51 +55,20 @@ __global__ __launch_bounds__(QA_THREADS, 1) void qkv_attn_kernel(QkvAttnGroup g)
             const int seg = c >= 2 * QA_HD ? 2 : c >= QA_HD ? 1 : 0;      // q / k / v
             const int cc = c - seg * QA_HD + fg * 8;            // this lane's 8 columns inside the head: cc .. cc + 7
             const int n = seg * (p.N / 3) + h * QA_HD + cc;     // ... as columns of the projection
-            float x[8];
+            const bool fold = p.ln_stats != nullptr;   // folded LayerNorm of the operand
+            float cv[8] = {}, bv[8], x[8], v[8];
+            if (fold) load8<float>(p.ln_c + n, cv);
 #pragma unroll
-            for (int e = 0; e < 8; ++e) x[e] = (e < 4 ? acc[0][2 * JP][e] : acc[0][2 * JP + 1][e - 4]) * os;
-            if (p.ln_stats) {                          // folded LayerNorm of the operand
-                float cv[8];
-                load8<float>(p.ln_c + n, cv);
-#pragma unroll
-                for (int e = 0; e < 8; ++e) x[e] = ln_rs[0] * (x[e] - ln_mu[0] * cv[e]);
-            }
-            float bv[8];
+            for (int e = 0; e < 8; ++e) x[e] = site_x(e < 4 ? acc[0][2 * JP][e] : acc[0][2 * JP + 1][e - 4], os, fold, ln_rs[0], ln_mu[0], cv[e]);
             load8<float>(p.bias + n, bv);
-            float v[8];
-            uint4 hi, lo;
-            if (seg < 2) {
-                // q / k: the row-major epilogue's float32 values (no slope, no residual: leaky(., 1), + 0), split as attn_tile splits them
+            if (seg < 2) {                             // q / k: the row-major epilogue's values, K's row layout (Q behind K and V^T)
 #pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    float y = x[e] + bv[e];
-                    y = leaky(y, 1.f);
-                    y += 0.f;
-                    v[e] = y;
-                }
-                h2_split8(v, hi, lo, p.h2s);
-                // K / Q layout: row fm, cell (cc / 32, ((cc % 16) / 4)) holds columns 32 s + 4 g + r (planes [0, 4)) and 32 s + 16 + 4 g + r ([4, 8));
-                // columns cc .. cc + 3 and cc + 4 .. cc + 7 fill the same half of two neighbouring cells
-                unsigned char* dst = smem + (seg ? 0 : L::BYTES) + fm * L::KROW + (cc >> 5) * 128 + ((cc & 15) >> 2) * 32 + ((cc & 31) >> 4) * 8;
-                *(uint2*)dst = make_uint2(hi.x, hi.y);
-                *(uint2*)(dst + 16) = make_uint2(lo.x, lo.y);
-                *(uint2*)(dst + 32) = make_uint2(hi.z, hi.w);
-                *(uint2*)(dst + 48) = make_uint2(lo.z, lo.w);
-            } else {
-                // v: the V^T epilogue's values (leaky(acc + b, 1)), split into the V^T layout of attn_stage_kv (H2OUT row order): d row
-                // 32 (dt >> 1) + 4 (dt & 1) + 8 (f >> 2) + (f & 3) is staged row 16 dt + f; key fm sits in cell (fm / 32, (fm % 16) / 4), slot
-                // 4 ((fm % 32) / 16) + fm % 4
+                for (int e = 0; e < 8; ++e) v[e] = site_row_value(x[e], bv[e]);
+                attn_store_row8<L>(smem + (seg ? 0 : L::BYTES), fm, cc, v, p.h2s);
+            } else {                                   // v: the V^T epilogue's values, the V^T layout
 #pragma unroll
-                for (int e = 0; e < 8; ++e) v[e] = leaky(x[e] + bv[e], 1.f);
-                h2_split8(v, hi, lo, p.h2s);
-                const h2f16x8 hv = __builtin_bit_cast(h2f16x8, hi), lv = __builtin_bit_cast(h2f16x8, lo);
-                unsigned char* col = smem + L::K_BYTES + ((fm >> 5) * 4 + ((fm & 15) >> 2)) * 32 + (((fm & 31) >> 4) * 4 + (fm & 3)) * 2;
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    const int j = 16 * (2 * (cc >> 5) + (e >> 2)) + 4 * ((cc & 31) >> 3) + (e & 3);
-                    *(_Float16*)(col + j * L::VROW) = hv[e];
-                    *(_Float16*)(col + j * L::VROW + 16) = lv[e];
-                }
+                for (int e = 0; e < 8; ++e) v[e] = site_vt_value(x[e], bv[e]);
+                attn_store_vt8<L>(smem, fm, cc, v, p.h2s);
             }
         });
     };
@@ -128,19 +90,15 @@ int make_problem(int dtype, const emage_qkv_attention_problem& q, int T, int d, 
     return 0;
 }
 
-int qkv_attention_impl(int dtype, const emage_qkv_attention_problem* problems, int n, int T, int d, int H, hipStream_t s) {
-    const auto make = [=](int dt, const emage_qkv_attention_problem& q, const H2Scale& hs, QkvAttnArgs& r) { return make_problem(dt, q, T, d, H, hs, r); };
-    return launch_sites(dtype, problems, n, H, make, qkv_attn_kernel, QA_THREADS, s);
-}
-
 }  // namespace
+
+extern "C" int emage_qkv_attention_grouped(int dtype, const emage_qkv_attention_problem* problems, int n_problems, int T, int d, int H, void* stream) {
+    const auto make = [=](int dt, const emage_qkv_attention_problem& q, const H2Scale& hs, QkvAttnArgs& r) { return make_problem(dt, q, T, d, H, hs, r); };
+    return launch_sites(dtype, problems, n_problems, H, make, qkv_attn_kernel, QA_THREADS, (hipStream_t)stream);
+}
 
 extern "C" int emage_qkv_attention(int dtype, const void* A, int lda, const void* W, const float* bias, const float* ln_stats, const float* ln_c,
                                    float ln_eps, void* out, int ldo, int B, int T, int d, int H, float a_scale, float w_scale, void* stream) {
-    emage_qkv_attention_problem q{A, W, bias, ln_stats, ln_c, out, lda, ldo, B, a_scale, w_scale, ln_eps};
-    return qkv_attention_impl(dtype, &q, 1, T, d, H, (hipStream_t)stream);
-}
-
-extern "C" int emage_qkv_attention_grouped(int dtype, const emage_qkv_attention_problem* problems, int n_problems, int T, int d, int H, void* stream) {
-    return qkv_attention_impl(dtype, problems, n_problems, T, d, H, (hipStream_t)stream);
+    const emage_qkv_attention_problem q{A, W, bias, ln_stats, ln_c, out, lda, ldo, B, a_scale, w_scale, ln_eps};
+    return emage_qkv_attention_grouped(dtype, &q, 1, T, d, H, stream);
 }

@@ -21,6 +21,7 @@ from __future__ import annotations
 
 import json
 import os
+from typing import NamedTuple
 
 import torch
 
@@ -654,6 +655,35 @@ class _S:
         self.img, self.stats = img, stats
 
 
+class _Memory(NamedTuple):
+    """The cross-attention memory (Tk frames per clip) of a stack of `n` decoder layers, in one of two forms (`_stack_memory` decides which).
+    Projected: k (B*Tk, n*d) keys and vt (B, n*d, Tp) V^T of every layer, as `_memory_kv` writes them.  Site (`_memory_site`): k / vt are
+    None — each layer's launch contracts the feature image img (B*Tk, km) with the stack's composed K / V operand cx.pk.w[kv_key] itself."""
+    k: object
+    vt: object
+    img: object
+    kv_key: object
+    n: int
+    tk: int
+    index: int = 0
+
+    def layer(self, i):
+        """What `_decoder_layer` takes for layer i of the stack."""
+        return self._replace(index=i)
+
+    def kv(self):
+        """This layer's projected memory as the attention launches take it: the (B*Tk, d) view of its keys, the view of the V^T buffer at
+        its first row, and that buffer's rows per clip."""
+        vt_rows, i = self.vt.shape[1], self.index
+        d = vt_rows // self.n
+        return self.k[:, i * d:(i + 1) * d], self.vt[:, i * d:], vt_rows
+
+    def clips(self, clip0, n):
+        """The memory of clips [clip0, clip0 + n) (row views)."""
+        rows = lambda x, per: None if x is None else x[clip0 * per:(clip0 + n) * per]
+        return self._replace(k=rows(self.k, self.tk), vt=rows(self.vt, 1), img=rows(self.img, self.tk))
+
+
 def _conv_encoder(cx: _Ctx, prefix, x_lo, t, n_layer, length, want_f32):
     """VQEncoderV5 / V6 (P:189-235) on a (M, Cp) operand; returns (lo (M,Cp(length)), f32 (M,length)|None)."""
     lp = _rup(length)
@@ -1153,6 +1183,9 @@ class _WavEncoderMixin:
 # ======================================================================================
 # the stacks' memory K / V operands composed with the memory projection in front of them (`compose_memory`): key "<kv entry>@<projection>"
 _BODY_KV, _FACE_KV = "cross.kv_all@audio_body_motion_proj", "face.kv_all@audio_face_motion_proj"
+# the two decoder stacks' memory: (composed K / V operand, the memory projection it absorbs, the plain K / V operand, layers)
+_STACKS = {"body": (_BODY_KV, "audio_body_motion_proj", "cross.kv_all", spec.N_CROSS_LAYERS),
+           "face": (_FACE_KV, "audio_face_motion_proj", "face.kv_all", spec.N_FACE_LAYERS)}
 
 
 class EmageAudioModel(_WavEncoderMixin, _EmageModule):
@@ -1245,10 +1278,8 @@ class EmageAudioModel(_WavEncoderMixin, _EmageModule):
         m = b * t
         if self._fused_self_attn(cx, b, t, d, h):
             att = cx.lo(m, d)
-            key = name + ".sa.qkv"
-            e = cx.pk.w[key] if x.ln is None else cx.pk.w[key + "@" + x.ln[1]]
-            assert e["cp"] == d and e["n"] == 3 * d
-            ops.qkv_attention(cx.h2dt, x.a, e["w"], e["b"], att, b, w_scale=e.get("ws", 1.0), ln=None if x.ln is None else (x.ln[0], e["c"]))
+            e, kw = self._site_operand(cx, name + ".sa.qkv", x, 3 * d)
+            ops.qkv_attention(cx.h2dt, x.a, e["w"], e["b"], att, b, **kw)
             return cx.gemm_s(att, name + ".sa.out", x, stats)
         qk = cx.f32(m, 2 * d) if cx.h2 else cx.lo(m, 2 * d)          # the attention kernel reads float32 q / k / v^T in the split modes
         vt = cx.vt_buffer(b, d, t)
@@ -1259,6 +1290,13 @@ class EmageAudioModel(_WavEncoderMixin, _EmageModule):
         att = cx.lo(m, d)
         ops.attention(cx.gdt, qk[:, :d], qk[:, d:], vt, d, att, b, h, t, t, d // h)
         return cx.gemm_s(att, name + ".sa.out", x, stats)
+
+    def _site_operand(self, cx, key, x, n):
+        """A fused site's projection operand for the activation x — the plain one, or the one with x's pending LayerNorm folded in — and the
+        scale / fold keywords its launch takes."""
+        e = cx.pk.w[key] if x.ln is None else cx.pk.w[key + "@" + x.ln[1]]
+        assert e["cp"] == self.config.hidden_size and e["n"] == n
+        return e, dict(w_scale=e.get("ws", 1.0), ln=None if x.ln is None else (x.ln[0], e["c"]))
 
     def _fused_self_attn(self, cx, b, t, d, h):
         """Whether a self-attention site runs as one `ops.qkv_attention` launch: EMAGE_H2 eval forward on the GPU, a full 64-frame window, and at
@@ -1314,38 +1352,51 @@ class EmageAudioModel(_WavEncoderMixin, _EmageModule):
             return False
         return all(cx.pk.w[k]["cp"] <= d for k in (_BODY_KV, _FACE_KV))
 
-    def _decoder_layer(self, cx, name, x, b, t, mem_k, mem_vt, vt_rows, tk, post_add=None, fold_out=False, mem_site=None):
-        """nn.TransformerDecoderLayer, post-norm, ReLU, no masks.  x: _X; mem_k: (B*Tk, ld) view of this
-        layer's projected memory keys; mem_vt: view at this layer's first row of a (B, vt_rows, Tp) V^T buffer.
-        `fold_ln`: norm1 / norm2 are folded into the contractions around them; fold_out: norm3 too — the result is then an `_X` with
-        `.ln` set, which only the next layer of the same stack can take.
-        mem_site (`_memory_site`; mem_k / mem_vt are then None): (memory feature image, key of the stack's composed K / V operand, layers in it,
-        this layer's index) — the site computes its K / V^T itself."""
+    def _cross_attn(self, cx, name, x, b, t, mem):
+        """Attention of x's queries over the layer's memory (`_Memory.layer`) -> att (B*T, d): one launch that computes K / V^T too (site form),
+        one launch on the projected K / V^T (`_fused_cross_attn`), or the q projection and the attention."""
         d, h = self.config.hidden_size, spec.N_HEAD
-        fold = cx.fold_ln
-        x = self._ln(cx, name + ".norm1", self._self_attn(cx, name, x, b, t, stats=fold))
-        if mem_site is not None:
+        if mem.k is None:
             att = cx.lo(b * t, d)
-            key = name + ".ca.q"
-            e = cx.pk.w[key] if x.ln is None else cx.pk.w[key + "@" + x.ln[1]]
-            mem, kv_key, n_layers, layer = mem_site
-            kv = cx.pk.w[kv_key]
-            assert e["cp"] == d and e["n"] == d and kv["n"] == 2 * n_layers * d
-            ops.qm_attention(cx.h2dt, x.a, e["w"], e["b"], mem, kv["w"], kv["b"], n_layers, layer, att, b, w_scale=e.get("ws", 1.0),
-                             wkv_scale=kv.get("ws", 1.0), ln=None if x.ln is None else (x.ln[0], e["c"]))
-        elif self._fused_cross_attn(cx, b, t, tk, d, h):
+            e, kw = self._site_operand(cx, name + ".ca.q", x, d)
+            kv = cx.pk.w[mem.kv_key]
+            assert kv["n"] == 2 * mem.n * d
+            ops.qm_attention(cx.h2dt, x.a, e["w"], e["b"], mem.img, kv["w"], kv["b"], mem.n, mem.index, att, b, wkv_scale=kv.get("ws", 1.0), **kw)
+        elif self._fused_cross_attn(cx, b, t, mem.tk, d, h):
             att = cx.lo(b * t, d)
-            key = name + ".ca.q"
-            e = cx.pk.w[key] if x.ln is None else cx.pk.w[key + "@" + x.ln[1]]
-            assert e["cp"] == d and e["n"] == d
-            ops.q_attention(cx.h2dt, x.a, e["w"], e["b"], mem_k, mem_vt, vt_rows, att, b, w_scale=e.get("ws", 1.0),
-                            ln=None if x.ln is None else (x.ln[0], e["c"]))
+            e, kw = self._site_operand(cx, name + ".ca.q", x, d)
+            ops.q_attention(cx.h2dt, x.a, e["w"], e["b"], *mem.kv(), att, b, **kw)
         else:
             q = cx.gemm_ln(x, name + ".ca.q", want="f32")[1] if cx.h2 else cx.gemm_r(x.a, name + ".ca.q")
             att = cx.lo(b * t, d)
-            ops.attention(cx.gdt, q, mem_k, mem_vt, vt_rows, att, b, h, t, tk, d // h)
-        x = self._ln(cx, name + ".norm2", cx.gemm_s(att, name + ".ca.out", x, fold))
+            ops.attention(cx.gdt, q, *mem.kv(), att, b, h, t, mem.tk, d // h)
+        return att
+
+    def _decoder_layer(self, cx, name, x, b, t, mem, post_add=None, fold_out=False):
+        """nn.TransformerDecoderLayer, post-norm, ReLU, no masks.  x: _X; mem: this layer's cross-attention memory
+        (`_Memory.layer`).  `fold_ln`: norm1 / norm2 are folded into the contractions around them; fold_out: norm3 too — the result is
+        then an `_X` with `.ln` set, which only the next layer of the same stack can take."""
+        fold = cx.fold_ln
+        x = self._ln(cx, name + ".norm1", self._self_attn(cx, name, x, b, t, stats=fold))
+        x = self._ln(cx, name + ".norm2", cx.gemm_s(self._cross_attn(cx, name, x, b, t, mem), name + ".ca.out", x, fold))
         return self._ln(cx, name + ".norm3", self._ffn(cx, name, x, stats=fold and fold_out and post_add is None), add=post_add)
+
+    def _stack_memory(self, cx, stack, feats, b, tk, site):
+        """The memory of decoder stack `stack` ("body" / "face") from its memory features (B*Tk, km) — the one place its form is decided.
+        site (`_memory_site` for the batch that CONSUMES it): the site form, nothing is launched.  Otherwise K / V^T by `_memory_kv`: from
+        the features with the composed operand (`compose_memory`), or from their projection (M:303) with the plain one.
+        feats may be a `_Memory` already (features hoisted for another batch size): kept as it is, unless it is in site form and this batch
+        does not take the sites — then the composed K / V launch runs here."""
+        kv_key, proj, plain, n = _STACKS[stack]
+        if isinstance(feats, _Memory):
+            if feats.k is not None or site:
+                return feats
+            feats = feats.img
+        if cx.compose and site:
+            return _Memory(None, None, feats, kv_key, n, tk)
+        if not cx.compose:
+            feats, kv_key = cx.gemm(feats, proj)[0], plain
+        return _Memory(*self._memory_kv(cx, kv_key, feats, b, tk, n), None, None, n, tk)
 
     def _memory_kv(self, cx, key, mem_lo, b, tk, n_layers):
         """Project a cross-attention memory for `n_layers` layers at once: K (B*Tk, n_layers*d) and
@@ -1364,18 +1415,18 @@ class EmageAudioModel(_WavEncoderMixin, _EmageModule):
     def _audio_features(self, cx, audio, b, t, use_audio, fk, lane_face, lane_body, nwin=1, hop=0, win_len=None):
         """Everything that depends on the waveform only (M:275-281, 303 and the cross-attention K/V projections):
         both WavEncoders, `audio_body_motion_proj` and the 8 layers' memory K / V^T.  Returns a dict
-        {memcat (B*T, audio_f+motion_f) with the face features in its first audio_f columns, bk, bvt, abody, ta}; `compose_memory`: abody is the
-        image of the body features, and bk / bvt stay None where the sites compute their own (`_memory_site`).
+        {memcat (B*T, audio_f+motion_f) with the face features in its first audio_f columns, body, ta}; body: the body stack's `_Memory`
+        (`_stack_memory`; None without audio).
         Runs on two stream lanes of `fk`; `inference()` calls it once for ALL full windows of a batch: `audio` is then
         the whole-clip tensor, `nwin` windows of `win_len` samples every `hop` samples, b = nwin * clips sequences."""
         c = self.config
-        af, mf, nc = c.audio_f, c.motion_f, spec.N_CROSS_LAYERS
+        af, mf = c.audio_f, c.motion_f
         lens = self._wav_lengths(audio.shape[1] if win_len is None else win_len)
         ta = lens[-1]
         if ta < t:
             raise RuntimeError(f"Sizes of tensors must match: audio features {ta} frames vs motion {t} frames")
         m = b * t
-        feats = dict(memcat=cx.lo(m, af + mf), bk=None, bvt=None, abody=None, ta=ta)            # [audio2face | body_hint_face] (M:288)
+        feats = dict(memcat=cx.lo(m, af + mf), body=None, ta=ta)            # [audio2face | body_hint_face] (M:288)
         fused0 = self._wav_block0_fused()
         wkw = dict(wav=audio, nwin=nwin, hop=hop, win_len=win_len) if fused0 else {}
         y0 = None
@@ -1394,22 +1445,15 @@ class EmageAudioModel(_WavEncoderMixin, _EmageModule):
             if use_audio:
                 if cx.h2:
                     a_body = ops.cast_pad(cx.h2dt, a_body, a_body.shape[1])
-                if cx.compose:      # the projection (M:303) is part of the K / V operand: the sites, or one K / V launch, contract the features
-                    feats["abody"] = a_body
-                    if not self._memory_site(cx, b // nwin, t, ta):
-                        feats["bk"], feats["bvt"] = self._memory_kv(cx, _BODY_KV, a_body, b, ta, nc)
-                else:
-                    mem_body, _ = cx.gemm(a_body, "audio_body_motion_proj")             # M:303
-                    feats["bk"], feats["bvt"] = self._memory_kv(cx, "cross.kv_all", mem_body, b, ta, nc)
+                feats["body"] = self._stack_memory(cx, "body", a_body, b, ta, self._memory_site(cx, b // nwin, t, ta))
         feats["_keep"] = (y0, a_face, a_body)       # cross-lane operands stay alive until the caller's join
         return feats
 
     @staticmethod
     def _feats_of_clips(feats, clip0, n, t):
         """The features `_audio_features` computed for many sequences, cut to sequences [clip0, clip0 + n) of t frames (row views)."""
-        ta = feats["ta"]
-        rows = lambda k, per: None if feats.get(k) is None else feats[k][clip0 * per:(clip0 + n) * per]
-        return dict(memcat=rows("memcat", t), ta=ta, bk=rows("bk", ta), bvt=rows("bvt", 1), abody=rows("abody", ta))
+        body = feats["body"]
+        return dict(memcat=feats["memcat"][clip0 * t:(clip0 + n) * t], ta=feats["ta"], body=None if body is None else body.clips(clip0, n))
 
     def _speaker_tables(self, cx, speaker_id, b, t):
         """Speaker / positional tables of a (B,T) window (M:285-286, P:341-343): they depend on the speaker ids and T
@@ -1476,8 +1520,9 @@ class EmageAudioModel(_WavEncoderMixin, _EmageModule):
         c_of = {"face": c.cf, "upper": c.cu, "hands": c.ch, "lower": c.cl}
         with Fork(dev, 3, self.concurrent) as fk:
             feats = _audio_feats if _audio_feats is not None else self._audio_features(cx, audio, b, t, use_audio, fk, 1, 2)
-            memcat, bk, bvt, ta = feats["memcat"], feats["bk"], feats["bvt"], feats["ta"]
-            site = use_audio and bk is None and self._memory_site(cx, b, t, ta)       # the stack sites compute their own K / V^T
+            memcat, body, ta = feats["memcat"], feats["body"], feats["ta"]
+            # the stack sites compute their own K / V^T (both stacks or neither: not when the features came with projected K / V^T)
+            site = use_audio and body.k is None and self._memory_site(cx, b, t, ta)
 
             with fk.lane(0):
                 # masked motion -> spatial hints (M:267-273)
@@ -1493,30 +1538,16 @@ class EmageAudioModel(_WavEncoderMixin, _EmageModule):
             # face branch (M:288-294) on lane 1, once the hints (lane 0) are there
             fk.after(1, 0)
             def face_layer(i, face):
-                if site:
-                    return self._decoder_layer(cx, f"face_motion_decoder.layers.{i}", face, b, t, None, None, nf * d, t, fold_out=i < nf - 1,
-                                               mem_site=(memcat, _FACE_KV, nf, i))
-                return self._decoder_layer(cx, f"face_motion_decoder.layers.{i}", face, b, t,
-                                           fkk[:, i * d:(i + 1) * d], fvt[:, i * d:], nf * d, t, fold_out=i < nf - 1)
+                return self._decoder_layer(cx, f"face_motion_decoder.layers.{i}", face, b, t, fmem.layer(i), fold_out=i < nf - 1)
 
             def cross_layer(i, x, base):
-                kw = dict(post_add=base.r if i == nc - 1 else None, fold_out=i < nc - 1)                      # motion_fea + cross
-                if site:
-                    return self._decoder_layer(cx, f"audio_motion_cross_attn.layers.{i}", x, b, t, None, None, nc * d, ta,
-                                               mem_site=(feats["abody"], _BODY_KV, nc, i), **kw)
-                return self._decoder_layer(cx, f"audio_motion_cross_attn.layers.{i}", x, b, t,
-                                           bk[:, i * d:(i + 1) * d], bvt[:, i * d:], nc * d, ta, **kw)
+                return self._decoder_layer(cx, f"audio_motion_cross_attn.layers.{i}", x, b, t, body.layer(i),
+                                           post_add=base.r if i == nc - 1 else None, fold_out=i < nc - 1)          # motion_fea + cross
 
             # the two decoder stacks side by side: lock step (one lane, shared launches) or two lanes
             paired = self.group_face_body and self.group_gemms and use_audio and dev.type == "cuda" and nf < nc
             with fk.lane(1):
-                if site:
-                    fkk = fvt = None
-                elif cx.compose:
-                    fkk, fvt = self._memory_kv(cx, _FACE_KV, memcat, b, t, nf)
-                else:
-                    mem_face, _ = cx.gemm(memcat, "audio_face_motion_proj")
-                    fkk, fvt = self._memory_kv(cx, "face.kv_all", mem_face, b, t, nf)
+                fmem = self._stack_memory(cx, "face", memcat, b, t, site)
                 face = face0
                 if not paired:
                     for i in range(nf):
@@ -1532,9 +1563,8 @@ class EmageAudioModel(_WavEncoderMixin, _EmageModule):
             if use_audio:
                 fk.after(0, 2)
                 base = x
-                if bk is None and not site:     # features hoisted for a batch that takes the sites, consumed by one that does not: the composed K / V launch here
-                    with fk.lane(0):
-                        bk, bvt = self._memory_kv(cx, _BODY_KV, feats["abody"], b, ta, nc)
+                with fk.lane(0):
+                    body = self._stack_memory(cx, "body", body, b, ta, site)
             if paired:
                 fk.after(0, 1)                  # the face memory (lane 1) feeds the lock-step walk on lane 0
                 pair = {}
@@ -1580,9 +1610,9 @@ class EmageAudioModel(_WavEncoderMixin, _EmageModule):
                     tgt = _X(tgt, tgt)
                 ops.add(cx.dt, lat[others[p][0]], lat[others[p][1]], out=mem_lo)
                 name = f"body_motion_decoder_{p}.layers.0"
-                k1, vt1 = self._memory_kv(cx, name + ".ca.kv", mem_lo, b, t, 1)
+                mem = _Memory(*self._memory_kv(cx, name + ".ca.kv", mem_lo, b, t, 1), None, None, 1, t)
                 # motion_refined + latent (M:326-328): the latent rides as the post-add of the layer's last LayerNorm (one launch less per part)
-                sum_lo = self._decoder_layer(cx, name, tgt, b, t, k1, vt1, d, t, post_add=lat[p]).a
+                sum_lo = self._decoder_layer(cx, name, tgt, b, t, mem.layer(0), post_add=lat[p]).a
                 lean_cls = _lean and c_of[p] > 0         # decode takes the arg-max code: rec_* fp32 copy unused
                 rec_lo, out[f"rec_{p}"] = cx.gemm(sum_lo, f"motion_out_proj_{p}", want="lo" if lean_cls else "both")
                 if not (_lean and c_of[p] == 0):

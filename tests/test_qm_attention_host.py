@@ -239,10 +239,10 @@ def test_hoisted_features_without_kv_serve_a_batch_that_keeps_the_launches(monke
         cx = M._Ctx(model._engine())
         with M.Fork(torch.device("cpu"), 3, model.concurrent) as fk:
             feats = model._audio_features(cx, audio, 2, T, True, fk, 1, 2)
-        assert feats["bk"] is None and feats["bvt"] is None and feats["abody"].shape == (2 * T, model.config.audio_f)
+        assert feats["body"].k is None and feats["body"].vt is None and feats["body"].img.shape == (2 * T, model.config.audio_f)
         for i in range(2):
             one = model._feats_of_clips(feats, i, 1, T)
-            assert one["bk"] is None and one["abody"].shape[0] == T and one["memcat"].shape[0] == T
+            assert one["body"].k is None and one["body"].img.shape[0] == T and one["memcat"].shape[0] == T
             one["memcat"] = one["memcat"].clone()                        # the forward writes the body hints into its columns
             got = model.forward(audio[i:i + 1], spk[i:i + 1], motion[i:i + 1], mask[i:i + 1], _audio_feats=one)
             ref = model.forward(audio[i:i + 1], spk[i:i + 1], motion[i:i + 1], mask[i:i + 1])

@@ -516,6 +516,15 @@ int emage_lstm_layer_health(const unsigned* sync, int sync_words, int* counter, 
 int emage_lstm_layer(int dtype, const float* gates_x, long ld_gx_b, int ld_gx_t, const void* w_hh0, const void* w_hh1,
                      float w_scale0, float w_scale1, float a_scale, float* hseq, long ld_h_b, int ld_h_t,
                      int B, int T, int H, unsigned* sync, int sync_words, void* stream);
+/* emage_lstm_layer_lengths: the same launch for clips of DIFFERENT lengths (recordings generated as one batch).  lengths: device array of
+ * B ints, or NULL (= emage_lstm_layer, which forwards here).  Clip b is a sequence of len_b = clamp(lengths[b], 0, T) steps: at every
+ * t >= len_b both directions' cell state and h_t are exactly 0.0f for that clip (selected, never multiplied: gates_x there may hold
+ * anything, NaN included), so the backward direction reaches t = len_b - 1 with zero state and hseq[b][0 .. len_b) carries the BITS of
+ * that clip run alone with T = len_b; hseq[b][len_b .. T) is 0.  The hand-over protocol is untouched (masked steps still store every word
+ * of h_t), so the cost stays that of T steps: lengths shorten no launch. */
+int emage_lstm_layer_lengths(int dtype, const float* gates_x, long ld_gx_b, int ld_gx_t, const void* w_hh0, const void* w_hh1,
+                             float w_scale0, float w_scale1, float a_scale, float* hseq, long ld_h_b, int ld_h_t,
+                             int B, int T, int H, const int* lengths, unsigned* sync, int sync_words, void* stream);
 
 /* DisCo's content blend (D:244-247): out = softmax(sel[:, 0:2])[0] * c1 + softmax(...)[1] * c2, rows of C channels. */
 int emage_softmax2_mix(const float* sel, int ld_sel, const float* c1, int ld1, const float* c2, int ld2,

@@ -40,6 +40,7 @@ struct SeqArgs {
     const unsigned char* w[2]; float os[2]; float a_scale;
     unsigned* sync;                                    // this launch's record: arrival counter of group g at word 32 g (one 128-B line each), error word at 32 * 16
     int B, T, slices;
+    const int* lengths;                                // per-clip sequence lengths (B entries) or nullptr: every clip runs all T steps
     int dbg;                                           // emage_set_tuning key 3 (tools): timing-only
                                                        // ablations (wrong results): 2 = no MFMA phase, 4 = no h load / staging, 8 = no waiting for the group; same bits: 16 = two staging phases (counter protocol only), 32 = round 2's counter protocol, 64 = s_sleep 1 between re-reads
 };
@@ -95,6 +96,20 @@ __global__ __launch_bounds__(256, OCC) void lstm_seq_kernel(SeqArgs p) {
     float c[FB];
 #pragma unroll
     for (int fb = 0; fb < FB; ++fb) c[fb] = 0.f;
+    // per-clip lengths (emage_lstm_layer_lengths): clip b is a sequence of len[b] steps; at every t >= len[b] its cell state and published h_t are
+    // exactly 0 in BOTH directions, so the reverse direction reaches t = len[b] - 1 with the zero state of a run of its own (a zero row of h_{t-1}
+    // gives the zero accumulator of the skipped MFMA phase of step 0: the valid steps carry the bits of that clip run alone over T = len[b]).
+    // Loaded once, ahead of the time loop; rows past the batch end keep T.
+    int len[FB];
+#pragma unroll
+    for (int fb = 0; fb < FB; ++fb) {
+        const int b = b_base + fb * 16 + fr;
+        len[fb] = p.T;
+        if (p.lengths && b < p.B) {
+            const int l = p.lengths[b];
+            len[fb] = l < 0 ? 0 : l > p.T ? p.T : l;
+        }
+    }
 
     const int st_row = lane >> 2, st_g = lane & 3;
 
@@ -305,11 +320,13 @@ __global__ __launch_bounds__(256, OCC) void lstm_seq_kernel(SeqArgs p) {
             const int b = b_base + fb * 16 + fr;
             const float gi = lstm_sigmoid<true>(acc[fb][0] + rv[fb].x), gf = lstm_sigmoid<true>(acc[fb][1] + rv[fb].y);
             const float gg = lstm_tanh<true>(acc[fb][2] + rv[fb].z), go = lstm_sigmoid<true>(acc[fb][3] + rv[fb].w);
-            const float cn = gf * c[fb] + gi * gg;
+            const bool live = t < len[fb];               // a masked step: a SELECT, not a multiply — gates_x there may hold anything, NaN included
+            const float cn = live ? gf * c[fb] + gi * gg : 0.f;
             c[fb] = cn;
             if (b < p.B) {
                 float* dst = p.hseq + (long)b * p.ld_h_b + (long)t * p.ld_h_t + dir * H + unit;
-                __hip_atomic_store(dst, go * lstm_tanh<true>(cn), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);       // write-through (sc1)
+                // every word of h_t is stored at every step, masked ones too (0.0f): consumers poll for the sentinel
+                __hip_atomic_store(dst, live ? go * lstm_tanh<true>(cn) : 0.f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);       // write-through (sc1)
             }
         }
 
@@ -378,11 +395,13 @@ int launch_seq(SeqArgs a, int B, int max_slices, unsigned* sync, hipStream_t s) 
     if (blocks_per_cu < 1 || 2 * max_slices * WPG > blocks_per_cu * device_cus()) return EMAGE_EINVAL;
     const float* gx = a.gx;
     float* hseq = a.hseq;
+    const int* lengths = a.lengths;
     int chunk = 0;
     for (int b0 = 0; b0 < B; b0 += ROWS * max_slices, ++chunk) {
         const int nb = B - b0 < ROWS * max_slices ? B - b0 : ROWS * max_slices;
         a.gx = gx + (long)b0 * a.ld_gx_b;
         a.hseq = hseq + (long)b0 * a.ld_h_b;
+        a.lengths = lengths ? lengths + b0 : nullptr;
         a.B = nb;
         a.slices = (nb + ROWS - 1) / ROWS;
         a.sync = sync + chunk * EMAGE_LSTM_SYNC_WORDS_PER_LAUNCH;
@@ -423,11 +442,18 @@ extern "C" int emage_lstm_layer_sync_words(int B, int H) {
 extern "C" int emage_lstm_layer(int dtype, const float* gates_x, long ld_gx_b, int ld_gx_t, const void* w_hh0, const void* w_hh1,
                                 float w_scale0, float w_scale1, float a_scale, float* hseq, long ld_h_b, int ld_h_t,
                                 int B, int T, int H, unsigned* sync, int sync_words, void* stream) {
+    return emage_lstm_layer_lengths(dtype, gates_x, ld_gx_b, ld_gx_t, w_hh0, w_hh1, w_scale0, w_scale1, a_scale, hseq, ld_h_b, ld_h_t, B, T, H, nullptr,
+                                    sync, sync_words, stream);
+}
+
+extern "C" int emage_lstm_layer_lengths(int dtype, const float* gates_x, long ld_gx_b, int ld_gx_t, const void* w_hh0, const void* w_hh1,
+                                        float w_scale0, float w_scale1, float a_scale, float* hseq, long ld_h_b, int ld_h_t,
+                                        int B, int T, int H, const int* lengths, unsigned* sync, int sync_words, void* stream) {
     if (dtype != EMAGE_F16X3 || !gates_x || !w_hh0 || !w_hh1 || !hseq || !sync || B <= 0 || T <= 0) return EMAGE_EINVAL;
     if (H != 256 && H != 512) return EMAGE_EINVAL;
     if (!(a_scale > 0.f && w_scale0 > 0.f && w_scale1 > 0.f)) return EMAGE_EINVAL;
     if (ld_gx_t % 4 || ld_gx_t < 8 * H || ld_gx_b % 4 || ld_h_t % 4 || ld_h_t < 2 * H || ld_h_b % 4) return EMAGE_EINVAL;
-    if (((uintptr_t)gates_x | (uintptr_t)w_hh0 | (uintptr_t)w_hh1 | (uintptr_t)hseq) & 15 || ((uintptr_t)sync & 3)) return EMAGE_EINVAL;
+    if (((uintptr_t)gates_x | (uintptr_t)w_hh0 | (uintptr_t)w_hh1 | (uintptr_t)hseq) & 15 || (((uintptr_t)sync | (uintptr_t)lengths) & 3)) return EMAGE_EINVAL;
     if (64 * ld_h_b * 4 + 4096 >= (1L << 31)) return EMAGE_EINVAL;                    // a block's 64 clip rows are addressed with 32-bit buffer offsets
     const int need = emage_lstm_layer_sync_words(B, H);
     if (need < 0 || sync_words < need) return EMAGE_EINVAL;
@@ -452,6 +478,7 @@ extern "C" int emage_lstm_layer(int dtype, const float* gates_x, long ld_gx_b, i
     a.os[0] = 1.f / (a_scale * w_scale0); a.os[1] = 1.f / (a_scale * w_scale1);
     a.a_scale = a_scale;
     a.T = T;
+    a.lengths = lengths;
     a.dbg = emage_dev::g_lstm_layer_dbg;
 #ifdef EMAGE_TOOLS
     if (ll && (a.dbg & 128)) return H == 512 ? launch_seq<512, 1, true>(a, B, max_slices, sync, s) : launch_seq<256, 1, true>(a, B, max_slices, sync, s);   // tools A/B: round 3's single hand-over phase

@@ -2111,13 +2111,31 @@ def _lstm_layer(dtype, gates_x, w_hh0, w_hh1, w_scale0, w_scale1, a_scale, hseq,
                                        _ptr(hseq), hseq.stride(0), hseq.stride(1), b, t, h2 // 2, _ptr(sync), sync.numel(), _stream()), "lstm_layer")
 
 
-def lstm_layer(dtype, gates_x, w_hh, w_scale, hseq, sync, *, a_scale=None):
+@_op("lstm_layer_lengths", "(int dtype, Tensor gates_x, Tensor w_hh0, Tensor w_hh1, float w_scale0, float w_scale1, float a_scale, Tensor lengths, "
+                           "Tensor(a!) hseq, Tensor(b!) sync) -> ()")
+def _lstm_layer_lengths(dtype, gates_x, w_hh0, w_hh1, w_scale0, w_scale1, a_scale, lengths, hseq, sync):
+    b, t, h2 = hseq.shape
+    assert gates_x.dim() == 3 and gates_x.shape[0] == b and gates_x.shape[1] == t and gates_x.stride(2) == 1 and hseq.stride(2) == 1
+    check(_lib.load().emage_lstm_layer_lengths(dtype, _ptr(gates_x), gates_x.stride(0), gates_x.stride(1), _ptr(w_hh0), _ptr(w_hh1), w_scale0, w_scale1,
+                                               a_scale, _ptr(hseq), hseq.stride(0), hseq.stride(1), b, t, h2 // 2, _ptr(lengths), _ptr(sync),
+                                               sync.numel(), _stream()), "lstm_layer_lengths")
+
+
+def lstm_layer(dtype, gates_x, w_hh, w_scale, hseq, sync, *, a_scale=None, lengths=None):
     """The whole recurrence of one bidirectional LSTM layer (zero initial state) in one launch per <= 256 clips:
     gates_x (B, T, 8H) fp32 (input projection incl. biases, columns dir * 4H + 4u + g), w_hh / w_scale the two directions'
     packed recurrent weights, hseq (B, T, 2H) fp32 out.  Bit-identical to T `lstm_step_pair` launches.  `sync` from
-    `lstm_layer_sync`; call `lstm_layer_check(sync)` once the stream is synchronised."""
+    `lstm_layer_sync`; call `lstm_layer_check(sync)` once the stream is synchronised.
+    lengths: (B,) int32 device tensor — clip b is a sequence of clamp(lengths[b], 0, T) steps: hseq[b, :len_b] carries the bits of that
+    clip run alone over len_b steps, hseq[b, len_b:] is exactly 0 and gates_x[b, len_b:] is never used (it may hold NaN)."""
     _dev(gates_x)
-    _lstm_layer(dtype, gates_x, w_hh[0], w_hh[1], float(w_scale[0]), float(w_scale[1]), float(A_SCALE_F16X3 if a_scale is None else a_scale), hseq, sync)
+    a_scale = float(A_SCALE_F16X3 if a_scale is None else a_scale)
+    if lengths is None:
+        _lstm_layer(dtype, gates_x, w_hh[0], w_hh[1], float(w_scale[0]), float(w_scale[1]), a_scale, hseq, sync)
+        return hseq
+    assert lengths.dtype == torch.int32 and lengths.dim() == 1 and lengths.numel() == hseq.shape[0] and lengths.is_contiguous() \
+        and lengths.device == hseq.device
+    _lstm_layer_lengths(dtype, gates_x, w_hh[0], w_hh[1], float(w_scale[0]), float(w_scale[1]), a_scale, lengths, hseq, sync)
     return hseq
 
 

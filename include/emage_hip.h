@@ -826,6 +826,68 @@ int emage_gather_windows(int audio_fmt, const void* audio, long total_samples, c
 int emage_copy_segments(const void* src, long src_rows, void* dst, long dst_rows, const long long* segments, int n_segments,
                         long width_bytes, long max_rows, int* status, void* stream);
 
+/* The streaming batch (csrc/stream.hip; pantomatrix_amd/streaming.py): `slots` live sessions of EmageAudioModel.inference whose audio arrives
+ * while they run.  Each entry point is ONE launch over all slots, driven by the per-tick table: EMAGE_STREAM_WORDS int32 words per slot on the
+ * device, filled by the host (which knows what it pushed; nothing is read back to build it):
+ *   READY        the slot runs a window this tick (0: its state is left bit for bit as it is and its output rows are zero)
+ *   AUDIO_READ   position in the slot's audio ring of the window's first sample      AUDIO_WRITE  position where this tick's PCM lands
+ *   PUSH_COUNT   samples of this tick's PCM for the slot (0: none)                   PUSH_SRC     their first sample in the staged buffer
+ *   CODE_WRITE   position in the slot's code rings of the window's first kept code
+ *   SEG_READ     position in the code rings of the decode segment's row 0            SEG_VALID    codes the segment holds from row 0 on
+ *   EMIT_ROW     segment row of the first frame to emit                              EMIT_COUNT   frames to emit
+ * Rings wrap at any element.  A row that points outside its buffers is skipped — nothing outside the buffers is read or written, the outputs
+ * the row would have filled are zero — and ORs EMAGE_STREAM_BAD_* into *status (one int32 on the device, sticky). */
+#define EMAGE_STREAM_WORDS 12
+#define EMAGE_STREAM_READY 0
+#define EMAGE_STREAM_AUDIO_READ 1
+#define EMAGE_STREAM_AUDIO_WRITE 2
+#define EMAGE_STREAM_PUSH_COUNT 3
+#define EMAGE_STREAM_PUSH_SRC 4
+#define EMAGE_STREAM_CODE_WRITE 5
+#define EMAGE_STREAM_SEG_READ 6
+#define EMAGE_STREAM_SEG_VALID 7
+#define EMAGE_STREAM_EMIT_ROW 8
+#define EMAGE_STREAM_EMIT_COUNT 9
+#define EMAGE_STREAM_BAD_PUSH 1
+#define EMAGE_STREAM_BAD_WINDOW 2
+#define EMAGE_STREAM_BAD_COMMIT 4
+#define EMAGE_STREAM_BAD_EMIT 8
+
+/* ring[slot][(AUDIO_WRITE + i) mod ring_len] = staged[PUSH_SRC + i] for i < PUSH_COUNT: the staged buffer (staged_samples samples,
+ * EMAGE_PCM_S16 decoded x * 2^-15 as in emage_gather_windows, or EMAGE_PCM_F32) holds the tick's PCM of every slot end to end; ring: (slots,
+ * ring_len) fp32.  Skipped (EMAGE_STREAM_BAD_PUSH) unless 0 <= PUSH_COUNT <= ring_len, the source range lies inside the staged buffer and
+ * 0 <= AUDIO_WRITE < ring_len. */
+int emage_stream_push(int audio_fmt, const void* staged, long staged_samples, const int* table, int slots, float* ring, long ring_len,
+                      int* status, void* stream);
+
+/* out[slot][i] = ring[slot][(AUDIO_READ + i) mod ring_len] for i < samples (<= ring_len) when the slot is READY, else 0: the audio slice of a
+ * window (M:393-394) as a row of the (slots, samples) batch, pitch ld_out floats.  AUDIO_READ outside [0, ring_len): zero-filled,
+ * EMAGE_STREAM_BAD_WINDOW. */
+int emage_stream_windows(const float* ring, long ring_len, const int* table, int slots, int samples, float* out, long ld_out, int* status,
+                         void* stream);
+
+/* After a window's forward and seed decode.  For a READY slot: code_ring[p][slot][(CODE_WRITE + j) mod ring_codes] = win_codes[p][slot][j] for
+ * j < keep (the window's first `keep` of `window` codes, M:419) for each of the `parts` routed parts, and seeds[slot] = the seed_floats floats
+ * at new_seed + slot * ld_seed (the last seed frames of the window's decode, M:412-418).  Then, for EVERY slot, the decode segment:
+ * segment[p][slot][j] = code_ring[p][slot][(SEG_READ + j) mod ring_codes] for j < SEG_VALID, code 0 for the rows behind and for every row of
+ * a slot that is not READY.  win_codes (parts, slots, window), code_ring (parts, slots, ring_codes), segment (parts, slots, seg_len): int64.
+ * A READY row with CODE_WRITE or SEG_READ outside [0, ring_codes) or SEG_VALID outside [0, min(seg_len, ring_codes)] is treated as not READY
+ * (EMAGE_STREAM_BAD_COMMIT). */
+int emage_stream_commit(const int* table, int slots, int parts, const int64_t* win_codes, int window, int keep, int64_t* code_ring,
+                        int ring_codes, int64_t* segment, int seg_len, const float* new_seed, long ld_seed, float* seeds, int seed_floats,
+                        int* status, void* stream);
+
+/* From the decoded segment (axis_angle (slots * seg_len, 165), expression (slots * seg_len, 100), vel: (slots * seg_len) rows of pitch ldv whose
+ * columns col0 .. col0 + 2 are the global model's x velocity, height and z velocity) rows EMIT_ROW .. EMIT_ROW + EMIT_COUNT - 1 of a READY slot
+ * go to rows 0 .. EMIT_COUNT - 1 of its (out_rows, .) output rows: poses, expressions, codes[row][p] = segment[p][slot][EMIT_ROW + row], and
+ * trans = (x, height, z) with the recurrence of emage_velocity_to_position CONTINUED from carry[slot] (3 floats; x and z are used): the first
+ * emitted row takes the carried position, each later one pos = fadd(fmul(v[row - 1], dt), pos), and the position behind the last emitted row is
+ * stored back — consecutive calls equal one scan over the whole sequence bit for bit.  Rows behind EMIT_COUNT are zero.  EMIT_COUNT outside
+ * [0, out_rows] or rows outside the segment: nothing emitted, carry kept, EMAGE_STREAM_BAD_EMIT. */
+int emage_stream_emit(const int* table, int slots, int seg_len, int out_rows, const float* axis_angle, const float* expression, const float* vel,
+                      int ldv, int col0, float dt, const int64_t* segment, int parts, float* carry, float* poses, float* expressions,
+                      float* trans, int64_t* codes, int* status, void* stream);
+
 /* The metrics of one validation step (train_emage_audio.py:130-204, mode="val": get_rec_loss / get_cls_loss of the three eval forwards, the
  * arg-max codes) over the REAL clips of a padded batch, in two launches (csrc/val.hip).  `entries`: a HOST array of up to
  * EMAGE_VAL_MAX_ENTRIES rows, one per (forward, body part), validated here and carried to the device by value in the kernel arguments

@@ -133,6 +133,10 @@ SIGNATURES = {
     "emage_gather_clip_speakers": [_p, _l, _p, _i, _i, _p, _l, _p, _l, _p, _p, _p],
     "emage_gather_windows": [_i, _p, _l, _p, _i, _i, _p, _l, _p, _p],
     "emage_copy_segments": [_p, _l, _p, _l, _p, _i, _l, _l, _p, _p],
+    "emage_stream_push": [_i, _p, _l, _p, _i, _p, _l, _p, _p],
+    "emage_stream_windows": [_p, _l, _p, _i, _i, _p, _l, _p, _p],
+    "emage_stream_commit": [_p, _i, _i, _p, _i, _i, _p, _i, _p, _i, _p, _l, _p, _i, _p, _p],
+    "emage_stream_emit": [_p, _i, _i, _i, _p, _p, _p, _i, _i, _f, _p, _i, _p, _p, _p, _p, _p, _p, _p],
     "emage_val_metrics_workspace_bytes": [_i, _i],
     "emage_val_metrics": [C.POINTER(ValEntry), _i, _i, _i, _p, _p, _p, _l, _p],
     "emage_mul_add": [_p, _i, _p, _i, _i, _p, _i, _p, _i, _i, _i, _p],

@@ -5,6 +5,7 @@
 #include "common.h"
 #include <math.h>
 #include "rot_math.h"
+#include "vel_step.h"
 
 namespace {
 
@@ -78,7 +79,7 @@ __global__ void velocity_scan_kernel(const float* __restrict__ vel, int ldv, int
         float pos = init[(long)b * ld_init + ax];
         o[0] = pos;
         for (int t = 1; t < T; ++t) {
-            pos = __fadd_rn(__fmul_rn(v[(long)(t - 1) * ldv], dt), pos);
+            pos = emage_vel::step(pos, v[(long)(t - 1) * ldv], dt);
             o[(long)t * 3] = pos;
         }
     }
@@ -104,7 +105,7 @@ __global__ __launch_bounds__(128) void velocity_scan_lds_kernel(const float* __r
         float prev = s_p[0];
         s_p[0] = pos;
         for (int t = 1; t < T; ++t) {
-            pos = __fadd_rn(__fmul_rn(prev, dt), pos);
+            pos = emage_vel::step(pos, prev, dt);
             prev = s_p[t];
             s_p[t] = pos;
         }

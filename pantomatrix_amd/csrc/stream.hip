@@ -1,0 +1,197 @@
+// Data movement of the streaming batch (pantomatrix_amd/streaming.py): a fixed number of slots, each one live session of
+// EmageAudioModel.inference (M:343-470) whose audio arrives while it runs.  Four table-driven kernels, each ONE launch over all slots, so a
+// tick is a fixed launch sequence whatever the sessions do — one captured graph:
+//   emage_stream_push     scatters the tick's staged PCM into the per-slot audio rings (fp32; s16 decoded x * 2^-15), wrapping at any sample;
+//   emage_stream_windows  cuts each ready slot's window out of its ring into a row of the (slots, samples) batch; other rows are zero;
+//   emage_stream_commit   appends a ready slot's kept codes to its code ring, takes its new seed rows, and lays out every slot's decode segment;
+//   emage_stream_emit     copies each slot's emit range out of the decoded segment and continues its root translation from the carried position.
+// All four read the per-tick table (EMAGE_STREAM_WORDS int32 words per slot, emage_hip.h) the host uploads once per tick.  A table row that
+// points outside its buffers is skipped (it reads and writes nothing; its outputs are zero) and ORs its bit into the sticky status word.
+// Volumes are tiny next to the forward (one window of audio and a few hundred codes per slot): plain element loops, no LDS but the scan's.
+#include "common.h"
+#include "vel_step.h"
+
+namespace {
+
+constexpr int THREADS = 256;
+constexpr int SPANS = 16;                      // blocks per slot of the two audio kernels
+
+struct Row {
+    int ready, audio_read, audio_write, push_count, push_src, code_write, seg_read, seg_valid, emit_row, emit_count;
+    __device__ explicit Row(const int* t)
+        : ready(t[EMAGE_STREAM_READY]), audio_read(t[EMAGE_STREAM_AUDIO_READ]), audio_write(t[EMAGE_STREAM_AUDIO_WRITE]),
+          push_count(t[EMAGE_STREAM_PUSH_COUNT]), push_src(t[EMAGE_STREAM_PUSH_SRC]), code_write(t[EMAGE_STREAM_CODE_WRITE]),
+          seg_read(t[EMAGE_STREAM_SEG_READ]), seg_valid(t[EMAGE_STREAM_SEG_VALID]), emit_row(t[EMAGE_STREAM_EMIT_ROW]),
+          emit_count(t[EMAGE_STREAM_EMIT_COUNT]) {}
+};
+
+__device__ __forceinline__ float pcm(const short* p, long i) { return (float)p[i] * (1.f / 32768.f); }
+__device__ __forceinline__ float pcm(const float* p, long i) { return p[i]; }
+
+template <typename T>
+__global__ __launch_bounds__(THREADS) void push_kernel(const T* __restrict__ staged, long staged_samples, const int* __restrict__ table,
+                                                       float* __restrict__ ring, long ring_len, int* __restrict__ status) {
+    const Row r(table + (long)blockIdx.x * EMAGE_STREAM_WORDS);
+    if (r.push_count == 0) return;
+    if (r.push_count < 0 || r.push_count > ring_len || r.push_src < 0 || r.push_src > staged_samples - r.push_count || r.audio_write < 0 ||
+        r.audio_write >= ring_len) {
+        if (threadIdx.x == 0 && blockIdx.y == 0) atomicOr(status, EMAGE_STREAM_BAD_PUSH);
+        return;
+    }
+    float* o = ring + (long)blockIdx.x * ring_len;
+    for (long i = (long)blockIdx.y * THREADS + threadIdx.x; i < r.push_count; i += (long)SPANS * THREADS) {
+        long p = r.audio_write + i;
+        if (p >= ring_len) p -= ring_len;
+        o[p] = pcm(staged, r.push_src + i);
+    }
+}
+
+__global__ __launch_bounds__(THREADS) void windows_kernel(const float* __restrict__ ring, long ring_len, const int* __restrict__ table, int samples,
+                                                          float* __restrict__ out, long ld, int* __restrict__ status) {
+    const Row r(table + (long)blockIdx.x * EMAGE_STREAM_WORDS);
+    float* o = out + (long)blockIdx.x * ld;
+    bool ok = r.ready != 0;
+    if (ok && (r.audio_read < 0 || r.audio_read >= ring_len)) {
+        if (threadIdx.x == 0 && blockIdx.y == 0) atomicOr(status, EMAGE_STREAM_BAD_WINDOW);
+        ok = false;
+    }
+    const float* src = ring + (long)blockIdx.x * ring_len;
+    for (int i = blockIdx.y * THREADS + threadIdx.x; i < samples; i += SPANS * THREADS) {
+        long p = (long)r.audio_read + i;
+        if (p >= ring_len) p -= ring_len;
+        o[i] = ok ? src[p] : 0.f;
+    }
+}
+
+// block = one slot.  Phase 1 (ready slots): codes and seed rows into the slot's state; phase 2 (every slot): the decode segment out of the
+// code ring, rows beyond seg_valid — and every row of a slot that is not ready — code 0.
+__global__ __launch_bounds__(THREADS) void commit_kernel(const int* __restrict__ table, int parts, const int64_t* __restrict__ win_codes, int window,
+                                                         int keep, int64_t* __restrict__ code_ring, int ring_codes, int64_t* __restrict__ segment,
+                                                         int seg_len, const float* __restrict__ new_seed, long ld_seed, float* __restrict__ seeds,
+                                                         int seed_floats, int slots, int* __restrict__ status) {
+    const int s = blockIdx.x, tid = threadIdx.x;
+    const Row r(table + (long)s * EMAGE_STREAM_WORDS);
+    bool ok = r.ready != 0;
+    if (ok && (r.code_write < 0 || r.code_write >= ring_codes || r.seg_read < 0 || r.seg_read >= ring_codes || r.seg_valid < 0 ||
+               r.seg_valid > seg_len || r.seg_valid > ring_codes)) {
+        if (tid == 0) atomicOr(status, EMAGE_STREAM_BAD_COMMIT);
+        ok = false;
+    }
+    if (ok) {
+        for (int i = tid; i < parts * keep; i += THREADS) {
+            const int p = i / keep, j = i - p * keep;
+            int c = r.code_write + j;
+            if (c >= ring_codes) c -= ring_codes;
+            code_ring[((long)p * slots + s) * ring_codes + c] = win_codes[((long)p * slots + s) * window + j];
+        }
+        for (int i = tid; i < seed_floats; i += THREADS) seeds[(long)s * seed_floats + i] = new_seed[(long)s * ld_seed + i];
+    }
+    __syncthreads();                                                   // the segment reads the codes this block has just appended
+    for (int i = tid; i < parts * seg_len; i += THREADS) {
+        const int p = i / seg_len, j = i - p * seg_len;
+        int64_t v = 0;
+        if (ok && j < r.seg_valid) {
+            int c = r.seg_read + j;
+            if (c >= ring_codes) c -= ring_codes;
+            v = code_ring[((long)p * slots + s) * ring_codes + c];
+        }
+        segment[((long)p * slots + s) * seg_len + j] = v;
+    }
+}
+
+// block = one slot: rows [emit_row, emit_row + emit_count) of the decoded segment into rows [0, emit_count) of the outputs, zeros behind.
+__global__ __launch_bounds__(THREADS) void emit_kernel(const int* __restrict__ table, int seg_len, int out_rows, const float* __restrict__ aa,
+                                                       const float* __restrict__ expr, const float* __restrict__ vel, int ldv, int col0, float dt,
+                                                       const int64_t* __restrict__ segment, int parts, int slots, float* __restrict__ carry,
+                                                       float* __restrict__ poses, float* __restrict__ expressions, float* __restrict__ trans,
+                                                       int64_t* __restrict__ codes, int* __restrict__ status) {
+    extern __shared__ float s_v[];                                     // [3][count]: the emitted rows' velocity columns, then the positions
+    const int s = blockIdx.x, tid = threadIdx.x;
+    const Row r(table + (long)s * EMAGE_STREAM_WORDS);
+    int n = r.ready ? r.emit_count : 0;
+    if (r.ready && (n < 0 || n > out_rows || r.emit_row < 0 || r.emit_row > seg_len - n)) {
+        if (tid == 0) atomicOr(status, EMAGE_STREAM_BAD_EMIT);
+        n = 0;
+    }
+    const long row0 = (long)s * seg_len + r.emit_row, out0 = (long)s * out_rows;
+    for (int i = tid; i < out_rows * 165; i += THREADS) poses[out0 * 165 + i] = i < n * 165 ? aa[row0 * 165 + i] : 0.f;
+    for (int i = tid; i < out_rows * 100; i += THREADS) expressions[out0 * 100 + i] = i < n * 100 ? expr[row0 * 100 + i] : 0.f;
+    for (int i = tid; i < out_rows * parts; i += THREADS) {
+        const int j = i / parts, p = i - j * parts;
+        codes[out0 * parts + i] = j < n ? segment[((long)p * slots + s) * seg_len + r.emit_row + j] : 0;
+    }
+    for (int i = tid; i < 3 * n; i += THREADS) {
+        const int t = i / 3, ax = i - t * 3;
+        s_v[ax * n + t] = vel[(row0 + t) * ldv + col0 + ax];
+    }
+    __syncthreads();
+    if (tid < 2 && n > 0) {                                            // x (axis 0) and z (axis 2) integrate; row t holds the position AT frame t
+        const int ax = tid * 2;
+        float pos = carry[(long)s * 3 + ax];
+        float* p = s_v + ax * n;
+        for (int t = 0; t < n; ++t) {
+            const float v = p[t];
+            p[t] = pos;
+            pos = emage_vel::step(pos, v, dt);
+        }
+        carry[(long)s * 3 + ax] = pos;                                 // the position of the first frame not emitted yet
+    }
+    __syncthreads();
+    for (int i = tid; i < out_rows * 3; i += THREADS) {
+        const int t = i / 3, ax = i - t * 3;
+        trans[out0 * 3 + i] = t < n ? s_v[ax * n + t] : 0.f;           // y (axis 1) is the decoded height, copied through
+    }
+}
+
+}  // namespace
+
+extern "C" int emage_stream_push(int audio_fmt, const void* staged, long staged_samples, const int* table, int slots, float* ring, long ring_len,
+                                 int* status, void* stream) {
+    if (!staged || !table || !ring || !status) return EMAGE_EINVAL;
+    if (audio_fmt != EMAGE_PCM_S16 && audio_fmt != EMAGE_PCM_F32) return EMAGE_EINVAL;
+    if (slots <= 0 || staged_samples <= 0 || ring_len <= 0 || ring_len > 0x7fffffffL || staged_samples > 0x7fffffffL) return EMAGE_EINVAL;
+    if (((uintptr_t)staged & (audio_fmt == EMAGE_PCM_S16 ? 1 : 3)) || ((uintptr_t)table & 3) || ((uintptr_t)ring & 3) || ((uintptr_t)status & 3)) return EMAGE_EINVAL;
+    if (audio_fmt == EMAGE_PCM_S16)
+        hipLaunchKernelGGL(push_kernel<short>, dim3((unsigned)slots, SPANS), dim3(THREADS), 0, (hipStream_t)stream, (const short*)staged, staged_samples,
+                           table, ring, ring_len, status);
+    else
+        hipLaunchKernelGGL(push_kernel<float>, dim3((unsigned)slots, SPANS), dim3(THREADS), 0, (hipStream_t)stream, (const float*)staged, staged_samples,
+                           table, ring, ring_len, status);
+    return launch_status();
+}
+
+extern "C" int emage_stream_windows(const float* ring, long ring_len, const int* table, int slots, int samples, float* out, long ld_out,
+                                    int* status, void* stream) {
+    if (!ring || !table || !out || !status) return EMAGE_EINVAL;
+    if (slots <= 0 || samples <= 0 || ring_len <= 0 || ring_len > 0x7fffffffL || samples > ring_len || ld_out < samples) return EMAGE_EINVAL;
+    if (((uintptr_t)ring & 3) || ((uintptr_t)table & 3) || ((uintptr_t)out & 3) || ((uintptr_t)status & 3)) return EMAGE_EINVAL;
+    hipLaunchKernelGGL(windows_kernel, dim3((unsigned)slots, SPANS), dim3(THREADS), 0, (hipStream_t)stream, ring, ring_len, table, samples, out, ld_out,
+                       status);
+    return launch_status();
+}
+
+extern "C" int emage_stream_commit(const int* table, int slots, int parts, const int64_t* win_codes, int window, int keep, int64_t* code_ring,
+                                   int ring_codes, int64_t* segment, int seg_len, const float* new_seed, long ld_seed, float* seeds, int seed_floats,
+                                   int* status, void* stream) {
+    if (!table || !win_codes || !code_ring || !segment || !new_seed || !seeds || !status) return EMAGE_EINVAL;
+    if (slots <= 0 || parts <= 0 || parts > 4 || window <= 0 || keep <= 0 || keep > window || ring_codes < keep || seg_len <= 0 || seed_floats <= 0 ||
+        ld_seed < seed_floats)
+        return EMAGE_EINVAL;
+    if (((uintptr_t)table & 3) || ((uintptr_t)win_codes & 7) || ((uintptr_t)code_ring & 7) || ((uintptr_t)segment & 7) || ((uintptr_t)new_seed & 3) ||
+        ((uintptr_t)seeds & 3) || ((uintptr_t)status & 3))
+        return EMAGE_EINVAL;
+    hipLaunchKernelGGL(commit_kernel, dim3((unsigned)slots), dim3(THREADS), 0, (hipStream_t)stream, table, parts, win_codes, window, keep, code_ring,
+                       ring_codes, segment, seg_len, new_seed, ld_seed, seeds, seed_floats, slots, status);
+    return launch_status();
+}
+
+extern "C" int emage_stream_emit(const int* table, int slots, int seg_len, int out_rows, const float* axis_angle, const float* expression,
+                                 const float* vel, int ldv, int col0, float dt, const int64_t* segment, int parts, float* carry, float* poses,
+                                 float* expressions, float* trans, int64_t* codes, int* status, void* stream) {
+    if (!table || !axis_angle || !expression || !vel || !segment || !carry || !poses || !expressions || !trans || !codes || !status) return EMAGE_EINVAL;
+    if (slots <= 0 || seg_len <= 0 || out_rows <= 0 || out_rows > 4096 || parts <= 0 || parts > 4 || col0 < 0 || ldv < col0 + 3) return EMAGE_EINVAL;
+    if (((uintptr_t)table & 3) || ((uintptr_t)segment & 7) || ((uintptr_t)codes & 7) || ((uintptr_t)status & 3)) return EMAGE_EINVAL;
+    hipLaunchKernelGGL(emit_kernel, dim3((unsigned)slots), dim3(THREADS), (size_t)3 * out_rows * sizeof(float), (hipStream_t)stream, table, seg_len,
+                       out_rows, axis_angle, expression, vel, ldv, col0, dt, segment, parts, slots, carry, poses, expressions, trans, codes, status);
+    return launch_status();
+}

@@ -914,15 +914,45 @@ class EmageVQModel(torch.nn.Module):
                 bs, t = x.shape[:2]
                 break
         m = bs * t
-        parts = {}
         dev = self.vq_model_face.device
         todo = (("lower", lower_index, lower_latent), ("hands", hands_index, hands_latent),
                 ("upper", upper_index, upper_latent), ("face", face_index, face_latent))
         trans = [None]
+
+        def scan(lower_mix):
+            trans[0] = self.get_global_motion(lower_mix.view(bs, t, -1), ref_trans)
+
+        parts = self._part_chains(todo, bs, t, scan if get_global_motion else None)
+        aa, motion, expr = ops.merge_parts(parts["face"], parts["upper"], parts["hands"], parts["lower"], m, dev)
+        return dict(expression=expr.view(bs, t, 100), all_motion4inference=motion.view(bs, t, 337),
+                    motion_axis_angle=aa.view(bs, t, 165), trans=trans[0])
+
+    def _decode_segments(self, face_index=None, upper_index=None, hands_index=None, lower_index=None):
+        """A batch of code SEGMENTS (B, T) -> (axis-angle (B * T, 165), expressions (B * T, 100), the global model's output (B * T, 61) whose
+        columns 54 .. 56 are x velocity, height, z velocity): `decode(get_global_motion=True)` without the scan over the velocities, which a
+        stream continues across segments (pantomatrix_amd/streaming.py).  The same part chains as `decode`."""
+        bs, t = next(x for x in (face_index, upper_index, hands_index, lower_index) if x is not None).shape[:2]
+        todo = (("lower", lower_index, None), ("hands", hands_index, None), ("upper", upper_index, None), ("face", face_index, None))
+        vel = [None]
+
+        def velocities(lower_mix):
+            vel[0] = self.global_motion.forward(lower_mix.view(bs, t, -1))["rec_pose"].view(bs * t, -1)
+
+        parts = self._part_chains(todo, bs, t, velocities)
+        aa, _motion, expr = ops.merge_parts(parts["face"], parts["upper"], parts["hands"], parts["lower"], bs * t, self.vq_model_face.device,
+                                            want_motion=False)
+        return aa, expr, vel[0]
+
+    def _part_chains(self, todo, bs, t, after_lower):
+        """The four part decoders of `decode` on (B, T) codes / latents -> {part: fp32 (B * T, dim) or None}; after_lower: what follows the
+        lower stream inside its chain (the global-translation model), called with the lower part's output, or None."""
+        m = bs * t
+        parts = {}
+        dev = self.vq_model_face.device
         # every part's operand set is packed BEFORE the chains below are entered (ADVICE round 4): a packing is torch arithmetic + launches
         # of its own and must not run at record time inside a lock-step chain, where only emage ops are deferred
         engines = {name: getattr(self, f"vq_model_{name}")._engine() for name, index, latent in todo if index is not None or latent is not None}
-        if get_global_motion:
+        if after_lower is not None:
             self.global_motion._engine()
 
         def part_chain(name, index, latent):
@@ -936,11 +966,11 @@ class EmageVQModel(torch.nn.Module):
                 parts[name] = model._decode_idx(cx, idx, bs, t)
             else:
                 parts[name] = None
-            if name == "lower" and get_global_motion:
+            if name == "lower" and after_lower is not None:
                 lower_mix = parts["lower"]
                 if lower_mix is None:   # zeros pose: identity rot6d + zero trans/contact (M:174-177)
                     lower_mix = torch.tensor([1.0, 0, 0, 0, 1, 0] * 9 + [0.0] * 7, device=dev).repeat(m, 1)
-                trans[0] = self.get_global_motion(lower_mix.view(bs, t, -1), ref_trans)
+                after_lower(lower_mix)
 
         # the four part decoders are independent chains of the same shapes on different weights (the global-translation AE follows the
         # lower stream): walked in lock step, their contractions share launches (4 x 8 launches with one block per CU -> 8 with four);
@@ -955,10 +985,7 @@ class EmageVQModel(torch.nn.Module):
                 for lane, (name, index, latent) in enumerate(todo):
                     with fk.lane(lane):
                         part_chain(name, index, latent)
-        trans = trans[0]
-        aa, motion, expr = ops.merge_parts(parts["face"], parts["upper"], parts["hands"], parts["lower"], m, dev)
-        return dict(expression=expr.view(bs, t, 100), all_motion4inference=motion.view(bs, t, 337),
-                    motion_axis_angle=aa.view(bs, t, 165), trans=trans)
+        return parts
 
     def get_global_motion(self, lower_body, ref_trans):                                          # M:195-205
         bs, t, _ = lower_body.shape

@@ -1689,6 +1689,145 @@ def copy_segments(src, dst, segments, width_bytes, max_rows, status):
     return dst
 
 
+# ---- the streaming batch (include/emage_hip.h: emage_stream_push ...) -----------------------------------------------------------------
+STREAM_WORDS = 12                                     # EMAGE_STREAM_WORDS and the word indices below: the per-tick table, int32 words per slot
+STREAM_FIELDS = ("ready", "audio_read", "audio_write", "push_count", "push_src", "code_write", "seg_read", "seg_valid", "emit_row", "emit_count")
+STREAM_STATUS_TEXT = "1: a push outside the staged buffer / ring; 2: a window outside its ring; 4: a commit row outside the code rings; 8: an emit range outside the segment"
+
+
+def stream_table(rows, *, ring_len, staged_samples, samples, ring_codes, seg_len, out_rows):
+    """The per-tick table of the four stream ops, checked on the host: `rows` holds one dict per slot (None: a slot with nothing to do) with
+    the fields of `STREAM_FIELDS` (missing ones are 0).  Every position must lie inside its ring, every push inside the staged buffer without
+    overlapping another slot's, every emit range inside the segment and the output rows -> (slots, STREAM_WORDS) int32 numpy array."""
+    import numpy as np
+    tab = np.zeros((len(rows), STREAM_WORDS), dtype=np.int32)
+    spans = []
+    for k, row in enumerate(rows):
+        if row is None:
+            continue
+        unknown = set(row) - set(STREAM_FIELDS)
+        if unknown:
+            raise ValueError(f"stream_table: slot {k}: unknown fields {sorted(unknown)}")
+        r = {f: int(row.get(f, 0)) for f in STREAM_FIELDS}
+        if r["push_count"]:
+            if not (0 < r["push_count"] <= ring_len and 0 <= r["push_src"] <= staged_samples - r["push_count"] and 0 <= r["audio_write"] < ring_len):
+                raise ValueError(f"stream_table: slot {k}: a push of {r['push_count']} samples from {r['push_src']} to {r['audio_write']} does not fit "
+                                 f"(staged buffer {staged_samples}, ring {ring_len})")
+            spans.append((r["push_src"], r["push_src"] + r["push_count"]))
+        if r["ready"]:
+            if not (samples <= ring_len and 0 <= r["audio_read"] < ring_len):
+                raise ValueError(f"stream_table: slot {k}: window at {r['audio_read']} outside the ring of {ring_len} samples")
+            if not (0 <= r["code_write"] < ring_codes and 0 <= r["seg_read"] < ring_codes and 0 <= r["seg_valid"] <= min(seg_len, ring_codes)):
+                raise ValueError(f"stream_table: slot {k}: code positions {r['code_write']} / {r['seg_read']} / {r['seg_valid']} outside the code ring "
+                                 f"of {ring_codes} / the segment of {seg_len}")
+            if not (0 <= r["emit_count"] <= out_rows and 0 <= r["emit_row"] <= seg_len - r["emit_count"]):
+                raise ValueError(f"stream_table: slot {k}: emit rows [{r['emit_row']}, +{r['emit_count']}) outside the segment of {seg_len} / the {out_rows} output rows")
+        tab[k, :len(STREAM_FIELDS)] = [r[f] for f in STREAM_FIELDS]
+    spans.sort()
+    if any(lo < prev_hi for (_l, prev_hi), (lo, _h) in zip(spans, spans[1:])):
+        raise ValueError("stream_table: two slots' pushes overlap in the staged buffer")
+    return tab
+
+
+def _stream_table_ok(table, slots):
+    assert table.dtype == torch.int32 and table.dim() == 2 and tuple(table.shape) == (slots, STREAM_WORDS) and table.is_contiguous()
+
+
+@_op("stream_push", "(Tensor staged, Tensor table, Tensor(a!) ring, Tensor(b!) status) -> ()")
+def _stream_push(staged, table, ring, status):
+    fmt = _lib.PCM_S16 if staged.dtype == torch.int16 else _lib.PCM_F32
+    check(_lib.load().emage_stream_push(fmt, _ptr(staged), staged.numel(), _ptr(table), ring.shape[0], _ptr(ring), ring.shape[1], _ptr(status),
+                                        _stream()), "stream_push")
+
+
+def stream_push(staged, table, ring, status):
+    """One launch scatters the tick's staged PCM (1-D int16 — decoded x * 2^-15 — or float32) into the per-slot audio rings `ring` (slots,
+    ring_len) float32 as `table` says, wrapping at any sample.  See include/emage_hip.h: emage_stream_push."""
+    _dev(ring)
+    assert staged.dtype in (torch.int16, torch.float32) and staged.dim() == 1 and staged.is_contiguous() and staged.numel() > 0
+    assert ring.dtype == torch.float32 and ring.dim() == 2 and ring.is_contiguous() and status.dtype == torch.int32 and status.numel() == 1
+    _stream_table_ok(table, ring.shape[0])
+    for t in (staged, table, status):
+        assert t.device == ring.device, "stream_push: every tensor on one device"
+    _stream_push(staged, table, ring, status)
+    return ring
+
+
+@_op("stream_windows", "(Tensor ring, Tensor table, Tensor(a!) out, Tensor(b!) status) -> ()")
+def _stream_windows(ring, table, out, status):
+    check(_lib.load().emage_stream_windows(_ptr(ring), ring.shape[1], _ptr(table), ring.shape[0], out.shape[1], _ptr(out), out.stride(0), _ptr(status),
+                                           _stream()), "stream_windows")
+
+
+def stream_windows(ring, table, out, status):
+    """One launch fills `out` (slots, samples) float32 with each ready slot's window out of its ring; rows of slots that are not ready are
+    zero.  See include/emage_hip.h: emage_stream_windows."""
+    _dev(out)
+    assert ring.dtype == torch.float32 and ring.dim() == 2 and ring.is_contiguous() and out.dtype == torch.float32 and out.dim() == 2
+    assert out.stride(1) == 1 and out.shape[0] == ring.shape[0] and 0 < out.shape[1] <= ring.shape[1] and status.dtype == torch.int32 and status.numel() == 1
+    _stream_table_ok(table, ring.shape[0])
+    for t in (ring, table, status):
+        assert t.device == out.device, "stream_windows: every tensor on one device"
+    _stream_windows(ring, table, out, status)
+    return out
+
+
+@_op("stream_commit", "(Tensor table, Tensor win_codes, int keep, Tensor(a!) code_ring, Tensor(b!) segment, Tensor new_seed, Tensor(c!) seeds, "
+                      "Tensor(d!) status) -> ()")
+def _stream_commit(table, win_codes, keep, code_ring, segment, new_seed, seeds, status):
+    parts, slots, window = win_codes.shape
+    check(_lib.load().emage_stream_commit(_ptr(table), slots, parts, _ptr(win_codes), window, keep, _ptr(code_ring), code_ring.shape[2], _ptr(segment),
+                                          segment.shape[2], _ptr(new_seed), new_seed.stride(0), _ptr(seeds), seeds[0].numel(), _ptr(status), _stream()),
+          "stream_commit")
+
+
+def stream_commit(table, win_codes, keep, code_ring, segment, new_seed, seeds, status):
+    """One launch: for ready slots the first `keep` codes of `win_codes` (parts, slots, window) go to the code rings (parts, slots, ring_codes)
+    and `new_seed` (slots, frames, 337) — a view whose slots may be any stride apart — replaces `seeds`; then every slot's decode segment
+    (parts, slots, seg_len) is laid out.  Slots that are not ready keep their state.  See include/emage_hip.h: emage_stream_commit."""
+    _dev(seeds)
+    parts, slots, _w = win_codes.shape
+    for t in (win_codes, code_ring, segment):
+        assert t.dtype == torch.int64 and t.dim() == 3 and t.is_contiguous() and tuple(t.shape[:2]) == (parts, slots)
+    assert seeds.dtype == torch.float32 and seeds.is_contiguous() and seeds.shape[0] == slots and new_seed.dtype == torch.float32
+    assert tuple(new_seed.shape) == tuple(seeds.shape) and new_seed[0].is_contiguous() and (slots == 1 or new_seed.stride(0) >= seeds[0].numel())
+    assert status.dtype == torch.int32 and status.numel() == 1
+    _stream_table_ok(table, slots)
+    for t in (table, win_codes, code_ring, segment, new_seed, status):
+        assert t.device == seeds.device, "stream_commit: every tensor on one device"
+    _stream_commit(table, win_codes, int(keep), code_ring, segment, new_seed, seeds, status)
+    return segment
+
+
+@_op("stream_emit", "(Tensor table, Tensor aa, Tensor expr, Tensor vel, int col0, float dt, Tensor segment, Tensor(a!) carry, Tensor(b!) poses, "
+                    "Tensor(c!) expressions, Tensor(d!) trans, Tensor(e!) codes, Tensor(f!) status) -> ()")
+def _stream_emit(table, aa, expr, vel, col0, dt, segment, carry, poses, expressions, trans, codes, status):
+    parts, slots, seg_len = segment.shape
+    check(_lib.load().emage_stream_emit(_ptr(table), slots, seg_len, poses.shape[1], _ptr(aa), _ptr(expr), _ptr(vel), _ld(vel), col0, dt, _ptr(segment),
+                                        parts, _ptr(carry), _ptr(poses), _ptr(expressions), _ptr(trans), _ptr(codes), _ptr(status), _stream()),
+          "stream_emit")
+
+
+def stream_emit(table, aa, expr, vel, col0, dt, segment, carry, poses, expressions, trans, codes, status):
+    """One launch copies each ready slot's emit range of the decoded segment (`aa` (slots * seg_len, 165), `expr` (., 100), the velocity
+    columns col0 .. col0 + 2 of `vel`) and of `segment`'s codes into the (slots, out_rows, .) outputs and continues the translation from
+    `carry` (slots, 3), storing the carry back.  See include/emage_hip.h: emage_stream_emit."""
+    _dev(poses)
+    parts, slots, seg_len = segment.shape
+    m, rows = slots * seg_len, poses.shape[1]
+    assert segment.dtype == torch.int64 and segment.is_contiguous() and codes.dtype == torch.int64 and tuple(codes.shape) == (slots, rows, parts)
+    assert tuple(aa.shape) == (m, 165) and tuple(expr.shape) == (m, 100) and vel.dim() == 2 and vel.shape[0] == m and vel.shape[1] >= col0 + 3
+    assert tuple(poses.shape) == (slots, rows, 165) and tuple(expressions.shape) == (slots, rows, 100) and tuple(trans.shape) == (slots, rows, 3)
+    assert tuple(carry.shape) == (slots, 3) and status.dtype == torch.int32 and status.numel() == 1
+    for t in (aa, expr, carry, poses, expressions, trans):
+        assert t.dtype == torch.float32 and t.is_contiguous()
+    assert vel.dtype == torch.float32 and vel.stride(1) == 1 and codes.is_contiguous()
+    _stream_table_ok(table, slots)
+    for t in (table, aa, expr, vel, segment, carry, expressions, trans, codes, status):
+        assert t.device == poses.device, "stream_emit: every tensor on one device"
+    _stream_emit(table, aa, expr, vel, int(col0), float(dt), segment, carry, poses, expressions, trans, codes, status)
+
+
 @_op("val_metrics", "(Tensor[] recs, Tensor[] latents, Tensor[] logits, Tensor[] index, Tensor(a!)[] preds, int[] desc, float[] weights, int T, "
                     "Tensor n_valid, Tensor(b!) acc, Tensor(c!) workspace) -> ()")
 def _val_metrics(recs, latents, logits, index, preds, desc, weights, t, n_valid, acc, workspace):

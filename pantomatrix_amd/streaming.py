@@ -1,0 +1,394 @@
+"""Gestures from LIVE audio: a fixed number of slots, each one session of `EmageAudioModel.inference` (M:343-470) whose waveform arrives in
+chunks while it runs, all slots advancing in lock step — one `forward` at B = slots per tick, one captured graph for the life of the batch.
+Sessions open, push PCM, receive frames and close at different times; the other slots keep running and nothing is captured again.
+
+The stream computes what the offline pass (`recordings.RecordingRunner`, the reference's `inference()` + `decode(get_global_motion=True)`)
+computes for the same audio.  Three rules make that so (DESIGN.md derives them):
+
+1. WHEN a window may run.  Window i reads samples [60 i 533, 60 i 533 + 64 * 533) but runs only once the session holds
+   `samples_for_frames(60 i + 64)` samples: only then is n * 30 // 16000 >= 60 i + 64 for every total n the session may be closed at, so the
+   offline `rounds = (L - 4) // 60` contains window i as a FULL window.  (34112 + 31980 i samples would run windows the reference treats as
+   part of a tail.)  The two counts drift apart by 20 samples a window; the audio ring is sized for it.
+2. HOW FAR emission lags.  Every convolution of kernel 3 widens the receptive field by a frame: a part decoder reaches 5 + vae_layer frames
+   either side, the translation path (lower decoder, global encoder, global decoder) R = (5 + L_lower) + (5 + 4 L_global).  A frame is
+   emitted once codes up to frame + R exist — one lag for poses, expressions and translation — decoded from the segment of the last
+   60 + 2 R codes, whose rows nearer than R to an edge that is not a true end of the stream are discarded.  At frame 0 the segment starts at
+   frame 0 (the reference zero-pads there); the true end is `close()`'s, decoded at its true length.
+3. The translation CONTINUES.  `emage_stream_emit` applies the step of `emage_velocity_to_position` (csrc/vel_step.h, shared) from the
+   position carried per slot, so the streamed translation is one scan over the whole velocity sequence, bit for bit.
+
+* ``StreamBatch``  the slots, their device state and the tick;
+* ``Session``      one live stream: `push(pcm)`, `close()`;
+* ``Emitted``      what a session receives: poses (n, 165), expressions (n, 100), trans (n, 3), codes {part: (n,) int64}."""
+from __future__ import annotations
+
+from typing import NamedTuple
+
+import numpy as np
+import torch
+
+from . import ops, synthetic
+from .recordings import MODEL_SR, SEED_DIMS, SPF, frames_of, identity_seed
+
+STATUS_TEXT = ops.STREAM_STATUS_TEXT
+
+
+class Emitted(NamedTuple):
+    poses: np.ndarray
+    expressions: np.ndarray
+    trans: np.ndarray
+    codes: dict
+
+
+def decode_radius(vq_model):
+    """(R_part, R) of rule 2: frames either side a code can reach in the poses / in anything the decode returns."""
+    r_part = 5 + max(int(getattr(vq_model, f"vq_model_{p}").config.vae_layer) for p in ("face", "upper", "hands", "lower"))
+    r_trans = (5 + int(vq_model.vq_model_lower.config.vae_layer)) + (5 + 4 * int(vq_model.global_motion.config.vae_layer))
+    return r_part, max(r_part, r_trans)
+
+
+def window_need(i, window=64, hop=60):
+    """Rule 1: samples a session must hold before window i runs."""
+    return synthetic.samples_for_frames(hop * i + window)
+
+
+def tail_of(n_samples, pre=4, hop=60):
+    """(rounds, tail frames) of a recording of `n_samples` samples: M:345, M:364-368; the tail window has pre + remain frames when
+    remain > pre (M:428-431), else there is none (0)."""
+    total = frames_of(n_samples)
+    if total <= pre:
+        return 0, 0
+    rounds, remain = (total - pre) // hop, (total - pre) % hop
+    return rounds, (pre + remain if remain > pre else 0)
+
+
+class Session:
+    """One live stream in one slot of a `StreamBatch`.  pushed: samples accepted so far; windows: full windows run; emitted: frames handed out."""
+
+    def __init__(self, batch, slot, speaker_id):
+        self.batch, self.slot, self.speaker_id = batch, slot, speaker_id
+        self.pushed = self.windows = self.emitted = 0
+        self.closed = False
+        self._staged = []                                   # host chunks not on the device yet
+
+    def push(self, pcm):
+        self.batch._push(self, pcm)
+
+    def close(self):
+        return self.batch._close(self)
+
+    @property
+    def ready(self):
+        return not self.closed and self.pushed >= window_need(self.windows, self.batch.window, self.batch.hop)
+
+
+class StreamBatch:
+    """`slots` sessions in lock step.
+
+    Device state per slot: an fp32 audio ring of `ring_len` samples (absolute sample a of the session lives at a mod ring_len; samples behind
+    the next window's start may be overwritten), a ring of the last `ring_codes` codes per routed part, the 4 seed rows the next window
+    starts from, the translation carry, the speaker id.  `step()` uploads the PCM staged since the last tick and a table row per slot
+    (`ops.stream_table`), runs the tick — push, windows, `forward` at B = slots, codes, seed decode, commit, segment decode, emit — as ONE
+    graph replay (use_graph=False: eagerly), and downloads the output rows.  Slots that are not ready run on zero audio; `commit` drops what
+    they compute and leaves their state bit for bit.
+
+    audio_format: "f32" or "s16" (decoded x * 2^-15 on the device) — the dtype `push` takes.  max_seconds: the longest session; with
+    max_push (the most samples a session may hold beyond what its next window needs) it sizes the ring: a push that does not fit raises.
+    Weights are fixed for the life of the batch: `step()` raises once the model's version stamp has moved."""
+
+    def __init__(self, model, vq_model, slots=8, audio_format="f32", max_seconds=3600, use_graph=True, max_push=3 * MODEL_SR):
+        dev = model.device
+        model._require_device(dev)                          # an MI355X: there is no CPU path (the host tests lift this check over stand-in ops)
+        on_gpu = dev.type == "cuda"
+        c = model.config
+        if int(c.pose_length) != 64 or int(c.seed_frames) != 4:
+            raise ValueError("StreamBatch: the model must have pose_length 64 and seed_frames 4")
+        if audio_format not in ("f32", "s16"):
+            raise ValueError("StreamBatch: audio_format must be 'f32' or 's16'")
+        if int(slots) <= 0 or int(max_push) <= 0 or max_seconds <= 0:
+            raise ValueError("StreamBatch: slots, max_push and max_seconds must be positive")
+        self.model, self.vq, self.device, self.slots = model, vq_model, dev, int(slots)
+        self.window, self.pre = 64, 4
+        self.hop = self.window - self.pre
+        self.r_part, self.lag = decode_radius(vq_model)
+        self.seg_len = self.hop + 2 * self.lag
+        self.ring_codes = -(-self.seg_len // self.hop) * self.hop          # a multiple of the hop: an append never wraps
+        self.max_samples = int(max_seconds * MODEL_SR)
+        i_max = max((frames_of(self.max_samples) - self.pre) // self.hop, 1)
+        self.ring_len = window_need(0) + 20 * i_max + int(max_push)        # rule 1's drift + the largest backlog
+        self.audio_dtype = torch.float32 if audio_format == "f32" else torch.int16
+        self.parts = [p for p, r in model._routes().items() if r]
+        s, n_p = self.slots, len(self.parts)
+        # ---- device state ----
+        self.ring = torch.zeros(s, self.ring_len, device=dev)
+        self.code_ring = torch.zeros(n_p, s, self.ring_codes, dtype=torch.int64, device=dev)
+        self.seeds = identity_seed(s).to(dev)
+        self.carry = torch.zeros(s, 3, device=dev)
+        self.speaker_id = torch.zeros(s, 1, dtype=torch.long, device=dev)
+        # ---- per tick ----
+        self.staged = torch.zeros(s * self.ring_len, dtype=self.audio_dtype, device=dev)
+        self.staged_host = torch.zeros(s * self.ring_len, dtype=self.audio_dtype, pin_memory=on_gpu)
+        self.table = torch.zeros(s, ops.STREAM_WORDS, dtype=torch.int32, device=dev)
+        self.table_host = torch.zeros(s, ops.STREAM_WORDS, dtype=torch.int32, pin_memory=on_gpu)
+        self.win_audio = torch.zeros(s, self.window * SPF, device=dev)
+        self.win_codes = torch.zeros(n_p, s, self.window, dtype=torch.int64, device=dev)
+        self.segment = torch.zeros(n_p, s, self.seg_len, dtype=torch.int64, device=dev)
+        self.tmpl_motion = identity_seed(s, self.window).to(dev)           # identity pose + all-ones mask (M:347-358), read-only
+        self.tmpl_mask = torch.ones_like(self.tmpl_motion)
+        self._ident = identity_seed(1)[0]
+        # the output rows and the two flags [non-finite values, status word] in ONE buffer: one device-to-host copy per tick
+        self.out, self.out_views = self._output_buffer(s, self.hop, dev, False)
+        self.out_host, self.host_views = self._output_buffer(s, self.hop, torch.device("cpu"), on_gpu)
+        self.nonfinite, self.status = self.out_views["flags"][0:1], self.out_views["flags"][1:2]
+        self.sessions = [None] * s
+        self.precision = model.precision
+        self.graph, self._operands = None, None
+        self.ticks = 0
+        self._upload([None] * s)
+        self._tick()                                                        # no slot ready: packs weights, warms the allocator, validates shapes
+        if on_gpu:
+            torch.cuda.synchronize(dev)
+        self._stamp = self._version_stamp()
+        if use_graph and on_gpu:
+            self.graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(self.graph, capture_error_mode="thread_local"):
+                self._tick()
+            if self._version_stamp() != self._stamp:
+                raise RuntimeError("StreamBatch: capturing the tick re-packed the models' operands")
+        # what the tick's launches read: alive as long as the batch, whatever becomes of the models
+        self._operands = (model._packed, [m._packed for m in vq_model._models()], dict(vq_model._templates))
+
+    def _output_buffer(self, s, rows, dev, pinned):
+        n_p = len(self.parts)
+        sizes = (("poses", s * rows * 165, torch.float32), ("expressions", s * rows * 100, torch.float32), ("trans", s * rows * 3, torch.float32),
+                 ("flags", 2, torch.int32), ("codes", s * rows * n_p, torch.int64))
+        f32_bytes = sum(n for _k, n, _d in sizes[:4]) * 4
+        pad = -f32_bytes % 8
+        buf = torch.zeros(f32_bytes + pad + sizes[4][1] * 8, dtype=torch.uint8, device=dev, pin_memory=pinned)
+        views, lo = {}, 0
+        for k, n, dt in sizes:
+            if k == "codes":
+                lo += pad
+            nbytes = n * (8 if dt == torch.int64 else 4)
+            views[k] = buf[lo:lo + nbytes].view(dt)
+            lo += nbytes
+        views["poses"], views["expressions"] = views["poses"].view(s, rows, 165), views["expressions"].view(s, rows, 100)
+        views["trans"], views["codes"] = views["trans"].view(s, rows, 3), views["codes"].view(s, rows, n_p)
+        return buf, views
+
+    def _version_stamp(self):
+        return (self.model._version_stamp(),) + tuple(m._version_stamp() for m in self.vq._models())
+
+    # ---- sessions -----------------------------------------------------------------------------------------------------------------------
+    def open(self, speaker_id=0, seed=None, ref_trans=None):
+        """A new session in the lowest free slot (raises when there is none).  seed (4, 337) / ref_trans (3,): as `RecordingSet` seeds a
+        recording; None: identity pose, zero translation (test_emage_audio.py)."""
+        free = [k for k, s in enumerate(self.sessions) if s is None]
+        if not free:
+            raise RuntimeError(f"StreamBatch: all {self.slots} slots are in use")
+        if not 0 <= int(speaker_id) < int(self.model.config.speaker_dims):
+            raise ValueError(f"StreamBatch.open: speaker id {speaker_id} outside [0, {int(self.model.config.speaker_dims)})")
+        k = free[0]
+        seed = self._ident if seed is None else torch.as_tensor(seed, dtype=torch.float32)
+        ref_trans = torch.zeros(3) if ref_trans is None else torch.as_tensor(ref_trans, dtype=torch.float32)
+        if tuple(seed.shape) != (self.pre, SEED_DIMS) or tuple(ref_trans.shape) != (3,):
+            raise ValueError(f"StreamBatch.open: seed {tuple(seed.shape)} / ref_trans {tuple(ref_trans.shape)}, expected (4, {SEED_DIMS}) / (3,)")
+        self.seeds[k].copy_(seed)                           # stream-ordered copies into fixed addresses: the next replay reads them
+        self.carry[k].copy_(ref_trans)
+        self.speaker_id[k].fill_(int(speaker_id))
+        self.sessions[k] = s = Session(self, k, int(speaker_id))
+        return s
+
+    def _push(self, s, pcm):
+        if s.closed:
+            raise RuntimeError("Session.push: the session is closed")
+        a = pcm.detach().cpu().numpy() if torch.is_tensor(pcm) else np.asarray(pcm)
+        if a.ndim != 1:
+            raise ValueError(f"Session.push: a 1-D chunk of samples, not {a.shape}")
+        if self.audio_dtype == torch.int16:
+            if a.dtype != np.int16:
+                raise ValueError(f"Session.push: this batch takes int16 PCM (audio_format='s16'), not {a.dtype}")
+        elif a.dtype == np.int16:
+            a = a.astype(np.float32) * np.float32(1.0 / 32768.0)
+        elif a.dtype != np.float32:
+            raise ValueError(f"Session.push: float32 or int16 samples, not {a.dtype}")
+        n = int(a.shape[0])
+        if s.pushed + n > self.max_samples:
+            raise ValueError(f"Session.push: {s.pushed + n} samples exceed max_seconds ({self.max_samples} samples)")
+        if s.pushed + n - self.hop * SPF * s.windows > self.ring_len:
+            raise ValueError(f"Session.push: {n} samples do not fit: the slot would hold {s.pushed + n - self.hop * SPF * s.windows} samples behind its "
+                             f"next window, its ring {self.ring_len} (call step(), or build the batch with a larger max_push)")
+        if n:
+            s._staged.append(np.ascontiguousarray(a))
+            s.pushed += n
+
+    # ---- the tick ---------------------------------------------------------------------------------------------------------------------------
+    def _rows(self, ready):
+        """One table row per slot: the staged PCM of every open session, and for the sessions of `ready` the window they run (rule 2)."""
+        rows, lo = [None] * self.slots, 0
+        host = self.staged_host.numpy()
+        for k, s in enumerate(self.sessions):
+            if s is None:
+                continue
+            row = {}
+            if s._staged:
+                n = sum(len(c) for c in s._staged)
+                np.concatenate(s._staged, out=host[lo:lo + n])
+                row.update(push_count=n, push_src=lo, audio_write=(s.pushed - n) % self.ring_len)
+                lo += n
+                s._staged = []
+            if s in ready:
+                have = self.hop * (s.windows + 1)                           # codes the slot holds after this window
+                valid = min(have, self.seg_len)
+                upto = max(s.emitted, have - self.lag)
+                row.update(ready=1, audio_read=(self.hop * SPF * s.windows) % self.ring_len, code_write=(self.hop * s.windows) % self.ring_codes,
+                           seg_read=(have - valid) % self.ring_codes, seg_valid=valid, emit_row=s.emitted - (have - valid), emit_count=upto - s.emitted)
+            rows[k] = row or None
+        return rows, lo
+
+    def _upload(self, rows, staged=0):
+        tab = ops.stream_table(rows, ring_len=self.ring_len, staged_samples=self.staged.numel(), samples=self.window * SPF,
+                               ring_codes=self.ring_codes, seg_len=self.seg_len, out_rows=self.hop)
+        self.table_host.copy_(torch.from_numpy(tab))
+        if staged:
+            self.staged[:staged].copy_(self.staged_host[:staged], non_blocking=True)
+        self.table.copy_(self.table_host, non_blocking=True)
+
+    def _codes_of(self, buf):
+        return {p: buf[j] for j, p in enumerate(self.parts)}
+
+    def _tick(self):
+        """The launches of one tick: no host state, so it is capturable."""
+        model, vq, s, w, pre = self.model, self.vq, self.slots, self.window, self.pre
+        ops.stream_push(self.staged, self.table, self.ring, self.status)
+        ops.stream_windows(self.ring, self.table, self.win_audio, self.status)
+        model.health_pending = pending = []
+        try:
+            net = model.forward(self.win_audio, self.speaker_id, self.tmpl_motion, self.tmpl_mask, use_audio=True, _lean=True, _seed=self.seeds)
+            codes = self._codes_of(self.win_codes)
+            model._window_codes(net, vq, codes, 0, s, w)
+            ops.count_nonfinite_multi(list(pending), self.nonfinite)
+        finally:
+            model.health_pending = None
+        ts = model._seed_decode_frames(vq, w)                                # M:412-418: only the last frames of the decode feed the next seed
+        dec = vq.decode(**{f"{p}_index": v[:, w - ts:] for p, v in codes.items()})["all_motion4inference"]
+        ops.stream_commit(self.table, self.win_codes, self.hop, self.code_ring, self.segment, dec[:, ts - pre:], self.seeds, self.status)
+        aa, expr, vel = vq._decode_segments(**{f"{p}_index": v for p, v in self._codes_of(self.segment).items()})
+        ops.count_nonfinite_multi([aa, expr, vel], self.nonfinite)
+        v = self.out_views
+        ops.stream_emit(self.table, aa, expr, vel, 54, 1 / 30, self.segment, self.carry, v["poses"], v["expressions"], v["trans"], v["codes"],
+                        self.status)
+
+    def _check_flags(self, flags):
+        bad, status = int(flags[0]), int(flags[1])
+        if status:
+            self.status.zero_()
+            raise RuntimeError(f"StreamBatch: the stream kernels reported status {status} ({STATUS_TEXT})")
+        if bad:
+            self.nonfinite.zero_()
+            raise FloatingPointError(f"{bad} non-finite values among the network outputs of a tick (precision {self.precision!r}): in f16x3 an activation "
+                                     "beyond |x| < 4094 overflows the fp16 planes — run this checkpoint with set_precision('fp32')")
+
+    def _emitted(self, views, k, n):
+        codes = views["codes"][k, :n].numpy()
+        return Emitted(views["poses"][k, :n].numpy().copy(), views["expressions"][k, :n].numpy().copy(), views["trans"][k, :n].numpy().copy(),
+                       {p: codes[:, j].copy() for j, p in enumerate(self.parts)})
+
+    def step(self):
+        """One tick: every session that holds the samples of its next window (rule 1) runs it -> {session: Emitted}.  With no session ready
+        nothing is launched and {} returned; what was pushed stays staged on the host.  A slot with two windows of backlog needs two ticks.
+        Behind a FloatingPointError (non-finite logits somewhere in the batch; they are not traced to a slot) the device state of the slots
+        that ran has advanced and their frames are lost: abandon the batch and build a new one."""
+        ready = [s for s in self.sessions if s is not None and s.ready]
+        if not ready:
+            return {}
+        if self._version_stamp() != self._stamp:
+            raise RuntimeError("StreamBatch.step: the models' parameters changed; weights are fixed for the life of a StreamBatch — build a new one")
+        rows, staged = self._rows(ready)
+        self._upload(rows, staged)
+        if self.graph is not None:
+            self.graph.replay()
+        else:
+            self._tick()
+        self.ticks += 1
+        self.out_host.copy_(self.out, non_blocking=True)
+        if self.device.type == "cuda":
+            torch.cuda.current_stream(self.device).synchronize()
+        self._check_flags(self.host_views["flags"])
+        out = {}
+        for s in ready:
+            n = int(rows[s.slot]["emit_count"])
+            out[s] = self._emitted(self.host_views, s.slot, n)
+            s.windows += 1
+            s.emitted += n
+        return out
+
+    # ---- the end of a session ---------------------------------------------------------------------------------------------------------------
+    def _close(self, s):
+        """The reference's tail window (M:428-470) at its own length, the last codes decoded at their TRUE length — the right edge is
+        zero-padded exactly where the reference pads it — and frames [emitted, frames_out) -> Emitted.  Frees the slot."""
+        if s.closed:
+            raise RuntimeError("Session.close: the session is closed")
+        if s.ready:
+            raise RuntimeError("Session.close: a full window is still pending — call step() first")
+        rounds, t = tail_of(s.pushed, self.pre, self.hop)
+        assert s.windows == rounds, (s.windows, rounds)                     # rule 1
+        result = self._finish(s, rounds, t)
+        s.emitted, s.closed = self.hop * rounds + t, True
+        self.sessions[s.slot] = None
+        return result
+
+    def _finish(self, s, rounds, t):
+        """The device side of `close()`: the tail window of `t` frames (0: none) behind `rounds` full windows, the last decode, the emit."""
+        model, vq, dev, k, pre, hop = self.model, self.vq, self.device, s.slot, self.pre, self.hop
+        rows, staged = self._rows([])
+        if staged:                                                          # PCM pushed since the last tick: a push-only launch
+            self._upload(rows, staged)
+            ops.stream_push(self.staged, self.table, self.ring, self.status)
+        frames_out = hop * rounds + t
+        lo = max(0, hop * rounds - 2 * self.lag) if rounds else 0           # first code of the last decode: R behind the first frame to emit
+        length, n_emit, n_p = frames_out - lo, frames_out - s.emitted, len(self.parts)
+        result = Emitted(np.zeros((0, 165), np.float32), np.zeros((0, 100), np.float32), np.zeros((0, 3), np.float32),
+                         {p: np.zeros(0, np.int64) for p in self.parts})
+        if n_emit > 0:
+            last = torch.zeros(n_p, 1, length, dtype=torch.int64, device=dev)
+            if rounds:                                                      # codes [lo, 60 rounds) out of the ring: at most two runs per part
+                segs, f = [], lo
+                while f < hop * rounds:
+                    n = min(hop * rounds - f, self.ring_codes - f % self.ring_codes)
+                    segs += [((j * self.slots + k) * self.ring_codes + f % self.ring_codes, j * length + f - lo, n) for j in range(n_p)]
+                    f += n
+                table, longest = ops.segment_table(segs, self.code_ring.numel(), last.numel(), dev)
+                ops.copy_segments(self.code_ring, last, table, 8, longest, self.status)
+            if t:
+                row = ops.stream_table([dict(ready=1, audio_read=(hop * SPF * rounds) % self.ring_len)], ring_len=self.ring_len, staged_samples=1,
+                                       samples=t * SPF, ring_codes=self.ring_codes, seg_len=self.seg_len, out_rows=hop)
+                audio = torch.zeros(1, t * SPF, device=dev)
+                ops.stream_windows(self.ring[k:k + 1], torch.from_numpy(row).to(dev), audio, self.status)
+                model.health_pending = pending = []
+                try:
+                    net = model.forward(audio, self.speaker_id[k:k + 1], self.tmpl_motion[:1, :t], self.tmpl_mask[:1, :t], use_audio=True, _lean=True,
+                                        _seed=self.seeds[k:k + 1])
+                    tail = torch.zeros(n_p, 1, t, dtype=torch.int64, device=dev)
+                    model._window_codes(net, vq, self._codes_of(tail), 0, 1, t)
+                    ops.count_nonfinite_multi(list(pending), self.nonfinite)
+                finally:
+                    model.health_pending = None
+                table, longest = ops.segment_table([(j * t, j * length + hop * rounds - lo, t) for j in range(n_p)], tail.numel(), last.numel(), dev)
+                ops.copy_segments(tail, last, table, 8, longest, self.status)
+            aa, expr, vel = vq._decode_segments(**{f"{p}_index": v for p, v in self._codes_of(last).items()})
+            ops.count_nonfinite_multi([aa, expr, vel], self.nonfinite)
+            out, views = self._output_buffer(1, n_emit, dev, False)
+            host, host_views = self._output_buffer(1, n_emit, torch.device("cpu"), False)
+            row = ops.stream_table([dict(ready=1, emit_row=s.emitted - lo, emit_count=n_emit)], ring_len=self.ring_len, staged_samples=1, samples=1,
+                                   ring_codes=self.ring_codes, seg_len=length, out_rows=n_emit)
+            ops.stream_emit(torch.from_numpy(row).to(dev), aa, expr, vel, 54, 1 / 30, last, self.carry[k:k + 1], views["poses"], views["expressions"],
+                            views["trans"], views["codes"], self.status)
+            views["flags"].copy_(self.out_views["flags"])
+            host.copy_(out)
+            self._check_flags(host_views["flags"])
+            result = self._emitted(host_views, 0, n_emit)
+        self.seeds[k].copy_(self._ident)                                   # a free slot runs on the identity seed
+        if dev.type == "cuda":
+            torch.cuda.current_stream(dev).synchronize()                    # the pinned staging buffers are the next tick's to refill
+        return result

@@ -1,0 +1,133 @@
+#!/usr/bin/env python
+"""What one tick of the streaming batch (`pantomatrix_amd.streaming.StreamBatch`) costs on the MI355X at S = 1, 8, 32 and 64 slots, all of
+them live and one window behind their audio — every tick each session pushes the 32 000 samples of its next window and the batch steps:
+  replay     `step()` of a captured batch: staging on the host, two host-to-device copies, ONE graph replay, one device-to-host copy;
+  eager      the same tick, its launches issued one by one (use_graph=False);
+  separate   S separate B = 1 windows through the entry points the parent commit has — `forward`, `_window_codes`, the seed decode and a
+             `decode(get_global_motion=True)` of the last 116 codes per session — which is what serving S live sessions costs without this
+             module (a server there would in fact decode each session's whole history; the arm does not charge for that).
+`decode_ms` is the eager segment decode + emit alone (`_decode_segments` at B = S, T = 60 + 2 lag, and `emage_stream_emit`), and
+`decode_share_of_eager_tick` its share of the eager tick — a share of the replay is not measured here (it needs a kernel trace).
+Wall time per tick around work that ends in a device synchronise (`step()` ends in one); the arms alternate, `--runs` times each, and the
+median and the run-to-run spread are reported.  Writes one JSON document to `--out` and prints it."""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+HOP_SAMPLES = 32000                                      # rule 1: a session's need grows by 60 frames = 32 000 samples a window
+
+
+def summary(values):
+    return {"runs": [round(v, 3) for v in values], "median": round(float(np.median(values)), 3), "spread": round(max(values) - min(values), 3)}
+
+
+class Live:
+    """S sessions of one batch, fed from one long waveform that each slot enters at another sample."""
+
+    def __init__(self, sb, base):
+        from pantomatrix_amd import streaming
+        self.sb, self.waves = sb, [base[1009 * k:] for k in range(sb.slots)]
+        self.sessions = [sb.open() for _ in range(sb.slots)]
+        for s, w in zip(self.sessions, self.waves):
+            s.push(w[:streaming.window_need(0)])
+        assert len(sb.step()) == sb.slots
+
+    def tick(self):
+        from pantomatrix_amd import streaming
+        for s, w in zip(self.sessions, self.waves):
+            s.push(w[s.pushed:streaming.window_need(s.windows)])
+        out = self.sb.step()
+        assert len(out) == self.sb.slots and all(e.poses.shape[0] == 60 for e in out.values())
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--slots", type=int, nargs="+", default=[1, 8, 32, 64])
+    ap.add_argument("--steps", type=int, default=40, help="ticks per timed run")
+    ap.add_argument("--runs", type=int, default=5)
+    ap.add_argument("--precision", default="f16x3")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "stream_bench.json"))
+    ap.add_argument("--commit", default=None, help="recorded in the document (the measured tree is not always a git checkout)")
+    args = ap.parse_args()
+    assert torch.cuda.is_available(), "bench_stream needs an MI355X: none of its figures means anything on a CPU"
+    from pantomatrix_amd import ops, streaming, synthetic
+    from pantomatrix_amd.recordings import identity_seed
+    from tools import workloads
+    dev = "cuda"
+    model, vq = workloads.product_models(precision=args.precision, device=dev)
+    ticks = 2 + args.runs * (args.steps + 1)
+    seconds = (ticks + 2) * HOP_SAMPLES // 16000 + 4
+    base = synthetic.synthetic_audio(1, seconds * 16000 + 1009 * max(args.slots))[0].numpy()
+    result = {"what": "one tick of StreamBatch, every slot live: graph replay vs eager tick vs S separate B = 1 windows (the parent commit's serving cost)",
+              "commit": args.commit, "config": {"precision": args.precision, "ticks_per_run": args.steps, "runs": args.runs, "samples_pushed_per_slot_and_tick": HOP_SAMPLES},
+              "slots": {}}
+    for n in args.slots:
+        live = {"replay": Live(streaming.StreamBatch(model, vq, slots=n, max_seconds=seconds, use_graph=True), base),
+                "eager": Live(streaming.StreamBatch(model, vq, slots=n, max_seconds=seconds, use_graph=False), base)}
+        sb = live["eager"].sb
+        lag, seg_len = sb.lag, sb.seg_len
+        audio = torch.from_numpy(base[:64 * 533].copy()).to(dev)[None]
+        spk, seed1 = torch.zeros(1, 1, dtype=torch.long, device=dev), identity_seed(1).to(dev)
+        motion, mask = identity_seed(1, 64).to(dev), torch.ones(1, 64, 337, device=dev)
+        codes = {p: torch.zeros(1, 64, dtype=torch.int64, device=dev) for p in sb.parts}
+        seg = {f"{p}_index": torch.zeros(1, seg_len, dtype=torch.int64, device=dev) for p in sb.parts}
+        ts = model._seed_decode_frames(vq, 64)
+        carry = sb.carry.clone()                                             # the decode arm must not move the live sessions' translation
+
+        def separate():
+            for _ in range(n):
+                net = model.forward(audio, spk, motion, mask, use_audio=True, _lean=True, _seed=seed1)
+                model._window_codes(net, vq, codes, 0, 1, 64)
+                vq.decode(**{f"{p}_index": v[:, 64 - ts:] for p, v in codes.items()})
+                pred = vq.decode(**seg, get_global_motion=True, ref_trans=torch.zeros(1, 3, device=dev))
+                pred["trans"].cpu()                                          # a session's frames leave the device every window
+            torch.cuda.synchronize()
+
+        def decode():
+            aa, expr, vel = vq._decode_segments(**{f"{p}_index": v for p, v in sb._codes_of(sb.segment).items()})
+            v = sb.out_views
+            ops.stream_emit(sb.table, aa, expr, vel, 54, 1 / 30, sb.segment, carry, v["poses"], v["expressions"], v["trans"], v["codes"], sb.status)
+            torch.cuda.synchronize()
+
+        arms = {"replay": live["replay"].tick, "eager": live["eager"].tick, "separate": separate, "decode": decode}
+        ms = {k: [] for k in arms}
+        for _ in range(args.runs):
+            for name, fn in arms.items():
+                steps = args.steps if name != "separate" else max(2, args.steps * 8 // max(n, 8))
+                fn()                                                         # warm-up of the arm's shapes (and of the caches behind the other arms)
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for _ in range(steps):
+                    fn()
+                torch.cuda.synchronize()
+                ms[name].append(1e3 * (time.perf_counter() - t0) / steps)
+        med = {k: float(np.median(v)) for k, v in ms.items()}
+        result["slots"][str(n)] = {
+            "tick_ms": {k: summary(ms[k]) for k in ("replay", "eager", "separate")}, "decode_ms": summary(ms["decode"]),
+            "decode_share_of_eager_tick": round(med["decode"] / med["eager"], 3), "replay_over_eager": round(med["replay"] / med["eager"], 3),
+            "replay_over_separate": round(med["replay"] / med["separate"], 3), "frames_per_second_replay": round(n * 60 / (med["replay"] * 1e-3), 1),
+            "real_time_sessions_replay": round(n * 2000.0 / med["replay"], 1), "lag_frames": lag, "segment_rows": seg_len,
+            "ring_samples_per_slot": sb.ring_len}
+        for l in live.values():
+            for s in l.sessions:
+                s._staged, s.closed = [], True                              # dropped, not closed: the tail of a benchmark session is nobody's output
+        del live, sb
+        torch.cuda.empty_cache()
+    result["peak_memory_gb"] = round(torch.cuda.max_memory_allocated() / 2 ** 30, 2)
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(result, f, indent=1)
+        f.write("\n")
+    print(json.dumps(result))
+
+
+if __name__ == "__main__":
+    main()

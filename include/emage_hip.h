@@ -860,6 +860,48 @@ int emage_copy_segments(const void* src, long src_rows, void* dst, long dst_rows
 int emage_stream_push(int audio_fmt, const void* staged, long staged_samples, const int* table, int slots, float* ring, long ring_len,
                       int* status, void* stream);
 
+/* emage_stream_push for sessions whose PCM arrives at ANY rate and layout: decode, channel mean and the polyphase filter of
+ * emage_audio_resample, continued across pushes, in ONE launch over all slots.  The samples a slot's ring receives equal
+ * emage_audio_resample over the session's whole PCM bit for bit, wherever the pushes were cut (same taps, same fmaf order: csrc/pcm_taps.h).
+ *   formats   HOST array of n_formats (1 .. EMAGE_STREAM_MAX_FORMATS) rows of EMAGE_STREAM_FORMAT_WORDS ints, validated here and carried to
+ *             the device by value: PCM code, channels (1..8), up, down (lowest terms of 16000 / rate, each <= 65536), half, rpp, row pitch and
+ *             the float offset (a multiple of 4) of the format's phase rows in `taps`.  up != down: half = 10 max(up, down),
+ *             rpp = ceil((2 half + 1) / up), pitch = rpp | 1, the rows as emage_audio_resample takes them, within its two LDS budgets.
+ *             up == down == 1: decode and channel mean only; half = 0, rpp = 1, pitch = 0, no rows.
+ *   taps      the phase rows of every format in one device buffer of taps_floats floats, 16-byte aligned.
+ *   staged    the tick's PCM of every slot (staged_bytes bytes, 16-byte aligned); a slot's frames are contiguous from a 16-byte boundary.
+ *   history   (slots, 2, hist_len) fp32: per slot two sides of the last hist_len decoded mono frames, the newest last.  hist_len >= rpp - 1
+ *             of every format.  A push reads side HIST_SIDE and writes the other; the host flips HIST_SIDE with every push of the slot.
+ *   rs_table  EMAGE_STREAM_RS_WORDS int32 words per slot on the device.  Positions are relative, so they fit whatever the session's age:
+ *     FRAMES      frames staged for the slot this tick (0: none)          SRC16      their first byte in `staged`, in units of 16 bytes
+ *     FORMAT      row of `formats`                                        FINAL      the input has ended: frames behind the staged ones are zeros
+ *     OUT_COUNT   outputs to write this tick                              OUT_POS    ring position of the first, m0 mod ring_len
+ *     KMAX0       (m0 down + half) / up - (frames pushed before this tick): the newest frame output m0 reads, relative to the first staged one
+ *     R0          (m0 down + half) mod up: its phase row
+ *     HIST_VALID  frames of the read side that exist (the rest, before the session's start, read as zeros)       HIST_SIDE  the side to read
+ *   Output m0 + j reads frames kmax - rpp + 1 .. kmax with kmax = KMAX0 + (j down + R0) / up: negative ones from the history, 0 .. FRAMES - 1
+ *   from the staged PCM.  A row with FRAMES and OUT_COUNT both 0 does nothing; FRAMES > 0 always writes the other history side (OUT_COUNT may
+ *   be 0); FRAMES == 0 with FINAL only flushes.  Skipped — ring and history untouched, EMAGE_STREAM_BAD_RESAMPLE — is a row with FORMAT
+ *   outside `formats`, the staged range outside `staged`, OUT_COUNT outside [0, ring_len], OUT_POS outside [0, ring_len), KMAX0 < 0, R0 outside
+ *   [0, up), HIST_VALID outside [0, hist_len], HIST_SIDE not 0 / 1, or — without FINAL — a last output that reads a frame behind the staged ones. */
+#define EMAGE_STREAM_RS_WORDS 12
+#define EMAGE_STREAM_RS_FRAMES 0
+#define EMAGE_STREAM_RS_SRC16 1
+#define EMAGE_STREAM_RS_FORMAT 2
+#define EMAGE_STREAM_RS_FINAL 3
+#define EMAGE_STREAM_RS_OUT_COUNT 4
+#define EMAGE_STREAM_RS_OUT_POS 5
+#define EMAGE_STREAM_RS_KMAX0 6
+#define EMAGE_STREAM_RS_R0 7
+#define EMAGE_STREAM_RS_HIST_VALID 8
+#define EMAGE_STREAM_RS_HIST_SIDE 9
+#define EMAGE_STREAM_BAD_RESAMPLE 16
+#define EMAGE_STREAM_MAX_FORMATS 8
+#define EMAGE_STREAM_FORMAT_WORDS 8
+int emage_stream_push_resample(const void* staged, long staged_bytes, const int* rs_table, int slots, const int* formats, int n_formats,
+                               const float* taps, long taps_floats, float* ring, long ring_len, float* history, int hist_len, int* status,
+                               void* stream);
+
 /* out[slot][i] = ring[slot][(AUDIO_READ + i) mod ring_len] for i < samples (<= ring_len) when the slot is READY, else 0: the audio slice of a
  * window (M:393-394) as a row of the (slots, samples) batch, pitch ld_out floats.  AUDIO_READ outside [0, ring_len): zero-filled,
  * EMAGE_STREAM_BAD_WINDOW. */

@@ -12,7 +12,8 @@ TOOLS_LIB_PATH = os.path.join(_HERE, "csrc", "libemage_hip_tools.so")   # -DEMAG
 F32, BF16, F16X3, H2 = 0, 1, 2, 3
 PCM_S16, PCM_S24, PCM_S32, PCM_F32 = 0, 1, 2, 3       # EMAGE_PCM_*: the sample formats of emage_audio_resample
 AUDIO_TILE = 1024                                     # EMAGE_AUDIO_TILE: outputs per tile of emage_audio_resample
-ABI_VERSION = 20                                      # unchanged by the gradient-norm, clip-store and validation entry points: they were ADDED, no existing prototype moved
+AUDIO_TAPS_LDS_BYTES, AUDIO_SPAN_LDS_BYTES = 96 * 1024, 64 * 1024      # EMAGE_AUDIO_*_LDS_BYTES: the LDS budgets a rate pair must fit
+ABI_VERSION = 20                                     # unchanged by the gradient-norm, clip-store and validation entry points: they were ADDED, no existing prototype moved
 
 _p, _i, _f, _l, _d = C.c_void_p, C.c_int, C.c_float, C.c_long, C.c_double
 
@@ -134,6 +135,7 @@ SIGNATURES = {
     "emage_gather_windows": [_i, _p, _l, _p, _i, _i, _p, _l, _p, _p],
     "emage_copy_segments": [_p, _l, _p, _l, _p, _i, _l, _l, _p, _p],
     "emage_stream_push": [_i, _p, _l, _p, _i, _p, _l, _p, _p],
+    "emage_stream_push_resample": [_p, _l, _p, _i, _p, _i, _p, _l, _p, _l, _p, _i, _p, _p],
     "emage_stream_windows": [_p, _l, _p, _i, _i, _p, _l, _p, _p],
     "emage_stream_commit": [_p, _i, _i, _p, _i, _i, _p, _i, _p, _i, _p, _l, _p, _i, _p, _p],
     "emage_stream_emit": [_p, _i, _i, _i, _p, _p, _p, _i, _i, _f, _p, _i, _p, _p, _p, _p, _p, _p, _p],

@@ -36,6 +36,18 @@ def out_length(n_in, up, down):
     return -(-int(n_in) * up // down)
 
 
+def stream_half(up, down):
+    """The filter's reach as a STREAM sees it: `half_length`, and 0 where up == down (the kernels only decode there: no filter, nothing held back)."""
+    return 0 if up == down else half_length(up, down)
+
+
+def available(n_in, up, down):
+    """Outputs that are FINAL after `n_in` input frames: output m reads frames up to kmax = (m down + half) // up, so it no longer depends on
+    what follows once n_in > kmax, i.e. m down + half < n_in up — the first ceil((n_in up - half) / down) outputs (the streaming
+    front end).  Never more than `out_length(n_in, up, down)`; the outputs between the two wait for more input or for the end of the stream."""
+    return max(0, -(-(int(n_in) * up - stream_half(up, down)) // down))
+
+
 def resample_filter(up, down):
     """The float64 taps of `scipy.signal.resample_poly(x, up, down)`'s default filter: 2 * half + 1 taps of a windowed-sinc low-pass with
     cutoff 1 / max(up, down) of Nyquist, Kaiser window beta = 5, unit gain at DC, times `up`."""

@@ -11,31 +11,16 @@
 // 32 lanes span ~88 words of 32 banks, about 3 lanes per bank.  Samples outside [0, n_in) are zeros in the LDS span, so the tap loop has no bounds tests.
 // Every output has one writer and a fixed summation order (taps in row order): the result is bit-reproducible.
 #include "common.h"
+#include "pcm_taps.h"
 
 namespace {
 
+using emage_pcm::decode_frame;                // the decode, the channel mean and the tap walk are the streaming resampler's too (stream.hip)
+using emage_pcm::sample_bytes;
+
 constexpr int TILE = EMAGE_AUDIO_TILE;
 constexpr int THREADS = 256;
-constexpr int SPAN_SLACK = 16;                // the vector-load path starts its span on a 16-byte chunk of the clip (up to 7 frames early)
-
-__host__ __device__ constexpr int sample_bytes(int fmt) { return fmt == EMAGE_PCM_S16 ? 2 : (fmt == EMAGE_PCM_S24 ? 3 : 4); }
-
-template <int FMT> __device__ __forceinline__ float decode_sample(const unsigned char* p) {
-    if constexpr (FMT == EMAGE_PCM_S16) return (float)*(const short*)p * (1.f / 32768.f);
-    else if constexpr (FMT == EMAGE_PCM_S24) {
-        const int v = (int)p[0] | ((int)p[1] << 8) | ((int)p[2] << 16);
-        return (float)((v ^ 0x800000) - 0x800000) * (1.f / 8388608.f);
-    } else if constexpr (FMT == EMAGE_PCM_S32) return (float)*(const int*)p * (1.f / 2147483648.f);      // int -> float rounds to nearest even
-    else return *(const float*)p;
-}
-
-// one frame -> mono: the fp32 sum in channel order over the channel count (one channel: no arithmetic)
-template <int FMT> __device__ __forceinline__ float decode_frame(const unsigned char* p, int channels) {
-    float s = decode_sample<FMT>(p);
-    if (channels == 1) return s;
-    for (int c = 1; c < channels; ++c) s += decode_sample<FMT>(p + c * sample_bytes(FMT));
-    return s / (float)channels;
-}
+constexpr int SPAN_SLACK = emage_pcm::SPAN_SLACK;    // the vector-load path starts its span on a 16-byte chunk of the clip (up to 7 frames early)
 
 __device__ __forceinline__ float s16_at(const uint4& q, int i) {          // sample i (0..7) of a 16-byte chunk of int16
     const unsigned w = i < 2 ? q.x : (i < 4 ? q.y : (i < 6 ? q.z : q.w));
@@ -104,7 +89,7 @@ __global__ __launch_bounds__(THREADS) void audio_resample_kernel(const unsigned 
             const float* __restrict__ h = s_h + (d % up) * row_pitch;
             const float* __restrict__ x = s_x + xoff + d / up;
             float acc = 0.f;
-            for (int i = 0; i < rpp; ++i) acc = fmaf(h[i], x[-i], acc);
+            for (int i = 0; i < rpp; ++i) acc = emage_pcm::tap_step(acc, h, x, i);
             orow[m0 + r] = acc;
         }
     }

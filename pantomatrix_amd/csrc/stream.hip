@@ -8,7 +8,10 @@
 // All four read the per-tick table (EMAGE_STREAM_WORDS int32 words per slot, emage_hip.h) the host uploads once per tick.  A table row that
 // points outside its buffers is skipped (it reads and writes nothing; its outputs are zero) and ORs its bit into the sticky status word.
 // Volumes are tiny next to the forward (one window of audio and a few hundred codes per slot): plain element loops, no LDS but the scan's.
+// A fifth, emage_stream_push_resample, stands in for emage_stream_push in batches whose sessions push PCM at other rates and layouts: the
+// polyphase filter of audio.hip continued across pushes (csrc/pcm_taps.h is shared), driven by a second per-tick table of its own.
 #include "common.h"
+#include "pcm_taps.h"
 #include "vel_step.h"
 
 namespace {
@@ -44,6 +47,102 @@ __global__ __launch_bounds__(THREADS) void push_kernel(const T* __restrict__ sta
         if (p >= ring_len) p -= ring_len;
         o[p] = pcm(staged, r.push_src + i);
     }
+}
+
+// ---- emage_stream_push_resample: the push for PCM at any rate and layout ---------------------------------------------------------------------
+// grid (slots, SPANS).  The blocks of a slot share the tiles of EMAGE_AUDIO_TILE outputs of its push as audio.hip's blocks share a clip's: the
+// format's phase rows stay in LDS, each tile's input span is decoded into LDS once, and an output is emage_pcm::tap_step over its row in row order — the
+// offline kernel's sum, so the bits are the offline kernel's.  A span's frames come from three places: the slot's history (frames before
+// this push), the staged PCM, and zeros (before the session's start; behind its end once FINAL).  Block 0 of a slot also writes the slot's
+// new history — into the side no block reads in this launch, so there is no order between blocks to keep.
+constexpr int TILE = EMAGE_AUDIO_TILE;
+
+struct Format { int pcm, channels, up, down, half, rpp, row_pitch, taps_offset; };      // EMAGE_STREAM_FORMAT_WORDS ints, in the header's order
+struct Formats { int n; Format f[EMAGE_STREAM_MAX_FORMATS]; };
+
+struct ResampleRow {
+    int frames, src16, format, final, out_count, out_pos, kmax0, r0, hist_valid, hist_side;
+    __device__ explicit ResampleRow(const int* t)
+        : frames(t[EMAGE_STREAM_RS_FRAMES]), src16(t[EMAGE_STREAM_RS_SRC16]), format(t[EMAGE_STREAM_RS_FORMAT]), final(t[EMAGE_STREAM_RS_FINAL]),
+          out_count(t[EMAGE_STREAM_RS_OUT_COUNT]), out_pos(t[EMAGE_STREAM_RS_OUT_POS]), kmax0(t[EMAGE_STREAM_RS_KMAX0]), r0(t[EMAGE_STREAM_RS_R0]),
+          hist_valid(t[EMAGE_STREAM_RS_HIST_VALID]), hist_side(t[EMAGE_STREAM_RS_HIST_SIDE]) {}
+};
+
+// frame k of the session, counted from the first staged one, as mono fp32: k < 0 lies in the history (hist[hist_len - 1] is frame -1)
+template <int FMT> __device__ __forceinline__ float stream_frame(long k, const unsigned char* src, int frames, int channels, const float* hist,
+                                                                 int hist_len, int hist_valid) {
+    if (k >= 0) return k < frames ? emage_pcm::decode_frame<FMT>(src + k * (channels * emage_pcm::sample_bytes(FMT)), channels) : 0.f;
+    return k >= -(long)hist_valid ? hist[hist_len + k] : 0.f;
+}
+
+template <int FMT> __device__ __forceinline__ void resample_slot(const ResampleRow& r, const Format& f, const unsigned char* src, const float* __restrict__ taps,
+                                                                 float* __restrict__ ring, long ring_len, float* hist, int hist_len, float* smem) {
+    const int tid = threadIdx.x;
+    const float* h_old = hist + (long)r.hist_side * hist_len;
+    if (blockIdx.y == 0 && r.frames > 0) {               // the last hist_len frames of (old history ++ push): entry hist_len - j is frame -j of the NEXT push
+        float* h_new = hist + (long)(1 - r.hist_side) * hist_len;
+        for (int j = tid + 1; j <= hist_len; j += THREADS) h_new[hist_len - j] = stream_frame<FMT>((long)r.frames - j, src, r.frames, f.channels, h_old, hist_len, r.hist_valid);
+    }
+    const int n_tiles = (r.out_count + TILE - 1) / TILE;
+    if ((int)blockIdx.y >= n_tiles) return;
+    const bool filter = f.up != f.down;                   // up == down == 1: decode and channel mean only, as audio_decode_kernel
+    const int table = filter ? f.up * f.row_pitch : 0;
+    float* s_h = smem;                                    // up rows of row_pitch taps
+    float* s_x = smem + ((table + 3) & ~3);               // the tile's decoded span
+    const float* rows = taps + f.taps_offset;             // 16-byte aligned: the offset is a multiple of 4 floats
+    for (int i = tid; i < table / 4; i += THREADS) ((float4*)s_h)[i] = ((const float4*)rows)[i];
+    for (int i = (table & ~3) + tid; i < table; i += THREADS) s_h[i] = rows[i];
+    for (int tile = blockIdx.y; tile < n_tiles; tile += gridDim.y) {
+        const int j0 = tile * TILE;                       // outputs are counted from the push's first, m0: nothing here is an absolute position
+        const int n = r.out_count - j0 < TILE ? r.out_count - j0 : TILE;
+        const long base0 = (long)j0 * f.down + r.r0;      // (m down + half) - (the first output's kmax) up, in 64 bits as audio.hip's base0
+        const long q0 = r.kmax0 + base0 / f.up;           // newest frame the tile's first output reads
+        const int rt = (int)(base0 % f.up);
+        const long k0 = q0 - (f.rpp - 1);                 // oldest frame any output of the tile reads
+        const int count = (int)(((long)(n - 1) * f.down + rt) / f.up) + f.rpp;
+        __syncthreads();                                  // the previous tile's readers are done with s_x
+        for (int i = tid; i < count; i += THREADS) s_x[i] = stream_frame<FMT>(k0 + i, src, r.frames, f.channels, h_old, hist_len, r.hist_valid);
+        __syncthreads();
+        for (int o = tid; o < n; o += THREADS) {
+            const int d = o * f.down + rt;                // fits 32 bits: TILE * down + up < 2^31 for up, down <= 65536
+            const float* x = s_x + (f.rpp - 1) + d / f.up;
+            long p = (long)r.out_pos + j0 + o;
+            if (p >= ring_len) p -= ring_len;
+            float acc = x[0];
+            if (filter) {
+                const float* h = s_h + (d % f.up) * f.row_pitch;
+                acc = 0.f;
+                for (int i = 0; i < f.rpp; ++i) acc = emage_pcm::tap_step(acc, h, x, i);
+            }
+            ring[p] = acc;
+        }
+    }
+}
+
+__global__ __launch_bounds__(THREADS) void push_resample_kernel(const unsigned char* __restrict__ staged, long staged_bytes, const int* __restrict__ rs_table,
+                                                                Formats fmts, const float* __restrict__ taps, float* __restrict__ ring, long ring_len,
+                                                                float* history, int hist_len, int* __restrict__ status) {
+    extern __shared__ __attribute__((aligned(16))) float s_resample[];
+    const ResampleRow r(rs_table + (long)blockIdx.x * EMAGE_STREAM_RS_WORDS);
+    if (r.frames == 0 && r.out_count == 0) return;
+    const bool known = r.format >= 0 && r.format < fmts.n;
+    const Format f = fmts.f[known ? r.format : 0];
+    bool ok = known && r.frames >= 0 && r.src16 >= 0 && r.out_count >= 0 && r.out_count <= ring_len && r.out_pos >= 0 && r.out_pos < ring_len &&
+              r.kmax0 >= 0 && r.r0 >= 0 && r.r0 < f.up && r.hist_valid >= 0 && r.hist_valid <= hist_len && (r.hist_side == 0 || r.hist_side == 1) &&
+              (long)r.src16 * 16 + (long)r.frames * (f.channels * emage_pcm::sample_bytes(f.pcm)) <= staged_bytes;
+    // without FINAL every frame an output reads must exist: the newest one the last output reads lies inside the staged frames
+    if (ok && !r.final && r.out_count > 0) ok = r.kmax0 + ((long)(r.out_count - 1) * f.down + r.r0) / f.up < r.frames;
+    if (!ok) {
+        if (threadIdx.x == 0 && blockIdx.y == 0) atomicOr(status, EMAGE_STREAM_BAD_RESAMPLE);
+        return;
+    }
+    const unsigned char* src = staged + (long)r.src16 * 16;
+    float* o = ring + (long)blockIdx.x * ring_len;
+    float* hist = history + (long)blockIdx.x * 2 * hist_len;
+    if (f.pcm == EMAGE_PCM_S16) resample_slot<EMAGE_PCM_S16>(r, f, src, taps, o, ring_len, hist, hist_len, s_resample);
+    else if (f.pcm == EMAGE_PCM_S24) resample_slot<EMAGE_PCM_S24>(r, f, src, taps, o, ring_len, hist, hist_len, s_resample);
+    else if (f.pcm == EMAGE_PCM_S32) resample_slot<EMAGE_PCM_S32>(r, f, src, taps, o, ring_len, hist, hist_len, s_resample);
+    else resample_slot<EMAGE_PCM_F32>(r, f, src, taps, o, ring_len, hist, hist_len, s_resample);
 }
 
 __global__ __launch_bounds__(THREADS) void windows_kernel(const float* __restrict__ ring, long ring_len, const int* __restrict__ table, int samples,
@@ -157,6 +256,43 @@ extern "C" int emage_stream_push(int audio_fmt, const void* staged, long staged_
     else
         hipLaunchKernelGGL(push_kernel<float>, dim3((unsigned)slots, SPANS), dim3(THREADS), 0, (hipStream_t)stream, (const float*)staged, staged_samples,
                            table, ring, ring_len, status);
+    return launch_status();
+}
+
+extern "C" int emage_stream_push_resample(const void* staged, long staged_bytes, const int* rs_table, int slots, const int* formats, int n_formats,
+                                          const float* taps, long taps_floats, float* ring, long ring_len, float* history, int hist_len, int* status,
+                                          void* stream) {
+    if (!staged || !rs_table || !formats || !taps || !ring || !history || !status) return EMAGE_EINVAL;
+    if (slots <= 0 || slots > 65535 || staged_bytes <= 0 || taps_floats <= 0 || ring_len <= 0 || ring_len > 0x7fffffffL || hist_len <= 0) return EMAGE_EINVAL;
+    if (n_formats <= 0 || n_formats > EMAGE_STREAM_MAX_FORMATS) return EMAGE_EINVAL;
+    if ((((uintptr_t)staged | (uintptr_t)taps) & 15) || (((uintptr_t)rs_table | (uintptr_t)ring | (uintptr_t)history | (uintptr_t)status) & 3)) return EMAGE_EINVAL;
+    Formats fmts{};
+    fmts.n = n_formats;
+    long lds_floats = 0;
+    for (int i = 0; i < n_formats; ++i) {
+        const int* w = formats + (long)i * EMAGE_STREAM_FORMAT_WORDS;
+        const Format f{w[0], w[1], w[2], w[3], w[4], w[5], w[6], w[7]};
+        if (f.pcm < EMAGE_PCM_S16 || f.pcm > EMAGE_PCM_F32 || f.channels < 1 || f.channels > 8) return EMAGE_EINVAL;
+        if (f.up <= 0 || f.down <= 0 || f.up > (1 << 16) || f.down > (1 << 16) || (f.up == f.down && f.up != 1)) return EMAGE_EINVAL;
+        long table = 0;
+        if (f.up == f.down) {
+            if (f.half != 0 || f.rpp != 1 || f.row_pitch != 0 || f.taps_offset != 0) return EMAGE_EINVAL;
+        } else {                                          // the geometry emage_audio_resample derives from (up, down), and its two LDS budgets
+            const int half = 10 * (f.up > f.down ? f.up : f.down), rpp = (2 * half + f.up) / f.up;
+            table = (long)f.up * (rpp | 1);
+            if (f.half != half || f.rpp != rpp || f.row_pitch != (rpp | 1)) return EMAGE_EINVAL;
+            if (f.taps_offset < 0 || (f.taps_offset & 3) || f.taps_offset + table > taps_floats || table * 4 > EMAGE_AUDIO_TAPS_LDS_BYTES) return EMAGE_EINVAL;
+        }
+        const long span_cap = ((long)(TILE - 1) * f.down + f.up - 1) / f.up + f.rpp + 1 + emage_pcm::SPAN_SLACK;
+        if (span_cap * 4 > EMAGE_AUDIO_SPAN_LDS_BYTES || f.rpp - 1 > hist_len) return EMAGE_EINVAL;
+        const long need = ((table + 3) & ~3L) + span_cap;
+        if (need > lds_floats) lds_floats = need;
+        fmts.f[i] = f;
+    }
+    static const hipError_t configured = hipFuncSetAttribute((const void*)push_resample_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    if (configured != hipSuccess) return (int)configured;
+    hipLaunchKernelGGL(push_resample_kernel, dim3((unsigned)slots, SPANS), dim3(THREADS), (size_t)lds_floats * sizeof(float), (hipStream_t)stream,
+                       (const unsigned char*)staged, staged_bytes, rs_table, fmts, taps, ring, ring_len, history, hist_len, status);
     return launch_status();
 }
 

@@ -1692,7 +1692,7 @@ def copy_segments(src, dst, segments, width_bytes, max_rows, status):
 # ---- the streaming batch (include/emage_hip.h: emage_stream_push ...) -----------------------------------------------------------------
 STREAM_WORDS = 12                                     # EMAGE_STREAM_WORDS and the word indices below: the per-tick table, int32 words per slot
 STREAM_FIELDS = ("ready", "audio_read", "audio_write", "push_count", "push_src", "code_write", "seg_read", "seg_valid", "emit_row", "emit_count")
-STREAM_STATUS_TEXT = "1: a push outside the staged buffer / ring; 2: a window outside its ring; 4: a commit row outside the code rings; 8: an emit range outside the segment"
+STREAM_STATUS_TEXT = "1: a push outside the staged buffer / ring; 2: a window outside its ring; 4: a commit row outside the code rings; 8: an emit range outside the segment; 16: a resample row outside the staged buffer / ring / history / declared formats"
 
 
 def stream_table(rows, *, ring_len, staged_samples, samples, ring_codes, seg_len, out_rows):
@@ -1750,6 +1750,134 @@ def stream_push(staged, table, ring, status):
     for t in (staged, table, status):
         assert t.device == ring.device, "stream_push: every tensor on one device"
     _stream_push(staged, table, ring, status)
+    return ring
+
+
+# the second per-tick table, of `stream_push_resample` alone (EMAGE_STREAM_RS_*), and the format descriptors (EMAGE_STREAM_FORMAT_WORDS ints each)
+STREAM_RS_WORDS = 12
+STREAM_RS_FIELDS = ("frames", "src16", "format", "final", "out_count", "out_pos", "kmax0", "r0", "hist_valid", "hist_side")
+STREAM_BAD_RESAMPLE = 16
+STREAM_MAX_FORMATS = 8
+STREAM_FORMAT_WORDS = 8
+STREAM_FORMAT_FIELDS = ("pcm", "channels", "up", "down", "half", "rpp", "row_pitch", "taps_offset")
+
+
+def stream_formats(audio_inputs, out_rate=16000):
+    """The formats a `stream_push_resample` launch may meet, fixed for the life of a batch: `audio_inputs` (1 .. STREAM_MAX_FORMATS
+    `audio.AudioInput`s) -> (descriptors (n, STREAM_FORMAT_WORDS) int32, taps: the phase rows of every format end to end, each from a
+    multiple of 4 floats (1-D float32 numpy, at least 4 floats), hist_len: the frames of history a slot keeps, max(rpp) - 1 and at least 1).
+    ValueError for what the kernel does not take: channels outside 1..8, a rate pair beyond the two LDS budgets of `emage_audio_resample`."""
+    import numpy as np
+    from . import audio
+    inputs = tuple(audio_inputs)
+    if not 1 <= len(inputs) <= STREAM_MAX_FORMATS:
+        raise ValueError(f"stream_formats: 1 .. {STREAM_MAX_FORMATS} audio inputs, not {len(inputs)}")
+    desc, rows, offset = np.zeros((len(inputs), STREAM_FORMAT_WORDS), dtype=np.int32), [], 0
+    for i, a in enumerate(inputs):
+        if not isinstance(a, audio.AudioInput):
+            raise ValueError(f"stream_formats: {a!r} is not an AudioInput")
+        if int(a.rate) <= 0 or not 1 <= int(a.channels) <= 8:
+            raise ValueError(f"stream_formats: {a}: a positive rate and 1 .. 8 channels")
+        up, down = audio.rate_ratio(a.rate, out_rate)
+        if max(up, down) > 1 << 16:
+            raise ValueError(f"stream_formats: {a}: the rate pair {up} / {down} is beyond 65536")
+        half, rpp, pitch, mine = 0, 1, 0, 0
+        if up != down:
+            half = audio.half_length(up, down)
+            rpp, pitch, mine = -(-(2 * half + 1) // up), audio.phase_pitch(2 * half + 1, up), offset
+            if up * pitch * 4 > _lib.AUDIO_TAPS_LDS_BYTES:
+                raise ValueError(f"stream_formats: {a}: {up} phase rows of {pitch} taps exceed the kernel's {_lib.AUDIO_TAPS_LDS_BYTES} bytes of LDS")
+            packed = audio.pack_taps(audio.resample_filter(up, down), up).reshape(-1)
+            rows.append(np.concatenate([packed, np.zeros(-len(packed) % 4, dtype=np.float32)]))
+            offset += len(rows[-1])
+        span = ((_lib.AUDIO_TILE - 1) * down + up - 1) // up + rpp + 1 + 16        # span_cap of csrc/audio.hip (its slack is 16 floats): the same rates pass
+        if span * 4 > _lib.AUDIO_SPAN_LDS_BYTES:
+            raise ValueError(f"stream_formats: {a}: a tile's input span of {span} frames exceeds the kernel's {_lib.AUDIO_SPAN_LDS_BYTES} bytes of LDS")
+        desc[i] = [audio.PCM_FORMATS[a.fmt], int(a.channels), up, down, half, rpp, pitch, mine]
+    taps = np.concatenate(rows) if rows else np.zeros(4, dtype=np.float32)
+    return desc, taps, max(int(desc[:, 5].max()) - 1, 1)
+
+
+def stream_resample_table(rows, *, formats, ring_len, staged_bytes, hist_len):
+    """The per-tick table of `stream_push_resample`, checked on the host.  `rows`: one dict per slot (None: nothing to do) holding the session's
+    ABSOLUTE counts — Python integers of any size — from which the int32 words, all relative, are formed here:
+      frames, src (byte offset of the slot's chunk in the staged buffer, a multiple of 16), format (row of `formats`, the descriptors of
+      `stream_formats`), final, frames_before (frames of the session pushed in earlier launches), outputs_before (= m0: outputs written by
+      them), out_count, hist_side.
+    Output m0 must not have been computable before (its newest frame is a staged one or later), without `final` the last output must read
+    staged frames only, with it the outputs end at ceil(frames up / down); every range lies inside its buffer and no two slots' chunks
+    overlap -> (slots, STREAM_RS_WORDS) int32 numpy array."""
+    import numpy as np
+    fields = ("frames", "src", "format", "final", "frames_before", "outputs_before", "out_count", "hist_side")
+    formats = np.asarray(formats).reshape(-1, STREAM_FORMAT_WORDS)
+    tab = np.zeros((len(rows), STREAM_RS_WORDS), dtype=np.int32)
+    spans = []
+    for k, row in enumerate(rows):
+        if row is None:
+            continue
+        unknown = set(row) - set(fields)
+        if unknown:
+            raise ValueError(f"stream_resample_table: slot {k}: unknown fields {sorted(unknown)}")
+        r = {f: int(row.get(f, 0)) for f in fields}
+        if r["frames"] == 0 and r["out_count"] == 0:
+            continue
+        if not 0 <= r["format"] < len(formats):
+            raise ValueError(f"stream_resample_table: slot {k}: format {r['format']} outside the {len(formats)} declared")
+        pcm, channels, up, down, half = (int(v) for v in formats[r["format"]][:5])
+        fb = channels * (2, 3, 4, 4)[pcm]
+        if r["frames"] < 0 or r["src"] < 0 or r["src"] % 16 or r["src"] + r["frames"] * fb > staged_bytes:
+            raise ValueError(f"stream_resample_table: slot {k}: {r['frames']} frames of {fb} bytes at byte {r['src']} do not fit the staged buffer of "
+                             f"{staged_bytes} bytes from a 16-byte boundary")
+        if not (0 <= r["out_count"] <= ring_len and r["frames_before"] >= 0 and r["outputs_before"] >= 0 and r["hist_side"] in (0, 1)):
+            raise ValueError(f"stream_resample_table: slot {k}: {r['out_count']} outputs behind {r['outputs_before']} into a ring of {ring_len}, "
+                             f"{r['frames_before']} frames before, history side {r['hist_side']}")
+        base = r["outputs_before"] * down + half
+        kmax0, r0 = base // up - r["frames_before"], base % up
+        last = kmax0 + ((r["out_count"] - 1) * down + r0) // up
+        total = r["frames_before"] + r["frames"]
+        if kmax0 < 0:
+            raise ValueError(f"stream_resample_table: slot {k}: output {r['outputs_before']} reads no frame of this push or later: it was due before")
+        if r["out_count"] and (last >= r["frames"] if not r["final"] else r["outputs_before"] + r["out_count"] > -(-total * up // down)):
+            raise ValueError(f"stream_resample_table: slot {k}: {r['out_count']} outputs from {r['outputs_before']} read beyond the {total} frames pushed"
+                             + (" (final)" if r["final"] else ""))
+        words = [r["frames"], r["src"] // 16, r["format"], int(bool(r["final"])), r["out_count"], r["outputs_before"] % ring_len, kmax0, r0,
+                 min(r["frames_before"], hist_len), r["hist_side"]]
+        if max(words) > 0x7fffffff:
+            raise ValueError(f"stream_resample_table: slot {k}: a word beyond int32: {words}")
+        tab[k, :len(words)] = words
+        if r["frames"]:
+            spans.append((r["src"], r["src"] + r["frames"] * fb))
+    spans.sort()
+    if any(lo < prev_hi for (_l, prev_hi), (lo, _h) in zip(spans, spans[1:])):
+        raise ValueError("stream_resample_table: two slots' chunks overlap in the staged buffer")
+    return tab
+
+
+@_op("stream_push_resample", "(Tensor staged, Tensor rs_table, int[] formats, Tensor taps, Tensor(a!) ring, Tensor(b!) history, Tensor(c!) status) -> ()")
+def _stream_push_resample(staged, rs_table, formats, taps, ring, history, status):
+    arr = (C.c_int * len(formats))(*formats)
+    check(_lib.load().emage_stream_push_resample(_ptr(staged), staged.numel(), _ptr(rs_table), ring.shape[0], arr, len(formats) // STREAM_FORMAT_WORDS,
+                                                 _ptr(taps), taps.numel(), _ptr(ring), ring.shape[1], _ptr(history), history.shape[2], _ptr(status),
+                                                 _stream()), "stream_push_resample")
+
+
+def stream_push_resample(staged, rs_table, formats, taps, ring, history, status):
+    """`stream_push` for PCM at any rate and layout, one launch: each slot's staged frames (`staged`: 1-D uint8, every slot's chunk from a
+    16-byte boundary) are decoded, down-mixed and run through the polyphase filter of `audio_resample`, continued from the slot's `history`
+    (slots, 2, hist_len) float32, into its ring — bit for bit the samples `audio_resample` gives for the session's whole PCM.  rs_table:
+    `stream_resample_table`; formats / taps: `stream_formats` (the descriptors as they are, the taps on the device).  See
+    include/emage_hip.h: emage_stream_push_resample."""
+    _dev(ring)
+    words = [int(v) for v in (formats.reshape(-1).tolist() if hasattr(formats, "reshape") else formats)]
+    assert words and len(words) % STREAM_FORMAT_WORDS == 0
+    assert staged.dtype == torch.uint8 and staged.dim() == 1 and staged.is_contiguous() and staged.numel() > 0
+    assert taps.dtype == torch.float32 and taps.dim() == 1 and taps.is_contiguous() and taps.numel() > 0
+    assert ring.dtype == torch.float32 and ring.dim() == 2 and ring.is_contiguous() and status.dtype == torch.int32 and status.numel() == 1
+    assert history.dtype == torch.float32 and history.dim() == 3 and history.is_contiguous() and tuple(history.shape[:2]) == (ring.shape[0], 2)
+    assert rs_table.dtype == torch.int32 and tuple(rs_table.shape) == (ring.shape[0], STREAM_RS_WORDS) and rs_table.is_contiguous()
+    for t in (staged, rs_table, taps, history, status):
+        assert t.device == ring.device, "stream_push_resample: every tensor on one device"
+    _stream_push_resample(staged, rs_table, words, taps, ring, history, status)
     return ring
 
 

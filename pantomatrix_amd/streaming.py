@@ -17,8 +17,17 @@ computes for the same audio.  Three rules make that so (DESIGN.md derives them):
 3. The translation CONTINUES.  `emage_stream_emit` applies the step of `emage_velocity_to_position` (csrc/vel_step.h, shared) from the
    position carried per slot, so the streamed translation is one scan over the whole velocity sequence, bit for bit.
 
+A batch built with ``audio_inputs=(AudioInput(48000, 1, "s16"), ...)`` takes each session's PCM as its source produces it — any rate, 1-8
+channels, 16 / 24 / 32-bit integer or float32 — and resamples it inside the tick (`ops.stream_push_resample`), with a fourth rule:
+
+4. WHICH samples a slot holds.  The offline front end (`ops.audio_resample`) computes y[m] = sum_k h[m down + half - k up] x[k]; output m
+   reads frames up to (m down + half) // up, so after n frames the first `available(n)` = ceil((n up - half) / down) outputs are FINAL —
+   they no longer depend on what follows, nor on where the pushes were cut — and only those count as `pushed`.  The 10-20 outputs behind
+   them wait for more input or for `end()`, which computes them against zeros: the offline right edge.  The ring then holds, bit for
+   bit, the offline kernel's samples, and rules 1-3 apply to them unchanged.
+
 * ``StreamBatch``  the slots, their device state and the tick;
-* ``Session``      one live stream: `push(pcm)`, `close()`;
+* ``Session``      one live stream: `push(pcm)`, `end()`, `close()`;
 * ``Emitted``      what a session receives: poses (n, 165), expressions (n, 100), trans (n, 3), codes {part: (n,) int64}."""
 from __future__ import annotations
 
@@ -27,10 +36,13 @@ from typing import NamedTuple
 import numpy as np
 import torch
 
-from . import ops, synthetic
+from . import audio, ops, synthetic
+from .audio import available                            # rule 4: the outputs that are final after n input frames
 from .recordings import MODEL_SR, SEED_DIMS, SPF, frames_of, identity_seed
 
 STATUS_TEXT = ops.STREAM_STATUS_TEXT
+_SAMPLE_BYTES = {"s16": 2, "s24": 3, "s32": 4, "f32": 4}
+_PUSH_DTYPES = {"s16": np.int16, "s24": np.uint8, "s32": np.int32, "f32": np.float32}
 
 
 class Emitted(NamedTuple):
@@ -63,16 +75,24 @@ def tail_of(n_samples, pre=4, hop=60):
 
 
 class Session:
-    """One live stream in one slot of a `StreamBatch`.  pushed: samples accepted so far; windows: full windows run; emitted: frames handed out."""
+    """One live stream in one slot of a `StreamBatch`.  pushed: 16 kHz samples the slot holds; windows: full windows run; emitted: frames
+    handed out; frames_in: raw frames accepted (= pushed, unless the batch resamples: then pushed counts the FINAL outputs, rule 4)."""
 
-    def __init__(self, batch, slot, speaker_id):
+    def __init__(self, batch, slot, speaker_id, fmt=None):
         self.batch, self.slot, self.speaker_id = batch, slot, speaker_id
-        self.pushed = self.windows = self.emitted = 0
-        self.closed = False
+        self.pushed = self.windows = self.emitted = self.frames_in = 0
+        self.closed = self.ended = False
+        self.fmt = fmt                                      # row of the batch's declared audio inputs (None: the 16 kHz path)
         self._staged = []                                   # host chunks not on the device yet
+        self._sent = self._written = 0                      # resampling batch: frames uploaded / outputs written to the ring so far
 
     def push(self, pcm):
         self.batch._push(self, pcm)
+
+    def end(self):
+        """No more input.  In a resampling batch the outputs held back for lack of later frames (rule 4) are released — computed against
+        zeros, the offline right edge — with the next launch; that can make one more full window ready.  Idempotent; `close()` calls it."""
+        self.batch._end(self)
 
     def close(self):
         return self.batch._close(self)
@@ -94,9 +114,15 @@ class StreamBatch:
 
     audio_format: "f32" or "s16" (decoded x * 2^-15 on the device) — the dtype `push` takes.  max_seconds: the longest session; with
     max_push (the most samples a session may hold beyond what its next window needs) it sizes the ring: a push that does not fit raises.
-    Weights are fixed for the life of the batch: `step()` raises once the model's version stamp has moved."""
+    Weights are fixed for the life of the batch: `step()` raises once the model's version stamp has moved.
 
-    def __init__(self, model, vq_model, slots=8, audio_format="f32", max_seconds=3600, use_graph=True, max_push=3 * MODEL_SR):
+    audio_inputs: None, or the `audio.AudioInput`s (rate, channels, sample format) sessions of this batch may push — fixed here, their filters
+    uploaded once.  The tick's first launch is then `ops.stream_push_resample`: each slot's raw PCM is decoded, down-mixed and resampled to
+    16 kHz on the device, filter state carried per slot, so that the ring holds bit for bit what `ops.audio_resample` gives for the
+    session's whole PCM (rule 4); `open(audio_input=...)` picks a session's format, `push` takes (n, channels) frames of it (packed 24-bit:
+    (n, 3 * channels) uint8).  `audio_format` is not used then; max_push and max_seconds stay in 16 kHz samples."""
+
+    def __init__(self, model, vq_model, slots=8, audio_format="f32", max_seconds=3600, use_graph=True, max_push=3 * MODEL_SR, audio_inputs=None):
         dev = model.device
         model._require_device(dev)                          # an MI355X: there is no CPU path (the host tests lift this check over stand-in ops)
         on_gpu = dev.type == "cuda"
@@ -119,6 +145,21 @@ class StreamBatch:
         self.audio_dtype = torch.float32 if audio_format == "f32" else torch.int16
         self.parts = [p for p, r in model._routes().items() if r]
         s, n_p = self.slots, len(self.parts)
+        self.audio_inputs = None if audio_inputs is None else tuple(audio_inputs)
+        staged_len = s * self.ring_len
+        if self.audio_inputs is not None:
+            self.formats, taps, self.hist_len = ops.stream_formats(self.audio_inputs, MODEL_SR)      # ValueError for what the kernel does not take
+            self.ratios = [audio.rate_ratio(a.rate, MODEL_SR) for a in self.audio_inputs]
+            self.frame_bytes = [a.channels * _SAMPLE_BYTES[a.fmt] for a in self.audio_inputs]
+            # the most a slot can have staged: the frames behind ring_len outputs plus those held back, in the format with the most bytes per
+            # 16 kHz sample; every slot's chunk starts on a 16-byte boundary
+            worst = max(((self.ring_len * down + audio.stream_half(up, down)) // up + 2) * fb for (up, down), fb in zip(self.ratios, self.frame_bytes))
+            self.audio_dtype, staged_len = torch.uint8, s * (-(-worst // 16) * 16)
+            self.taps = torch.from_numpy(taps).to(dev)
+            self.history = torch.zeros(s, 2, self.hist_len, device=dev)        # per slot two sides: a push reads one and writes the other
+            self.hist_side = [0] * s
+            self.rs_table = torch.zeros(s, ops.STREAM_RS_WORDS, dtype=torch.int32, device=dev)
+            self.rs_table_host = torch.zeros(s, ops.STREAM_RS_WORDS, dtype=torch.int32, pin_memory=on_gpu)
         # ---- device state ----
         self.ring = torch.zeros(s, self.ring_len, device=dev)
         self.code_ring = torch.zeros(n_p, s, self.ring_codes, dtype=torch.int64, device=dev)
@@ -126,8 +167,8 @@ class StreamBatch:
         self.carry = torch.zeros(s, 3, device=dev)
         self.speaker_id = torch.zeros(s, 1, dtype=torch.long, device=dev)
         # ---- per tick ----
-        self.staged = torch.zeros(s * self.ring_len, dtype=self.audio_dtype, device=dev)
-        self.staged_host = torch.zeros(s * self.ring_len, dtype=self.audio_dtype, pin_memory=on_gpu)
+        self.staged = torch.zeros(staged_len, dtype=self.audio_dtype, device=dev)
+        self.staged_host = torch.zeros(staged_len, dtype=self.audio_dtype, pin_memory=on_gpu)
         self.table = torch.zeros(s, ops.STREAM_WORDS, dtype=torch.int32, device=dev)
         self.table_host = torch.zeros(s, ops.STREAM_WORDS, dtype=torch.int32, pin_memory=on_gpu)
         self.win_audio = torch.zeros(s, self.window * SPF, device=dev)
@@ -180,14 +221,25 @@ class StreamBatch:
         return (self.model._version_stamp(),) + tuple(m._version_stamp() for m in self.vq._models())
 
     # ---- sessions -----------------------------------------------------------------------------------------------------------------------
-    def open(self, speaker_id=0, seed=None, ref_trans=None):
+    def open(self, speaker_id=0, seed=None, ref_trans=None, audio_input=None):
         """A new session in the lowest free slot (raises when there is none).  seed (4, 337) / ref_trans (3,): as `RecordingSet` seeds a
-        recording; None: identity pose, zero translation (test_emage_audio.py)."""
+        recording; None: identity pose, zero translation (test_emage_audio.py).  audio_input: in a batch built with `audio_inputs`, the one
+        of them this session pushes (None: the first).  The session starts with an empty filter history, whatever the slot held before."""
         free = [k for k, s in enumerate(self.sessions) if s is None]
         if not free:
             raise RuntimeError(f"StreamBatch: all {self.slots} slots are in use")
         if not 0 <= int(speaker_id) < int(self.model.config.speaker_dims):
             raise ValueError(f"StreamBatch.open: speaker id {speaker_id} outside [0, {int(self.model.config.speaker_dims)})")
+        fmt = None
+        if self.audio_inputs is None:
+            if audio_input is not None:
+                raise ValueError("StreamBatch.open: audio_input needs a batch built with audio_inputs=(...)")
+        elif audio_input is None:
+            fmt = 0
+        elif audio_input in self.audio_inputs:
+            fmt = self.audio_inputs.index(audio_input)
+        else:
+            raise ValueError(f"StreamBatch.open: {audio_input} is not one of the batch's declared audio inputs {self.audio_inputs}")
         k = free[0]
         seed = self._ident if seed is None else torch.as_tensor(seed, dtype=torch.float32)
         ref_trans = torch.zeros(3) if ref_trans is None else torch.as_tensor(ref_trans, dtype=torch.float32)
@@ -196,13 +248,48 @@ class StreamBatch:
         self.seeds[k].copy_(seed)                           # stream-ordered copies into fixed addresses: the next replay reads them
         self.carry[k].copy_(ref_trans)
         self.speaker_id[k].fill_(int(speaker_id))
-        self.sessions[k] = s = Session(self, k, int(speaker_id))
+        self.sessions[k] = s = Session(self, k, int(speaker_id), fmt)
         return s
+
+    def _fits(self, s, pushed, n):
+        """Raises unless a session that then holds `pushed` 16 kHz samples fits max_seconds and its slot's ring."""
+        if pushed > self.max_samples:
+            raise ValueError(f"Session.push: {pushed} samples exceed max_seconds ({self.max_samples} samples)")
+        if pushed - self.hop * SPF * s.windows > self.ring_len:
+            raise ValueError(f"Session.push: {n} samples do not fit: the slot would hold {pushed - self.hop * SPF * s.windows} samples behind its "
+                             f"next window, its ring {self.ring_len} (call step(), or build the batch with a larger max_push)")
+
+    def _push_frames(self, s, a):
+        """`_push` of a resampling batch: `a` holds frames of the session's declared format."""
+        inp, (up, down) = self.audio_inputs[s.fmt], self.ratios[s.fmt]
+        width = inp.channels * (3 if inp.fmt == "s24" else 1)
+        if a.ndim == 1 and width == 1:
+            a = a[:, None]
+        if a.ndim != 2 or a.shape[1] != width or a.dtype != _PUSH_DTYPES[inp.fmt]:
+            raise ValueError(f"Session.push: this session takes {inp}: (n, {width}) {np.dtype(_PUSH_DTYPES[inp.fmt]).name} frames, not {a.shape} {a.dtype}")
+        n = int(a.shape[0])
+        # the ring and max_seconds are checked against what `end()` would release too, so that ending a session never overflows either
+        self._fits(s, audio.out_length(s.frames_in + n, up, down), n)
+        if n:
+            s._staged.append(np.ascontiguousarray(a).view(np.uint8).reshape(-1))
+            s.frames_in += n
+            s.pushed = available(s.frames_in, up, down)
+
+    def _end(self, s):
+        if s.closed:
+            raise RuntimeError("Session.end: the session is closed")
+        if not s.ended and s.fmt is not None:
+            s.pushed = audio.out_length(s.frames_in, *self.ratios[s.fmt])
+        s.ended = True
 
     def _push(self, s, pcm):
         if s.closed:
             raise RuntimeError("Session.push: the session is closed")
+        if s.ended:
+            raise RuntimeError("Session.push: the session's input has ended")
         a = pcm.detach().cpu().numpy() if torch.is_tensor(pcm) else np.asarray(pcm)
+        if s.fmt is not None:
+            return self._push_frames(s, a)
         if a.ndim != 1:
             raise ValueError(f"Session.push: a 1-D chunk of samples, not {a.shape}")
         if self.audio_dtype == torch.int16:
@@ -213,14 +300,11 @@ class StreamBatch:
         elif a.dtype != np.float32:
             raise ValueError(f"Session.push: float32 or int16 samples, not {a.dtype}")
         n = int(a.shape[0])
-        if s.pushed + n > self.max_samples:
-            raise ValueError(f"Session.push: {s.pushed + n} samples exceed max_seconds ({self.max_samples} samples)")
-        if s.pushed + n - self.hop * SPF * s.windows > self.ring_len:
-            raise ValueError(f"Session.push: {n} samples do not fit: the slot would hold {s.pushed + n - self.hop * SPF * s.windows} samples behind its "
-                             f"next window, its ring {self.ring_len} (call step(), or build the batch with a larger max_push)")
+        self._fits(s, s.pushed + n, n)
         if n:
             s._staged.append(np.ascontiguousarray(a))
             s.pushed += n
+            s.frames_in += n
 
     # ---- the tick ---------------------------------------------------------------------------------------------------------------------------
     def _rows(self, ready):
@@ -231,7 +315,11 @@ class StreamBatch:
             if s is None:
                 continue
             row = {}
-            if s._staged:
+            if s.fmt is not None:
+                lo, resample = self._resample_row(s, host, lo)
+                if resample is not None:
+                    row.update(resample=resample)
+            elif s._staged:
                 n = sum(len(c) for c in s._staged)
                 np.concatenate(s._staged, out=host[lo:lo + n])
                 row.update(push_count=n, push_src=lo, audio_write=(s.pushed - n) % self.ring_len)
@@ -246,7 +334,32 @@ class StreamBatch:
             rows[k] = row or None
         return rows, lo
 
+    def _resample_row(self, s, host, lo):
+        """The resampling batch's share of `_rows`: the session's staged frames go to the staging buffer from byte `lo` (a multiple of 16),
+        its row of the second table says which outputs they complete (rule 4) -> (the next free 16-byte boundary, that row or None)."""
+        k = s.slot
+        nbytes = sum(len(c) for c in s._staged)
+        frames = nbytes // self.frame_bytes[s.fmt]
+        upto = s.pushed                                     # available(frames_in), or out_length(frames_in) once ended: all staged frames go now
+        if not frames and upto == s._written:
+            return lo, None
+        if frames:
+            np.concatenate(s._staged, out=host[lo:lo + nbytes])
+            s._staged = []
+        row = dict(frames=frames, src=lo, format=s.fmt, final=int(s.ended), frames_before=s._sent, outputs_before=s._written,
+                   out_count=upto - s._written, hist_side=self.hist_side[k])
+        if frames:
+            self.hist_side[k] ^= 1                          # the launch writes the other side: the slot's next push reads that one
+        s._sent, s._written = s._sent + frames, upto
+        return lo + -(-nbytes // 16) * 16, row
+
     def _upload(self, rows, staged=0):
+        if self.audio_inputs is not None:                  # a resampling batch: the pushes travel in the second table, under the key "resample"
+            rs_rows = [r.get("resample") if r else None for r in rows]
+            rows = [{f: v for f, v in r.items() if f != "resample"} if r else None for r in rows]
+            self.rs_table_host.copy_(torch.from_numpy(ops.stream_resample_table(rs_rows, formats=self.formats, ring_len=self.ring_len,
+                                                                                 staged_bytes=self.staged.numel(), hist_len=self.hist_len)))
+            self.rs_table.copy_(self.rs_table_host, non_blocking=True)
         tab = ops.stream_table(rows, ring_len=self.ring_len, staged_samples=self.staged.numel(), samples=self.window * SPF,
                                ring_codes=self.ring_codes, seg_len=self.seg_len, out_rows=self.hop)
         self.table_host.copy_(torch.from_numpy(tab))
@@ -257,10 +370,16 @@ class StreamBatch:
     def _codes_of(self, buf):
         return {p: buf[j] for j, p in enumerate(self.parts)}
 
+    def _launch_push(self):
+        if self.audio_inputs is None:
+            ops.stream_push(self.staged, self.table, self.ring, self.status)
+        else:
+            ops.stream_push_resample(self.staged, self.rs_table, self.formats, self.taps, self.ring, self.history, self.status)
+
     def _tick(self):
         """The launches of one tick: no host state, so it is capturable."""
         model, vq, s, w, pre = self.model, self.vq, self.slots, self.window, self.pre
-        ops.stream_push(self.staged, self.table, self.ring, self.status)
+        self._launch_push()
         ops.stream_windows(self.ring, self.table, self.win_audio, self.status)
         model.health_pending = pending = []
         try:
@@ -329,6 +448,8 @@ class StreamBatch:
         zero-padded exactly where the reference pads it — and frames [emitted, frames_out) -> Emitted.  Frees the slot."""
         if s.closed:
             raise RuntimeError("Session.close: the session is closed")
+        if s.fmt is not None:
+            self._end(s)                                                    # releases the outputs held back: one more full window may be ready
         if s.ready:
             raise RuntimeError("Session.close: a full window is still pending — call step() first")
         rounds, t = tail_of(s.pushed, self.pre, self.hop)
@@ -342,9 +463,9 @@ class StreamBatch:
         """The device side of `close()`: the tail window of `t` frames (0: none) behind `rounds` full windows, the last decode, the emit."""
         model, vq, dev, k, pre, hop = self.model, self.vq, self.device, s.slot, self.pre, self.hop
         rows, staged = self._rows([])
-        if staged:                                                          # PCM pushed since the last tick: a push-only launch
+        if staged or any(r and "resample" in r for r in rows):             # PCM pushed since the last tick (or a filter's tail to flush): a push-only launch
             self._upload(rows, staged)
-            ops.stream_push(self.staged, self.table, self.ring, self.status)
+            self._launch_push()
         frames_out = hop * rounds + t
         lo = max(0, hop * rounds - 2 * self.lag) if rounds else 0           # first code of the last decode: R behind the first frame to emit
         length, n_emit, n_p = frames_out - lo, frames_out - s.emitted, len(self.parts)

@@ -9,7 +9,10 @@ them live and one window behind their audio — every tick each session pushes t
 `decode_ms` is the eager segment decode + emit alone (`_decode_segments` at B = S, T = 60 + 2 lag, and `emage_stream_emit`), and
 `decode_share_of_eager_tick` its share of the eager tick — a share of the replay is not measured here (it needs a kernel trace).
 Wall time per tick around work that ends in a device synchronise (`step()` ends in one); the arms alternate, `--runs` times each, and the
-median and the run-to-run spread are reported.  Writes one JSON document to `--out` and prints it."""
+median and the run-to-run spread are reported.  Writes one JSON document to `--out` and prints it.
+`--audio-input RATE:CH:FMT` measures something else: the captured tick of a batch built with `audio_inputs=(that input,)` — raw PCM staged,
+`stream_push_resample` as the first launch — against the captured 16 kHz f32 tick of the same tree, the two interleaved on the same device,
+into profiles/stream_resample_bench.json.  The kernel's own time needs a kernel trace of such a run (`rocprofv3 --kernel-trace --stats`)."""
 import argparse
 import json
 import os
@@ -48,16 +51,114 @@ class Live:
         assert len(out) == self.sb.slots and all(e.poses.shape[0] == 60 for e in out.values())
 
 
+class LiveRaw:
+    """`Live` for a batch that resamples: S sessions fed raw PCM of one `AudioInput`, each tick the frames that make the next window final."""
+
+    def __init__(self, sb, base, inp):
+        from pantomatrix_amd import audio, streaming
+        self.sb, (self.up, self.down) = sb, audio.rate_ratio(inp.rate, 16000)
+        self.half = audio.stream_half(self.up, self.down)
+        t = np.arange(int((len(base) - 1) * self.down / self.up)) * (self.up / self.down)          # the 16 kHz waveform, linearly interpolated to the rate
+        x = np.interp(t, np.arange(len(base)), base).astype(np.float32)
+        if inp.fmt == "f32":
+            pcm = x[:, None]
+        elif inp.fmt == "s16":
+            pcm = np.round(x * 32767.0).clip(-32768, 32767).astype(np.int16)[:, None]
+        elif inp.fmt == "s32":
+            pcm = np.round(x.astype(np.float64) * (2.0 ** 31 - 1)).astype(np.int64).clip(-2 ** 31, 2 ** 31 - 1).astype(np.int32)[:, None]
+        else:
+            v = np.round(x * 8388607.0).astype(np.int64) & 0xFFFFFF
+            pcm = np.stack([v & 0xFF, (v >> 8) & 0xFF, (v >> 16) & 0xFF], axis=-1).astype(np.uint8)[:, None, :]
+        pcm = np.repeat(pcm, inp.channels, axis=1).reshape(len(x), -1)                               # every channel the same signal
+        skip = 1009 * self.down // self.up
+        self.waves = [pcm[skip * k:] for k in range(sb.slots)]
+        self.sessions = [sb.open() for _ in range(sb.slots)]
+        self.frames_per_tick = 0
+        self.tick(first=streaming.window_need(0))
+
+    def frames_for(self, need):
+        """The fewest frames whose FINAL outputs reach `need` samples: n up - half > (need - 1) down."""
+        return ((need - 1) * self.down + self.half) // self.up + 1
+
+    def tick(self, first=None):
+        from pantomatrix_amd import streaming
+        for s, w in zip(self.sessions, self.waves):
+            upto = self.frames_for(first or streaming.window_need(s.windows))
+            self.frames_per_tick = upto - s.frames_in
+            s.push(w[s.frames_in:upto])
+        out = self.sb.step()
+        assert len(out) == self.sb.slots and (first or all(e.poses.shape[0] == 60 for e in out.values()))
+
+
+def resample_arm(args, inp):
+    """`--audio-input`: the captured tick with that input against the 16 kHz f32 tick of the same tree, interleaved on the same device."""
+    from pantomatrix_amd import streaming, synthetic
+    from tools import workloads
+    model, vq = workloads.product_models(precision=args.precision, device="cuda")
+    ticks = 2 + args.runs * (args.steps + 1)
+    seconds = (ticks + 2) * HOP_SAMPLES // 16000 + 4
+    base = synthetic.synthetic_audio(1, seconds * 16000 + 1009 * max(args.slots))[0].numpy()
+    parent = {}
+    try:
+        with open(os.path.join(ROOT, "profiles", "stream_bench.json")) as f:
+            parent = {k: v["tick_ms"]["replay"] for k, v in json.load(f)["slots"].items()}
+    except (OSError, KeyError, ValueError):
+        pass
+    result = {"what": f"one captured tick of StreamBatch, every slot live, fed {inp} (stream_push_resample) vs fed 16 kHz f32 (stream_push): same tree, "
+                      "arms interleaved; parent_replay_tick_ms is the replay tick recorded in profiles/stream_bench.json",
+              "commit": args.commit, "audio_input": {"rate": inp.rate, "channels": inp.channels, "fmt": inp.fmt},
+              "config": {"precision": args.precision, "ticks_per_run": args.steps, "runs": args.runs, "samples_per_slot_and_tick": HOP_SAMPLES}, "slots": {}}
+    for n in args.slots:
+        live = {"f32_16k": Live(streaming.StreamBatch(model, vq, slots=n, max_seconds=seconds, use_graph=True), base),
+                "resample": LiveRaw(streaming.StreamBatch(model, vq, slots=n, max_seconds=seconds, use_graph=True, audio_inputs=(inp,)), base, inp)}
+        ms = {k: [] for k in live}
+        for _ in range(args.runs):
+            for name, l in live.items():
+                l.tick()
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for _ in range(args.steps):
+                    l.tick()
+                torch.cuda.synchronize()
+                ms[name].append(1e3 * (time.perf_counter() - t0) / args.steps)
+        med = {k: float(np.median(v)) for k, v in ms.items()}
+        sb = live["resample"].sb
+        result["slots"][str(n)] = {"tick_ms": {k: summary(v) for k, v in ms.items()}, "resample_minus_f32_ms": round(med["resample"] - med["f32_16k"], 3),
+                                   "resample_over_f32": round(med["resample"] / med["f32_16k"], 3), "parent_replay_tick_ms": parent.get(str(n)),
+                                   "frames_per_slot_and_tick": live["resample"].frames_per_tick,
+                                   "staged_bytes_per_tick": n * live["resample"].frames_per_tick * sb.frame_bytes[0], "history_frames": sb.hist_len}
+        for l in live.values():
+            for s in l.sessions:
+                s._staged, s.closed = [], True                              # dropped, not closed: the tail of a benchmark session is nobody's output
+        del live, sb
+        torch.cuda.empty_cache()
+    return result
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--slots", type=int, nargs="+", default=[1, 8, 32, 64])
     ap.add_argument("--steps", type=int, default=40, help="ticks per timed run")
     ap.add_argument("--runs", type=int, default=5)
     ap.add_argument("--precision", default="f16x3")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "stream_bench.json"))
+    ap.add_argument("--out", default=None, help="default: profiles/stream_bench.json, or profiles/stream_resample_bench.json with --audio-input")
     ap.add_argument("--commit", default=None, help="recorded in the document (the measured tree is not always a git checkout)")
+    ap.add_argument("--audio-input", default=None, metavar="RATE:CH:FMT", help="measure the resampling tick for this input (e.g. 44100:2:s16) "
+                    "against the 16 kHz f32 tick instead of the three arms above")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "bench_stream needs an MI355X: none of its figures means anything on a CPU"
+    if args.audio_input:
+        from pantomatrix_amd.audio import AudioInput
+        rate, ch, fmt = args.audio_input.split(":")
+        result = resample_arm(args, AudioInput(int(rate), int(ch), fmt))
+        result["peak_memory_gb"] = round(torch.cuda.max_memory_allocated() / 2 ** 30, 2)
+        out = args.out or os.path.join(ROOT, "profiles", "stream_resample_bench.json")
+        with open(out, "w") as f:
+            json.dump(result, f, indent=1)
+            f.write("\n")
+        print(json.dumps(result))
+        return
+    args.out = args.out or os.path.join(ROOT, "profiles", "stream_bench.json")
     from pantomatrix_amd import ops, streaming, synthetic
     from pantomatrix_amd.recordings import identity_seed
     from tools import workloads

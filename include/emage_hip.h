@@ -426,6 +426,17 @@ int emage_layernorm(int dtype, const void* x, int ldx, const float* gamma, const
  *   where(mask == 0, motion, seed) and count as unmasked — the seed splice of inference() (M:386-391).  motion / mask:
  *   fp32, frame (b, t) at b*ldb + t*C (a window of a longer (B, L, C) tensor is read in place); seed: frame (b, t) at
  *   b*ld_seed + t*C.
+ * emage_pack_motion_hints: emage_pack_motion with a table-driven source (recordings.RecordingRunner(hints=True): keyframes, kept body
+ *   parts).  The hint store is two arrays of store_rows rows with one pitch ld >= C: motion (fp32) and keep (uint8, the reference's mask
+ *   values — 1: generate this element, 0: this element is given; only 0 and 1 occur).  table: B rows of two 64-bit words on the device,
+ *   {store row of this window's frame 0, avail}: frame t of batch row b reads store row table[b][0] + t when t < avail; frames
+ *   t >= avail read nothing and behave as keep = 1 (avail = 0: a row without hints).  Per element n < C, as emage_pack_motion:
+ *   seed != NULL and t < pre: keep == 0 ? motion : seed[b, t, n]; otherwise keep == 1 ? mask_embedding[n] : motion.  Every dtype of
+ *   emage_pack_motion, the EMAGE_H2 codes with their activation-shift bits included.  With ld % 8 == 0 (ld = 344 for C = 337), motion
+ *   16-byte and keep 8-byte aligned, the EMAGE_H2 form reads a group of 8 columns as two 16-byte loads and one 8-byte flag word; any other
+ *   ld >= C reads element by element.  A table row with avail < 0, avail > T, first < 0 or first + avail > store_rows is treated as
+ *   avail = 0 and ORs 4 into *status (the sticky int32 word of emage_gather_windows / emage_copy_segments); nothing outside the two
+ *   arrays is ever read.
  * emage_cast_pad: fp32 (M,C) -> `dtype` (M, ldo) with zero tail [C, n_store).
  */
 int emage_add(int dtype, const void* a, int lda, const void* b, int ldb, int mod_b, const void* c, int ldc, int mod_c,
@@ -433,6 +444,9 @@ int emage_add(int dtype, const void* a, int lda, const void* b, int ldb, int mod
 int emage_pack_motion(int dtype, const float* motion, const float* mask, long ldb, const float* mask_embedding,
                       const float* seed, long ld_seed, int pre,
                       void* out, int ldo, int n_store, int B, int T, int C, void* stream);
+int emage_pack_motion_hints(int dtype, const float* motion, const unsigned char* keep, long store_rows, int ld, const long long* table,
+                            const float* mask_embedding, const float* seed, long ld_seed, int pre,
+                            void* out, int ldo, int n_store, int B, int T, int C, int* status, void* stream);
 int emage_cast_pad(int dtype, const float* src, int lds, void* out, int ldo, int n_store, int M, int C, void* stream);
 
 /*

@@ -146,6 +146,7 @@ SIGNATURES = {
     "emage_layernorm": [_i, _p, _i, _p, _p, _f, _p, _i, _p, _p, _i, _i, _i, _p],
     "emage_add": [_i, _p, _i, _p, _i, _i, _p, _i, _i, _i, _p, _p, _i, _i, _i, _p],
     "emage_pack_motion": [_i, _p, _p, _l, _p, _p, _l, _i, _p, _i, _i, _i, _i, _i, _p],
+    "emage_pack_motion_hints": [_i, _p, _p, _l, _i, _p, _p, _p, _l, _i, _p, _i, _i, _i, _i, _i, _p, _p],
     "emage_cast_pad": [_i, _p, _i, _p, _i, _i, _i, _i, _p],
     "emage_h2_cast": [_p, _i, _p, _i, _i, _i, _i, _f, _i, _p],
     "emage_f16x3_pack_weights": [_p, _i, _p, _i, _i, _i, _f, _p],

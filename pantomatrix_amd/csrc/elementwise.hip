@@ -117,6 +117,92 @@ __global__ __launch_bounds__(256) void pack_motion_h2_kernel(const float* __rest
     }
 }
 
+// pack_motion_kernel with a TABLE-DRIVEN source (recordings.RecordingRunner(hints=True)): the windows are not dense (B, T, C) tensors but rows of
+// a hint store — motion fp32 / keep uint8 (the reference's mask: 1 = generate, 0 = given), store_rows rows of pitch ld — and table row b =
+// {store row of the window's frame 0, avail} says where batch row b reads: frame t < avail reads store row first + t, frames behind read
+// nothing and count as keep == 1.  A row that does not lie inside the store reads nothing either (avail = 0) and is reported in the status word.
+struct HintRow { long first; int avail; };
+__device__ __forceinline__ HintRow hint_row(const long long* __restrict__ table, int b, int Tn, long store_rows, bool report, int* __restrict__ status) {
+    const long first = table[2 * (long)b], avail = table[2 * (long)b + 1];
+    if (avail < 0 || avail > Tn || first < 0 || first > store_rows - avail) {
+        if (report) atomicOr(status, 4);
+        return HintRow{0, 0};
+    }
+    return HintRow{first, (int)avail};
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void pack_motion_hints_kernel(const float* __restrict__ motion, const unsigned char* __restrict__ keep, long store_rows, int ld,
+                                                                const long long* __restrict__ table, const float* __restrict__ emb,
+                                                                const float* __restrict__ seed, long ld_seed, int pre,
+                                                                T* __restrict__ out, int ldo, int n_store, int B, int Tn, int C, int* __restrict__ status) {
+    const long total = (long)B * Tn * n_store;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const int m = (int)(i / n_store), n = (int)(i - (long)m * n_store);
+        const int b = m / Tn, t = m - b * Tn;
+        const HintRow h = hint_row(table, b, Tn, store_rows, t == 0 && n == 0, status);
+        float v = 0.f;
+        if (n < C) {
+            unsigned char k = 1;
+            float mv = 0.f;
+            if (t < h.avail) {
+                const long src = (h.first + t) * ld + n;
+                k = keep[src];
+                mv = motion[src];
+            }
+            if (seed && t < pre) v = k == 0 ? mv : seed[(long)b * ld_seed + (long)t * C + n];
+            else v = k == 1 ? emb[n] : mv;
+        }
+        out[(long)m * ldo + n] = Elem<T>::to(v);
+    }
+}
+
+// EMAGE_H2 form: one thread per group of 8 logical columns.  VEC (ld % 8 == 0, motion 16-byte and keep 8-byte aligned): a group is two float4
+// and one 8-byte word of flags — it ends inside its row of the store, as ld is a multiple of 8 and n0 < C <= ld; else element by element.
+template <bool VEC>
+__global__ __launch_bounds__(256) void pack_motion_hints_h2_kernel(const float* __restrict__ motion, const unsigned char* __restrict__ keep, long store_rows, int ld,
+                                                                   const long long* __restrict__ table, const float* __restrict__ emb,
+                                                                   const float* __restrict__ seed, long ld_seed, int pre,
+                                                                   h2_t* __restrict__ out, int ldo, int n_store, int B, int Tn, int C, float h2s,
+                                                                   int* __restrict__ status) {
+    const int ng = n_store >> 3;
+    const long total = (long)B * Tn * ng;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const int m = (int)(i / ng), n0 = 8 * (int)(i - (long)m * ng);
+        const int b = m / Tn, t = m - b * Tn;
+        const HintRow h = hint_row(table, b, Tn, store_rows, t == 0 && n0 == 0, status);
+        float v[8], mv[8];
+        unsigned char k[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) { v[e] = 0.f; mv[e] = 0.f; k[e] = 1; }
+        if (n0 < C) {
+            if (t < h.avail) {
+                const long src = (h.first + t) * ld + n0;
+                if (VEC) {
+                    const float4 lo = *(const float4*)(motion + src), hi = *(const float4*)(motion + src + 4);
+                    const unsigned long long kw = *(const unsigned long long*)(keep + src);
+                    mv[0] = lo.x; mv[1] = lo.y; mv[2] = lo.z; mv[3] = lo.w; mv[4] = hi.x; mv[5] = hi.y; mv[6] = hi.z; mv[7] = hi.w;
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) k[e] = (unsigned char)(kw >> (8 * e));
+                } else {
+#pragma unroll
+                    for (int e = 0; e < 8; ++e)
+                        if (n0 + e < C) { k[e] = keep[src + e]; mv[e] = motion[src + e]; }
+                }
+            }
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const int n = n0 + e;
+                if (n < C) {
+                    if (seed && t < pre) v[e] = k[e] == 0 ? mv[e] : seed[(long)b * ld_seed + (long)t * C + n];
+                    else v[e] = k[e] == 1 ? emb[n] : mv[e];
+                }
+            }
+        }
+        h2_store8(out + (long)m * ldo + n0, v, h2s);
+    }
+}
+
 // src may alias out (same row stride): each thread reads its 8 values before it writes their 32 bytes
 __global__ __launch_bounds__(256) void cast_pad_h2_kernel(const float* src, int lds, h2_t* out, int ldo, int n_store, int M, int C, float h2s) {
     const int ng = n_store >> 3;
@@ -256,6 +342,29 @@ extern "C" int emage_pack_motion(int dtype, const float* motion, const float* ma
     else if (dtype == EMAGE_H2) {
         if (n_store % 8 || ldo % 8 || ((uintptr_t)out & 15)) return EMAGE_EINVAL;
         hipLaunchKernelGGL(pack_motion_h2_kernel, dim3(grid_for((long)B * T * n_store / 8)), block, 0, s, motion, mask, ldb, mask_embedding, seed, ld_seed, pre, (h2_t*)out, ldo, n_store, B, T, C, hs.s);
+    } else return EMAGE_EINVAL;
+    return launch_status();
+}
+
+extern "C" int emage_pack_motion_hints(int dtype, const float* motion, const unsigned char* keep, long store_rows, int ld, const long long* table,
+                                       const float* mask_embedding, const float* seed, long ld_seed, int pre,
+                                       void* out, int ldo, int n_store, int B, int T, int C, int* status, void* stream) {
+    H2Scale hs;
+    if (h2_dtype(dtype, hs)) return EMAGE_EINVAL;
+    if (!motion || !keep || !table || !mask_embedding || !out || !status || B <= 0 || T <= 0 || C <= 0 || n_store < C || ldo < n_store) return EMAGE_EINVAL;
+    if (ld < C || store_rows <= 0 || store_rows > 0x7fffffffffffL / ld || (seed && (pre <= 0 || pre > T || ld_seed < (long)pre * C))) return EMAGE_EINVAL;
+    if (((uintptr_t)table & 7) || ((uintptr_t)status & 3) || ((uintptr_t)motion & 3)) return EMAGE_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    const dim3 grid(grid_for((long)B * T * n_store)), block(256);
+    if (dtype == EMAGE_BF16) hipLaunchKernelGGL((pack_motion_hints_kernel<bf16_t>), grid, block, 0, s, motion, keep, store_rows, ld, table, mask_embedding, seed, ld_seed, pre, (bf16_t*)out, ldo, n_store, B, T, C, status);
+    else if (dtype == EMAGE_F32) hipLaunchKernelGGL((pack_motion_hints_kernel<float>), grid, block, 0, s, motion, keep, store_rows, ld, table, mask_embedding, seed, ld_seed, pre, (float*)out, ldo, n_store, B, T, C, status);
+    else if (dtype == EMAGE_H2) {
+        if (n_store % 8 || ldo % 8 || ((uintptr_t)out & 15)) return EMAGE_EINVAL;
+        const dim3 g8(grid_for((long)B * T * n_store / 8));
+        if (ld % 8 == 0 && ((uintptr_t)motion & 15) == 0 && ((uintptr_t)keep & 7) == 0)
+            hipLaunchKernelGGL((pack_motion_hints_h2_kernel<true>), g8, block, 0, s, motion, keep, store_rows, ld, table, mask_embedding, seed, ld_seed, pre, (h2_t*)out, ldo, n_store, B, T, C, hs.s, status);
+        else
+            hipLaunchKernelGGL((pack_motion_hints_h2_kernel<false>), g8, block, 0, s, motion, keep, store_rows, ld, table, mask_embedding, seed, ld_seed, pre, (h2_t*)out, ldo, n_store, B, T, C, hs.s, status);
     } else return EMAGE_EINVAL;
     return launch_status();
 }

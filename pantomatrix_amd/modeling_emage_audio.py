@@ -846,12 +846,17 @@ class EmageVQVAEConv(_Tokenizer):
 # ======================================================================================
 # EmageVQModel  (M:72-205)
 # ======================================================================================
+# joint partition of the 55 SMPL-X joints, M:75-90 (boolean masks in the reference); the hands are joints 25-54 (M:103)
+JOINT_MASK_UPPER = tuple(j in (3, 6, 9, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21) for j in range(55))
+JOINT_MASK_LOWER = tuple(j in (0, 1, 2, 4, 5, 7, 8, 10, 11) for j in range(55))
+JOINT_MASK_HANDS = tuple(25 <= j < 55 for j in range(55))
+
+
 class EmageVQModel(torch.nn.Module):
     def __init__(self, face_model, upper_model, hands_model, lower_model, global_model):
         super().__init__()
-        # joint partition of the 55 SMPL-X joints, M:75-90 (boolean masks in the reference)
-        self.joint_mask_upper = [j in (3, 6, 9, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21) for j in range(55)]
-        self.joint_mask_lower = [j in (0, 1, 2, 4, 5, 7, 8, 10, 11) for j in range(55)]
+        self.joint_mask_upper = list(JOINT_MASK_UPPER)
+        self.joint_mask_lower = list(JOINT_MASK_LOWER)
         self.vq_model_face = face_model
         self.vq_model_upper = upper_model
         self.vq_model_hands = hands_model
@@ -1504,13 +1509,15 @@ class EmageAudioModel(_WavEncoderMixin, _EmageModule):
         return dict(spk_body=spk_body, face0=face0, pos_spk=pos_spk, t=t)
 
     def forward(self, audio, speaker_id, masked_motion, mask, use_audio=True, _audio_feats=None, _tables=None, _lean=False,
-                _seed=None):
+                _seed=None, _hints=None):
         """EmageAudioModel.forward (M:265-341), eval mode.  audio (B,L) fp32, speaker_id (B,1) int64,
         masked_motion / mask (B,T,337) fp32 -> dict of 8 (B,T,256) fp32 tensors.
         `_audio_feats` / `_tables` (internal): waveform-only features and speaker tables already computed by
         `inference()`; `_seed` (internal): (B, seed_frames, 337) view spliced into the first frames by the packing
         kernel (M:386-391); `_lean` (internal, `infer_codes`): skip the outputs the decode does not consume (the
-        classifier of a latent-routed part, the fp32 copy of a classified part's latent).
+        classifier of a latent-routed part, the fp32 copy of a classified part's latent); `_hints` (internal,
+        `recordings.RecordingRunner`): (store_motion, store_keep, table, status) — the window's motion / mask come from
+        a hint store through a device table (`ops.pack_motion_hints`); masked_motion / mask then only give the shape.
         audio / masked_motion / mask may be windows (views) of longer clip tensors: they are read in place."""
         if self.training and _audio_feats is None and _seed is None:
             # train mode (T:156-181): batch-statistics BatchNorm, dropout, outputs connected to the parameters for loss.backward()
@@ -1529,10 +1536,11 @@ class EmageAudioModel(_WavEncoderMixin, _EmageModule):
             audio = audio.to(device=dev, dtype=torch.float32)
             if audio.stride(1) != 1:
                 audio = audio.contiguous()
-        motion3 = self._frames_view(masked_motion.to(device=dev, dtype=torch.float32))
-        mask3 = self._frames_view(mask.to(device=dev, dtype=torch.float32))
-        if b > 1 and motion3.stride(0) != mask3.stride(0):      # the packing kernel takes one clip stride for both
-            motion3, mask3 = motion3.contiguous(), mask3.contiguous()
+        if _hints is None:
+            motion3 = self._frames_view(masked_motion.to(device=dev, dtype=torch.float32))
+            mask3 = self._frames_view(mask.to(device=dev, dtype=torch.float32))
+            if b > 1 and motion3.stride(0) != mask3.stride(0):      # the packing kernel takes one clip stride for both
+                motion3, mask3 = motion3.contiguous(), mask3.contiguous()
 
         out = {}
         parts = ("upper", "hands", "lower")
@@ -1553,7 +1561,11 @@ class EmageAudioModel(_WavEncoderMixin, _EmageModule):
 
             with fk.lane(0):
                 # masked motion -> spatial hints (M:267-273)
-                x0 = ops.pack_motion(cx.dt, motion3, mask3, pk.w["mask_emb"], _rup(cm), seed=_seed)
+                if _hints is None:
+                    x0 = ops.pack_motion(cx.dt, motion3, mask3, pk.w["mask_emb"], _rup(cm), seed=_seed)
+                else:
+                    store_motion, store_keep, table, status = _hints
+                    x0 = ops.pack_motion_hints(cx.dt, store_motion, store_keep, table, pk.w["mask_emb"], _rup(cm), t, status, seed=_seed)
                 hint, _ = _conv_encoder(cx, "motion_encoder", x0, t, spec.MOTION_ENC_LAYERS, mf, False)
                 hh, _ = cx.gemm(hint, "bodyhints.fc1", slope=0.1)               # [face | body] hidden, (M, 2d)
                 with ops.lockstep(self.group_gemms) as ls:                      # the two second layers: one launch

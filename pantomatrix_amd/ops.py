@@ -1622,6 +1622,11 @@ def gather_clip_speakers(order, cursor, n_batches, clips, speakers, out, status)
     return out
 
 
+# the sticky status word the recording pass's table-driven kernels share (gather_windows, copy_segments, pack_motion_hints)
+STATUS = ("1: an audio window outside the flat array (zero-filled); 2: a copy segment outside its buffers (skipped); "
+          "4: a hint-table row outside the hint store (read as a row without hints)")
+
+
 @_op("gather_windows", "(Tensor audio, Tensor offsets, Tensor(a!) out, Tensor(b!) status) -> ()")
 def _gather_windows(audio, offsets, out, status):
     fmt = _lib.PCM_S16 if audio.dtype == torch.int16 else _lib.PCM_F32
@@ -2200,6 +2205,49 @@ def pack_motion(dtype, motion, mask, emb, n_store, seed=None):
         assert seed.dtype == torch.float32 and seed.shape == (b, pre, c) and seed.stride(2) == 1 and (seed.stride(1) == c or pre == 1)
     out = torch.empty(b * t, n_store, dtype=TORCH_DTYPE[dtype], device=motion.device)
     _pack_motion(dtype, motion, mask, emb, seed, out)
+    return out
+
+
+@_op("pack_motion_hints", "(int dtype, Tensor store_motion, Tensor store_keep, Tensor table, Tensor emb, Tensor? seed, int t, Tensor(a!) out, "
+     "Tensor(b!) status) -> ()")
+def _pack_motion_hints(dtype, store_motion, store_keep, table, emb, seed, t, out, status):
+    b, c = table.shape[0], emb.numel()
+    pre, ld_seed = 0, 0
+    if seed is not None:
+        pre = seed.shape[1]
+        ld_seed = seed.stride(0) if b > 1 else pre * c
+    check(_lib.load().emage_pack_motion_hints(dtype, _ptr(store_motion), _ptr(store_keep), store_motion.shape[0], store_motion.stride(0), _ptr(table),
+                                              _ptr(emb), _ptr(seed), ld_seed, pre, _ptr(out), _ld(out), out.shape[1], b, t, c, _ptr(status),
+                                              _stream()), "pack_motion_hints")
+
+
+def pack_motion_hints(dtype, store_motion, store_keep, table, emb, n_store, t, status, seed=None):
+    """`pack_motion` reading its windows out of a hint store through a device table.  store_motion (rows, C) float32 / store_keep (rows, C)
+    uint8 (the reference's mask values: 1 = generate, 0 = given): views with unit column stride and ONE row pitch ld >= C (ld % 8 == 0
+    takes the vector path of the H2 form); table (B, 2) int64 contiguous on the device, row b = {store row of the window's frame 0,
+    avail}: frame t' < avail reads store row first + t', the frames behind count as masked.  With ld % 8 == 0 a group of 8 columns is read
+    whole, so the storage behind EVERY row, the last one included, must reach ld columns (slices `[:, :C]` of a (rows, ld) tensor do;
+    checked here).  A row outside the store reads nothing and
+    sets bit 2 (value 4) of `status`.  seed: as in `pack_motion`.  -> (B*t, n_store) in `dtype`.  See include/emage_hip.h:
+    emage_pack_motion_hints."""
+    _dev(store_motion)
+    rows, c = store_motion.shape
+    assert store_motion.dtype == torch.float32 and store_keep.dtype == torch.uint8 and store_keep.shape == (rows, c) and emb.numel() == c
+    assert store_motion.stride(1) == 1 and store_keep.stride(1) == 1 and store_motion.stride(0) == store_keep.stride(0) >= c
+    ld = store_motion.stride(0)
+    reach = (rows - 1) * ld + (ld if ld % 8 == 0 else c)             # elements from row 0 on that the kernel may read
+    for x in (store_motion, store_keep):
+        assert x.storage_offset() + reach <= x.untyped_storage().nbytes() // x.element_size(), "pack_motion_hints: the store's last row is cut short"
+    assert table.dtype == torch.int64 and table.dim() == 2 and table.shape[1] == 2 and table.is_contiguous() and table.shape[0] > 0
+    assert status.dtype == torch.int32 and status.numel() == 1 and t > 0
+    b = table.shape[0]
+    if seed is not None:
+        pre = seed.shape[1]
+        assert seed.dtype == torch.float32 and seed.shape == (b, pre, c) and seed.stride(2) == 1 and (seed.stride(1) == c or pre == 1)
+    for x in (store_keep, table, emb, status):
+        assert x.device == store_motion.device, "pack_motion_hints: every tensor on one device"
+    out = torch.empty(b * t, n_store, dtype=TORCH_DTYPE[dtype], device=store_motion.device)
+    _pack_motion_hints(dtype, store_motion, store_keep, table, emb, seed, int(t), out, status)
     return out
 
 

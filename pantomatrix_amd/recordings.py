@@ -15,7 +15,9 @@ No kernel learns about lengths.  The window schedule of `inference()` (M:343-470
 Two data-movement kernels (csrc/recordings.hip) keep the pass free of host state, so it is capturable as one hipGraph per tuple of lengths:
 `emage_gather_windows` cuts the audio windows of a step / a tail group out of the flat array of all recordings, `emage_copy_segments` gathers
 a tail group's seed rows, scatters its codes into each recording's slot and packs every recording's result into one flat buffer per output
-(three device-to-host copies per pass, not three per recording).
+(three device-to-host copies per pass, not three per recording).  Motion hints (`masked_motion` / `mask` of `inference()`, M:343-359:
+keyframes, kept body parts) are a third table-driven input: `emage_pack_motion_hints` (csrc/elementwise.hip) packs each forward's window
+operand out of a per-frame hint store (`RecordingRunner(hints=True)`).
 
 * ``window_schedule``   the schedule itself, pure Python (the host tests restate M:364-368 / M:428-431 against it);
 * ``RecordingSet``      the recordings of a split (``from_index``) or a list of waveforms / WAV files (``from_audio``) on the device;
@@ -37,8 +39,9 @@ from .data import SMPLX_FPS, _is_s16_mono, _speaker_rows, foot_contact_path
 MODEL_SR = 16000                                        # `inference()` hard-codes 16000 // 30 samples per frame (M:345, M:393)
 SPF = MODEL_SR // SMPLX_FPS
 SEED_DIMS = 337                                         # 55 joints x 6, trans, foot contact (T:59-60)
+HINT_LD = 344                                           # row pitch of a hint store: 337 rounded up to 8 columns (32 bytes of motion, 8 of flags)
 WIDTHS = (("poses", 165), ("expressions", 100), ("trans", 3))
-STATUS_TEXT = "1: an audio window outside the flat array (zero-filled); 2: a copy segment outside its buffers (skipped)"
+STATUS_TEXT = ops.STATUS
 
 
 class Schedule:
@@ -107,6 +110,21 @@ def identity_seed(n, frames=4):
     return seed
 
 
+def part_columns(part):
+    """The columns of the 337 (55 joints x rot6d | trans | foot contact) that belong to `part`: "upper" / "hands" / "lower" by the joint
+    partition of `EmageVQModel` (M:75-90, M:103), "trans" (330:333), "contact" (333:337) -> sorted (n,) int64 array.  For building
+    `mask` arrays: `mask[a:b, part_columns("upper")] = 0` keeps the upper body of frames a..b-1."""
+    from .modeling_emage_audio import JOINT_MASK_HANDS, JOINT_MASK_LOWER, JOINT_MASK_UPPER
+    if part == "trans":
+        return np.arange(330, 333, dtype=np.int64)
+    if part == "contact":
+        return np.arange(333, SEED_DIMS, dtype=np.int64)
+    masks = {"upper": JOINT_MASK_UPPER, "hands": JOINT_MASK_HANDS, "lower": JOINT_MASK_LOWER}
+    if part not in masks:
+        raise ValueError(f"part_columns: {part!r} is none of 'upper', 'hands', 'lower', 'trans', 'contact'")
+    return np.array([6 * j + k for j in range(55) if masks[part][j] for k in range(6)], dtype=np.int64)
+
+
 def _host_ids(ids, n, who, speaker_dims=None):
     """One speaker-table row per recording as a host (n,) int64 tensor: None -> zeros, an int -> that id for every recording."""
     if ids is None:
@@ -137,15 +155,32 @@ class RecordingSet:
     rot6d(poses[:4]) | trans[:4] | foot_contact[:4] and `ref_trans` (R, 3) = trans[0] (T:53-60, T:83).
 
     The poses are RAW: `inference_fn` does not apply the dataset's `normalize` that `data.ClipStore` applies.  The rest of the ground-truth
-    motion is not kept: with `mask=None` the forward replaces every non-seed frame by the mask embedding (M:267-268) and the windows
-    re-seed themselves from their own decode (M:384-391), so only the first four frames of `masked_motion` ever reach the network.
-    Motion hints and masks beyond the seed are out of scope.
+    motion is not kept unless it is a hint: with `mask=None` the forward replaces every non-seed frame by the mask embedding (M:267-268)
+    and the windows re-seed themselves from their own decode (M:384-391), so only the first four frames of `masked_motion` ever reach the
+    network.
+
+    Motion hints — the model's completion use, `inference(audio, speaker_id, vq_model, masked_motion=, mask=)` (M:343-359): keyframes, a
+    body part kept from a capture, a pose to hold.  masked_motion: per recording None or an (h_r, 337) float array, a PREFIX of the
+    recording (h_r <= frames_r, M:352-353); mask: per recording None or an (m_r, 337) array of exactly 0 / 1 (bool or float arrays
+    holding only those values are taken; anything else raises ValueError — a narrowing: the reference compares `== 0` and `== 1` and
+    leaves other values to fall between), 1 = generate this element, 0 = this element is given.  As in the reference, recording r's
+    motion is the identity template overwritten by its `masked_motion` prefix and its mask all ones overwritten by its `mask` prefix
+    (M:348-359): `masked_motion` without `mask` influences only the seed.  Stored as `hint_motion` (F, 344) float32 / `hint_keep`
+    (F, 344) uint8 on the device (columns 337.. are padding, so a group of 8 columns is 32 / 8 bytes aligned): recording r's rows
+    [hint_offsets[r], hint_offsets[r] + hint_len[r]) cover max(h_r, m_r) frames, template-filled where one of the two is shorter.
+    `hinted`: some recording's mask has a 0 in it — the pass then needs a runner built with `hints=True` (`RecordingRunner.for_set` does); a
+    hinted set is also `seeded`, with `mask` alone too (its seed is then the identity template).
+    `seeds` and `masked_motion` exclude each other: with `masked_motion`, `seeds[r]` is the first four frames of recording r's motion as
+    defined above (M:379); `ref_trans` stays an argument of its own.
 
     speaker_ids: one row of the model's speaker tables per recording (ints >= 0), kept on the host as `speaker_ids` ((R,) int64) —
     `RecordingRunner.load` copies them into the runner's id buffers.  None (both reference loops): the set names no speakers and the
     runner keeps the ids it was built with (0 by default)."""
 
-    def __init__(self, audios, device, seeds=None, ref_trans=None, items=None, audio_sr=MODEL_SR, seed_poses=None, speaker_ids=None):
+    def __init__(self, audios, device, seeds=None, ref_trans=None, items=None, audio_sr=MODEL_SR, seed_poses=None, speaker_ids=None,
+                 masked_motion=None, mask=None):
+        if seeds is not None and masked_motion is not None:
+            raise ValueError("RecordingSet: pass `seeds` or `masked_motion`, not both (the seed is the first four frames of masked_motion, M:379)")
         if audio_sr != MODEL_SR:
             raise ValueError(f"RecordingSet: the model's windows are cut at {MODEL_SR} Hz (M:345), not {audio_sr}")
         if not len(audios):
@@ -165,7 +200,12 @@ class RecordingSet:
         for a, lo, hi in zip(waves, self.sample_offsets[:-1], self.sample_offsets[1:]):
             self.audio[lo:hi].copy_(a if a.dtype == dtype else a.to(torch.float32) * (1.0 / 32768.0))
         n = len(waves)
-        self.seeded = seeds is not None
+        hint_seeds = self._store_hints(masked_motion, mask)
+        # a hinted set is seeded whatever it was hinted with: the seed frames are part of the hints, and with `mask` alone the seed is the
+        # identity template the mask's zeros declare as given (M:348-359, M:379)
+        self.seeded = seeds is not None or hint_seeds is not None or self.hinted
+        if hint_seeds is not None:
+            seeds = hint_seeds
         seeds = identity_seed(n) if seeds is None else torch.as_tensor(seeds, dtype=torch.float32)
         ref_trans = torch.zeros(n, 3) if ref_trans is None else torch.as_tensor(ref_trans, dtype=torch.float32)
         if tuple(seeds.shape) != (n, 4, SEED_DIMS) or tuple(ref_trans.shape) != (n, 3):
@@ -173,6 +213,47 @@ class RecordingSet:
         self.seeds, self.ref_trans = seeds.to(self.device).contiguous(), ref_trans.to(self.device).contiguous()
         self.speaker_ids = None if speaker_ids is None else _host_ids(speaker_ids, n, "RecordingSet")
         self.items, self.seed_poses = items, seed_poses      # seed_poses: (R, 4, 165) host tensor, the raw axis-angle frames behind `seeds` (from_index)
+
+    def _store_hints(self, masked_motion, mask):
+        """The hint store of the set (see the class docstring) -> the seeds `masked_motion` defines, (R, 4, 337), or None without it."""
+        n, frames = len(self.sample_counts), self.frames
+        rows = []
+        for name, arg, dtype in (("masked_motion", masked_motion, np.float32), ("mask", mask, np.float32)):
+            per = [None] * n if arg is None else list(arg)
+            if len(per) != n:
+                raise ValueError(f"RecordingSet: {name} needs one entry (an array or None) per recording, got {len(per)} for {n}")
+            for r, a in enumerate(per):
+                if a is None:
+                    continue
+                a = np.asarray(a.detach().cpu().numpy() if torch.is_tensor(a) else a)
+                if a.ndim != 2 or a.shape[1] != SEED_DIMS or a.shape[0] > frames[r]:
+                    raise ValueError(f"RecordingSet: recording {r}: {name} must be a prefix (h, {SEED_DIMS}) of its {frames[r]} frames, got {a.shape}")
+                if name == "mask" and not np.isin(a, (0, 1)).all():
+                    raise ValueError(f"RecordingSet: recording {r}: mask must hold exactly 0 (given) and 1 (generate)")
+                per[r] = np.ascontiguousarray(a, dtype=dtype)
+            rows.append(per)
+        motions, masks = rows
+        self.hint_len = [max(0 if a is None else a.shape[0], 0 if k is None else k.shape[0]) for a, k in zip(motions, masks)]
+        self.hint_offsets = np.cumsum([0] + self.hint_len)
+        self.hinted = any(k is not None and bool((k == 0).any()) for k in masks)
+        total = int(self.hint_offsets[-1])
+        motion = np.zeros((total, HINT_LD), np.float32)
+        motion[:, 0:330:6] = 1.0                                                        # the identity template (M:348-351) ...
+        motion[:, 4:330:6] = 1.0
+        keep = np.ones((total, HINT_LD), np.uint8)                                      # ... and the all-ones mask (M:356)
+        for a, k, lo in zip(motions, masks, self.hint_offsets[:-1]):
+            if a is not None:
+                motion[lo:lo + a.shape[0], :SEED_DIMS] = a
+            if k is not None:
+                keep[lo:lo + k.shape[0], :SEED_DIMS] = k.astype(np.uint8)
+        self.hint_motion, self.hint_keep = torch.from_numpy(motion).to(self.device), torch.from_numpy(keep).to(self.device)
+        if masked_motion is None:
+            return None
+        seeds = identity_seed(n)
+        for r, a in enumerate(motions):
+            if a is not None:
+                seeds[r, :min(4, a.shape[0])] = torch.from_numpy(a[:4])
+        return seeds
 
     def __len__(self):
         return len(self.sample_counts)
@@ -182,21 +263,26 @@ class RecordingSet:
         return [frames_of(n) for n in self.sample_counts]
 
     @classmethod
-    def from_audio(cls, audios, device, seeds=None, ref_trans=None, audio_sr=MODEL_SR, speaker_ids=None):
+    def from_audio(cls, audios, device, seeds=None, ref_trans=None, audio_sr=MODEL_SR, speaker_ids=None, masked_motion=None, mask=None):
         """1-D waveforms (int16 / float32 arrays or tensors) or WAV paths — the test_emage_audio.py case: no motion, identity seed, zero
-        `ref_trans` unless given.  Paths load by the rule of `ClipStore.from_index`."""
+        `ref_trans` unless given.  Paths load by the rule of `ClipStore.from_index`.  masked_motion / mask: motion hints, one entry per
+        recording (the class docstring)."""
         paths = [a for a in audios if isinstance(a, (str, os.PathLike))]
         s16 = all(_is_s16_mono(p, audio_sr) for p in paths)
         waves = [_load_wave(a, audio_sr, device, s16) if isinstance(a, (str, os.PathLike)) else a for a in audios]
-        return cls(waves, device, seeds=seeds, ref_trans=ref_trans, audio_sr=audio_sr, speaker_ids=speaker_ids)
+        return cls(waves, device, seeds=seeds, ref_trans=ref_trans, audio_sr=audio_sr, speaker_ids=speaker_ids, masked_motion=masked_motion, mask=mask)
 
     @classmethod
-    def from_index(cls, meta_paths, split="test", device="cuda", audio_sr=MODEL_SR, speakers=None):
+    def from_index(cls, meta_paths, split="test", device="cuda", audio_sr=MODEL_SR, speakers=None, hint_mask=None):
         """The reference's index JSONs (one path, a list of paths, or the items), filtered by `mode == split`, then the FIRST item per
         `video_id` (T:38-42).  Each recording is loaded once: `beat_format_load`, the foot-contact `.npy` next to it, and the audio — the
         file's int16 samples when every file is mono 16-bit PCM at `audio_sr`, else `audio.load_audio` (on the device when there is one).
         speakers: as in `data.ClipStore.from_index` — None (every recording is speaker 0), a `data.SpeakerMap`, a dict {speaker number: row}
-        or a callable item -> row."""
+        or a callable item -> row.
+        hint_mask: a callable `(item, frames) -> (frames, 337) 0 / 1 array or None` ("keep the captured upper body, generate the rest":
+        `mask[:, part_columns("upper")] = 0`).  When given, every recording's WHOLE ground-truth motion — rot6d(poses) | trans |
+        foot_contact, cut at the recording's `frames` — becomes its `masked_motion` and the callable's result its `mask`; the seeds are
+        bit for bit those of a set built without it."""
         if isinstance(meta_paths, (str, os.PathLike)):
             meta_paths = [meta_paths]
         items = []
@@ -212,7 +298,7 @@ class RecordingSet:
         if not items:
             raise ValueError(f"RecordingSet.from_index: no item with mode == {split!r}")
         s16 = all(_is_s16_mono(it["audio_path"], audio_sr) for it in items)
-        waves, seeds, ref, raw = [], [], [], []
+        waves, seeds, ref, raw, motions, masks = [], [], [], [], [], []
         for it in items:
             rec = motion_io.beat_format_load(it["motion_path"], mask=None)
             contact = np.load(foot_contact_path(it["motion_path"]))
@@ -224,9 +310,19 @@ class RecordingSet:
             ref.append(torch.from_numpy(trans[0]))
             raw.append(torch.from_numpy(poses[:4].copy()))
             waves.append(_load_wave(it["audio_path"], audio_sr, device, s16))
+            if hint_mask is not None:
+                frames = frames_of(len(waves[-1]))
+                h = min(frames, poses.shape[0], trans.shape[0], contact.shape[0])
+                full = torch.cat([axis_angle_to_rot6d(torch.from_numpy(poses[:h]).reshape(h, -1, 3)).reshape(h, -1), torch.from_numpy(trans[:h]),
+                                  torch.from_numpy(np.asarray(contact[:h], dtype=np.float32))], dim=-1)
+                full[:4] = seeds[-1][:h]                     # the seed frames ARE today's seed, whatever a longer batch does to the last bit
+                motions.append(full.numpy())
+                masks.append(hint_mask(it, frames))
         row_of = _speaker_rows(speakers)
-        return cls(waves, device, seeds=torch.stack(seeds), ref_trans=torch.stack(ref), items=items, audio_sr=audio_sr, seed_poses=torch.stack(raw),
-                   speaker_ids=None if speakers is None else [int(row_of(it)) for it in items])
+        hinted = hint_mask is not None
+        return cls(waves, device, seeds=None if hinted else torch.stack(seeds), ref_trans=torch.stack(ref), items=items, audio_sr=audio_sr,
+                   seed_poses=torch.stack(raw), speaker_ids=None if speakers is None else [int(row_of(it)) for it in items],
+                   masked_motion=motions if hinted else None, mask=masks if hinted else None)
 
 
 class _Unit:
@@ -235,7 +331,7 @@ class _Unit:
 
 
 class _Tail:
-    __slots__ = ("t", "n", "offsets", "seed_segs", "code_segs", "ranks", "ids")
+    __slots__ = ("t", "n", "offsets", "seed_segs", "code_segs", "ranks", "ids", "hint_lo")
 
 
 class _Decode:
@@ -268,17 +364,28 @@ class RecordingRunner:
     it — the periodic test pass of a training run.  New weights reach a replay as in `validation.Validator`: the packing of the model's
     operand set is captured into a second graph over the same memory pool, and `__call__` replays it first whenever the model's version
     stamp has moved (a training step, `load_state_dict`), so the pass reads operands packed from the current parameters at the addresses it
-    was captured with.  The VQ models are frozen in the reference's training (T:233-245); after changing THEM build a new runner."""
+    was captured with.  The VQ models are frozen in the reference's training (T:233-245); after changing THEM build a new runner.
+
+    hints: False — every forward reads the read-only templates (identity pose, all-ones mask), the launch sequence of a runner without the
+    argument; `load()` of a set whose `hinted` is True raises.  True — the pass honours a set's motion hints (`RecordingSet`:
+    masked_motion / mask): the runner owns a hint store with a row for every frame of every recording, `hint_motion` (sum(frames_r), 344)
+    float32 and `hint_keep` uint8 — 344 columns x 5 bytes per frame, ~100 MB for the 57.7 k frames (1 924 s) of the 26 recordings
+    tools/bench_recordings.py measures — recording r's rows starting at its frame offset, and ONE int64 table `hint_table` with a row per (unit row) and per (tail-group member), parallel to `win_offsets` /
+    `g.offsets`: {frame offset of the recording + window start, clamp(hint_len_r - start, 0, t)}.  Each forward packs its window operand
+    with `ops.pack_motion_hints` from its slice of the table instead of `ops.pack_motion` from the templates; nothing else changes, the
+    seed chain included.  Hints are INPUT DATA like audio and speaker ids: `load()` copies the set's hint rows into the store and rewrites
+    the table's `avail` column (stream-ordered copies into fixed addresses), so a replay with other hints of any prefix lengths on the
+    same recording lengths needs no new graph.  The seed frames are part of the hints: a hinted set needs a `seeded` runner (`for_set`)."""
 
     def __init__(self, model, vq_model, lengths_in_samples, seeded=False, use_graph=True, max_batch=64, max_hoist_rows=256, speaker_id=0,
-                 audio_dtype=torch.float32):
+                 audio_dtype=torch.float32, hints=False):
         dev = model.device
         model._require_device(dev)                          # an MI355X: there is no CPU path (the host tests lift this check over stand-in ops)
         on_gpu = dev.type == "cuda"
         if audio_dtype not in (torch.float32, torch.int16):
             raise ValueError("audio_dtype must be torch.float32 or torch.int16")
         c = model.config
-        self.model, self.vq, self.device, self.seeded = model, vq_model, dev, bool(seeded)
+        self.model, self.vq, self.device, self.seeded, self.hints = model, vq_model, dev, bool(seeded), bool(hints)
         self.window, self.pre = int(c.pose_length), int(c.seed_frames)
         self.max_batch, self.max_hoist_rows = int(max_batch), max(int(max_hoist_rows), int(max_batch))
         if self.max_batch <= 0 or self.pre != 4:
@@ -294,6 +401,7 @@ class RecordingRunner:
         self.rank = {r: k for k, r in enumerate(self.order)}
         self.frames_out = list(sched.frames)
         self.out_offsets = np.cumsum([0] + self.frames_out)
+        self.frame_offsets = np.cumsum([0] + list(sched.lengths))                       # recording r's rows of the hint store (input order)
         self._plan(sched)
         # ---- static buffers ----
         lmax, w, mb = max(sched.lengths), self.window, min(self.max_batch, n_rec)
@@ -306,6 +414,11 @@ class RecordingRunner:
         self.ref_trans = torch.zeros(n_rec, 1, 3, device=dev)
         self.tmpl_motion = identity_seed(mb, w).to(dev)                                # identity pose + all-ones mask (M:347-358), read-only
         self.tmpl_mask = torch.ones_like(self.tmpl_motion)
+        if self.hints:                                                                 # the template's contents: a row nobody loaded is no hint
+            self.hint_motion = identity_seed(1, int(self.frame_offsets[-1]))[0].to(dev)
+            self.hint_motion = torch.cat([self.hint_motion, torch.zeros(self.hint_motion.shape[0], HINT_LD - SEED_DIMS, device=dev)], dim=1)
+            self.hint_keep = torch.ones(self.hint_motion.shape[0], HINT_LD, dtype=torch.uint8, device=dev)
+            self.hint_table = torch.tensor([[int(self.frame_offsets[r]) + s, 0] for r, s, _t in self.hint_rows], dtype=torch.int64, device=dev)
         routes = model._routes()
         self.codes = {p: torch.zeros(n_rec, lmax, dtype=torch.int64, device=dev) for p, r in routes.items() if r}
         n_win = max([c_[1] for c_ in self.chunks], default=0)
@@ -336,6 +449,7 @@ class RecordingRunner:
         srt_rounds = [sched.rounds[r] for r in self.order]
         has_tail = [sched.remain[r] > self.pre for r in self.order]
         units, offsets = [], []
+        self.hint_rows = []                             # (recording, window start, frames) per row of `hint_table`: the units' rows, then the tail groups'
         for i in range(max(srt_rounds, default=0)):
             active = sum(1 for r in srt_rounds if r > i)                                # a prefix: rounds is monotone in the length
             for lo in range(0, active, self.max_batch):
@@ -343,6 +457,7 @@ class RecordingRunner:
                 u.start, u.lo, u.hi, u.seq = i * hop, lo, min(lo + self.max_batch, active), len(offsets)
                 u.need_seed = any(srt_rounds[k] > i + 1 or has_tail[k] for k in range(u.lo, u.hi))
                 offsets += [int(self.sample_offsets[self.order[k]]) + u.start * SPF for k in range(u.lo, u.hi)]
+                self.hint_rows += [(self.order[k], u.start, w) for k in range(u.lo, u.hi)]
                 units.append(u)
         # hoisting chunks: whole units, at most max_hoist_rows sequences each -> (first sequence, sequences, units)
         self.chunks = []
@@ -368,6 +483,8 @@ class RecordingRunner:
                 g.code_segs = ops.segment_table([(j * t, self.rank[r] * lmax + s, t) for j, (r, s) in enumerate(grp)], g.n * t, n_rec * lmax, dev)[0]
                 g.ranks = torch.tensor([self.rank[r] for r, _s in grp], dtype=torch.long, device=dev)
                 g.ids = torch.zeros(g.n, 1, dtype=torch.long, device=dev)               # the members' speaker ids (`set_speaker_ids`)
+                g.hint_lo = len(self.hint_rows)
+                self.hint_rows += [(r, s, t) for r, s in grp]
                 self.tails.append(g)
         self.decodes = []
         k = 0
@@ -420,6 +537,26 @@ class RecordingRunner:
             for g in self.tails:
                 g.ids.copy_(self.speaker_id.index_select(0, g.ranks))
 
+    def _hints_of(self, row0, n):
+        """The extra `forward` argument of a unit / tail group whose table rows are [row0, row0 + n): nothing without hints."""
+        if not self.hints:
+            return {}
+        return {"_hints": (self.hint_motion[:, :SEED_DIMS], self.hint_keep[:, :SEED_DIMS], self.hint_table[row0:row0 + n], self.status)}
+
+    def set_hints(self, recording_set):
+        """A set's hint rows into the store and the `avail` column of the table: stream-ordered copies into fixed addresses.  Rows of the
+        store behind a recording's `hint_len` keep what an earlier set left there; no table row reaches them."""
+        rs = recording_set
+        for r, (n, lo) in enumerate(zip(rs.hint_len, rs.hint_offsets[:-1])):
+            if n > self.schedule.lengths[r]:
+                raise ValueError(f"RecordingRunner: recording {r} carries {n} hinted frames, more than its {self.schedule.lengths[r]} frames")
+            if n:
+                fo = int(self.frame_offsets[r])
+                self.hint_motion[fo:fo + n].copy_(rs.hint_motion[lo:lo + n], non_blocking=True)
+                self.hint_keep[fo:fo + n].copy_(rs.hint_keep[lo:lo + n], non_blocking=True)
+        avail = [min(max(int(rs.hint_len[r]) - s, 0), t) for r, s, t in self.hint_rows]
+        self.hint_table[:, 1].copy_(torch.tensor(avail, dtype=torch.int64))
+
     def _pass(self):
         """The three phases in order; the tool times them one by one."""
         self._full_windows()
@@ -455,7 +592,8 @@ class RecordingRunner:
                         f = model._feats_of_clips(feats, k0, n, w)
                     row0 = u.lo if self.per_recording_ids else 0
                     net = model.forward(win[k0:k0 + n], self.speaker_id[row0:row0 + n], self.tmpl_motion[:n], self.tmpl_mask[:n], use_audio=True,
-                                        _audio_feats=f, _tables=self._sliced_tables(tables, row0, n), _lean=True, _seed=self.seeds[u.lo:u.hi])
+                                        _audio_feats=f, _tables=self._sliced_tables(tables, row0, n), _lean=True, _seed=self.seeds[u.lo:u.hi],
+                                        **self._hints_of(u.seq, n))
                     codes = {p: v[u.lo:u.hi] for p, v in self.codes.items()}
                     model._window_codes(net, vq, codes, u.start, n, w)
                     self._flush_health(pending)
@@ -478,7 +616,7 @@ class RecordingRunner:
                 ops.gather_windows(self.audio, g.offsets, a, self.status)
                 ops.copy_segments(self.seeds, self.tail_seed, g.seed_segs, pre * SEED_DIMS * 4, 1, self.status)
                 net = model.forward(a, g.ids if self.per_recording_ids else self.speaker_id[:n], self.tmpl_motion[:n, :t], self.tmpl_mask[:n, :t], use_audio=True, _lean=True,
-                                    _seed=self.tail_seed[:n])
+                                    _seed=self.tail_seed[:n], **self._hints_of(g.hint_lo, n))
                 model._window_codes(net, vq, {p: v[:n * t].view(n, t) for p, v in self.tail_codes.items()}, 0, n, t)
                 self._flush_health(pending)
                 for p, v in self.tail_codes.items():
@@ -513,8 +651,12 @@ class RecordingRunner:
 
     # ---- one pass end to end ------------------------------------------------------------------------------------------------------------
     def load(self, recording_set):
-        """Copy a set's audio and speaker ids (and, when `seeded`, its seeds and `ref_trans`) into the runner's input buffers (stream-ordered)."""
+        """Copy a set's audio and speaker ids (and, when `seeded`, its seeds and `ref_trans`; with `hints`, its motion hints) into the runner's
+        input buffers (stream-ordered)."""
         rs = recording_set
+        if rs.hinted and not (self.hints and self.seeded):
+            raise ValueError("RecordingRunner: the set carries motion hints (a mask with a 0 in it); build the runner with hints=True and "
+                             "seeded=True (RecordingRunner.for_set does both)")
         if list(rs.sample_counts) != self.sample_counts:
             raise ValueError("RecordingRunner: this runner was built for other recording lengths (one runner, one graph, per tuple of lengths)")
         if rs.audio.dtype != self.audio.dtype:
@@ -525,6 +667,8 @@ class RecordingRunner:
         if self.seeded:
             self.seed0.copy_(rs.seeds.to(self.device).index_select(0, self._order_dev))
             self.ref_trans.copy_(rs.ref_trans.to(self.device).index_select(0, self._order_dev).view(-1, 1, 3))
+        if self.hints:
+            self.set_hints(rs)
 
     def run_device(self):
         """One pass over the current input buffers, on the current stream; the results stay in `flat` (rows in input order)."""
@@ -565,6 +709,7 @@ class RecordingRunner:
     @classmethod
     def for_set(cls, model, vq_model, recording_set, **kw):
         kw.setdefault("seeded", recording_set.seeded)
+        kw.setdefault("hints", recording_set.hinted)
         if recording_set.speaker_ids is not None:
             kw.setdefault("speaker_id", recording_set.speaker_ids)
         return cls(model, vq_model, recording_set.sample_counts, audio_dtype=recording_set.audio.dtype, **kw)
@@ -580,14 +725,16 @@ def _save_outputs(results, names, audio_paths, save_path, pose_fps):
     return save_list
 
 
-def test_pass(model, vq, meta_paths, save_path, runner=None, pose_fps=None, device=None, speakers=None):
+def test_pass(model, vq, meta_paths, save_path, runner=None, pose_fps=None, device=None, speakers=None, hint_mask=None):
     """`inference_fn` (T:33-102): generate every test recording of the index JSONs and write `<video_id>_output.npz`
     -> (test_list, save_list) with the reference's keys.  runner: a `RecordingRunner` built for these recordings (the periodic test pass of
     a training run keeps one and replays its graph) or any callable `recording_set -> [(poses, expressions, trans)]`; None builds one.
-    speakers: where each recording's speaker-table row comes from (`RecordingSet.from_index`; None: speaker 0, as the reference)."""
+    speakers: where each recording's speaker-table row comes from (`RecordingSet.from_index`; None: speaker 0, as the reference).
+    hint_mask: `(item, frames) -> 0 / 1 mask or None` — complete each recording's ground-truth motion where the mask is 1 and keep it where
+    it is 0 (`RecordingSet.from_index`); a `runner` handed in must then have been built with hints=True."""
     if device is None:
         device = getattr(runner, "device", None) or model.device
-    rs = RecordingSet.from_index(meta_paths, "test", device, speakers=speakers)
+    rs = RecordingSet.from_index(meta_paths, "test", device, speakers=speakers, hint_mask=hint_mask)
     if runner is None:
         runner = RecordingRunner.for_set(model, vq, rs)
     if pose_fps is None:
@@ -600,15 +747,16 @@ def test_pass(model, vq, meta_paths, save_path, runner=None, pose_fps=None, devi
 test_pass.__test__ = False                               # a library function, not a pytest case
 
 
-def generate_folder(model, vq, audio_folder, save_folder, runner=None, pose_fps=None, speaker_id=0):
+def generate_folder(model, vq, audio_folder, save_folder, runner=None, pose_fps=None, speaker_id=0, masked_motion=None, mask=None):
     """test_emage_audio.py:96-105: every `*.wav` of `audio_folder` (sorted) -> `<stem>_output.npz` in `save_folder`, no seed and zero
     `ref_trans` -> save_list.  speaker_id: the speaker-table row of every file (an int) or a callable `path -> row`; 0 (the default, what
-    the reference passes) names no speakers: a `runner` handed in keeps the ids it was built with."""
+    the reference passes) names no speakers: a `runner` handed in keeps the ids it was built with.  masked_motion / mask: motion hints, one
+    entry (an array or None) per file in sorted order (`RecordingSet`)."""
     paths = sorted(glob.glob(os.path.join(audio_folder, "*.wav")))
     if not paths:
         raise ValueError(f"generate_folder: no *.wav in {audio_folder}")
     ids = [int(speaker_id(p)) for p in paths] if callable(speaker_id) else (int(speaker_id) or None)
-    rs = RecordingSet.from_audio(paths, getattr(runner, "device", None) or model.device, speaker_ids=ids)
+    rs = RecordingSet.from_audio(paths, getattr(runner, "device", None) or model.device, speaker_ids=ids, masked_motion=masked_motion, mask=mask)
     if runner is None:
         runner = RecordingRunner.for_set(model, vq, rs)
     if pose_fps is None:

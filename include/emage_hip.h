@@ -991,6 +991,20 @@ long emage_val_metrics_workspace_bytes(int M, int n_entries);
 int emage_val_metrics(const emage_val_entry* entries, int n_entries, int M, int T, const int* n_valid, void* acc,
                       void* workspace, long workspace_bytes, void* stream);
 
+/*
+ * rep15d (csrc/motion_rep.hip): the motion representation the reference's BC / L1div metrics read, emage_utils/motion_rep_transfer.py:51-64,
+ * from what this library generates and the joint positions that belong to it.
+ *   poses (B * T, 165) fp32 axis-angle, contiguous;  joints (B * T, >= 55, 3) fp32 rows of pitch ld_joints >= 165 floats: the first 55 SMPL-X
+ *   joints of each frame (from whatever evaluates the body model);  rep (B, T, 55, 15) fp32, contiguous, per joint
+ *   [position 3 | velocity 3 | rot-6D 6 | angular velocity 3].
+ * Differences per sequence of T >= 2 frames: (x[1] - x[0]) / dt at the first frame, (x[n + 1] - x[n - 1]) / (2 dt) inside,
+ * (x[T - 1] - x[T - 2]) / dt at the last; x = the joint position (velocity) or the pose (angular velocity); fp32 subtraction, then an fp32
+ * division.  rot-6D is emage_axis_angle_to_rot6d's arithmetic, bit for bit.  One launch, no frame of another sequence is read.
+ * EMAGE_EINVAL before any launch: a NULL pointer, B <= 0, T < 2, ld_joints < 165, dt not positive, B * T beyond the grid limit.
+ */
+#define EMAGE_REP_JOINTS 55
+int emage_motion_rep(const float* poses, const float* joints, long ld_joints, float dt, float* rep, int B, int T, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -13,6 +13,7 @@ F32, BF16, F16X3, H2 = 0, 1, 2, 3
 PCM_S16, PCM_S24, PCM_S32, PCM_F32 = 0, 1, 2, 3       # EMAGE_PCM_*: the sample formats of emage_audio_resample
 AUDIO_TILE = 1024                                     # EMAGE_AUDIO_TILE: outputs per tile of emage_audio_resample
 AUDIO_TAPS_LDS_BYTES, AUDIO_SPAN_LDS_BYTES = 96 * 1024, 64 * 1024      # EMAGE_AUDIO_*_LDS_BYTES: the LDS budgets a rate pair must fit
+REP_JOINTS = 55                                       # EMAGE_REP_JOINTS: the joints of the pose layout, (T, 165)
 ABI_VERSION = 20                                     # unchanged by the gradient-norm, clip-store and validation entry points: they were ADDED, no existing prototype moved
 
 _p, _i, _f, _l, _d = C.c_void_p, C.c_int, C.c_float, C.c_long, C.c_double
@@ -163,6 +164,7 @@ SIGNATURES = {
     "emage_softmax2_mix": [_p, _i, _p, _i, _p, _i, _p, _i, _i, _i, _p],
     "emage_lstm_inputs": [_p, _p, _i, _p, _l, _i, _i, _p, _p, _i, _i, _i, _i, _p],
     "emage_rot6d_scatter": [_p, _i, _p, _p, _i, _i, _p],
+    "emage_motion_rep": [_p, _p, _l, _f, _p, _i, _i, _p],
 }
 RESTYPES = {"emage_bn_stats_workspace_bytes": _l, "emage_vq_quantize_train_workspace_bytes": _l, "emage_wav_conv_in_backward_workspace_bytes": _l, "emage_layernorm_backward_affine_workspace_bytes": _l,
             "emage_grad_norm_workspace_bytes": _l, "emage_val_metrics_workspace_bytes": _l, "emage_embedding_backward_workspace_bytes": _l}

@@ -13,7 +13,7 @@ import subprocess
 import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-SOURCES = ["gemm.hip", "gemm_h2.hip", "attention.hip", "qkv_attention.hip", "q_attention.hip", "vq.hip", "vq_train.hip", "embedding.hip", "elementwise.hip", "motion.hip", "wavconv.hip", "audio.hip", "convslab.hip", "lstm.hip", "lstmseq.hip", "train.hip", "train_backward.hip", "optim.hip", "data.hip", "recordings.hip", "stream.hip", "val.hip", "version.hip"]
+SOURCES = ["gemm.hip", "gemm_h2.hip", "attention.hip", "qkv_attention.hip", "q_attention.hip", "vq.hip", "vq_train.hip", "embedding.hip", "elementwise.hip", "motion.hip", "wavconv.hip", "audio.hip", "convslab.hip", "lstm.hip", "lstmseq.hip", "train.hip", "train_backward.hip", "optim.hip", "data.hip", "recordings.hip", "stream.hip", "val.hip", "motion_rep.hip", "version.hip"]
 HEADERS = ["common.h", "gemm_tile.h", "h2_tile.h", "h2.h", "attn_tile.h", "attn_site.h", "ln_row.h", "rot_math.h", "col_reduce.h", "philox.h", "argmax_row.h", "vel_step.h", "pcm_taps.h"]
 LIB = os.path.join(HERE, "libemage_hip.so")
 TOOLS_LIB = os.path.join(HERE, "libemage_hip_tools.so")

@@ -2526,3 +2526,23 @@ def rot6d_scatter(rot6d2d, slot_of_joint, n_joints=55):
     out = torch.empty(m, n_joints * 3, dtype=torch.float32, device=rot6d2d.device)
     _rot6d_scatter(rot6d2d, slot_of_joint, out)
     return out
+
+
+REP_JOINTS = _lib.REP_JOINTS
+
+
+@_op("motion_rep", "(Tensor poses, Tensor joints, float dt, Tensor(a!) rep) -> ()")
+def _motion_rep(poses, joints, dt, rep):
+    b, t = rep.shape[0], rep.shape[1]
+    check(_lib.load().emage_motion_rep(_ptr(poses), _ptr(joints), joints.stride(0), dt, _ptr(rep), b, t, _stream()), "motion_rep")
+
+
+def motion_rep(poses, joints, dt, rep):
+    """See include/emage_hip.h: emage_motion_rep.  poses (B T, 165), joints (B T, >= 55, 3) rows of any pitch -> rep (B, T, 55, 15), all fp32."""
+    _dev(poses)
+    b, t = rep.shape[0], rep.shape[1]
+    assert rep.dtype == torch.float32 and rep.is_contiguous() and tuple(rep.shape) == (b, t, REP_JOINTS, 15)
+    assert poses.dtype == torch.float32 and poses.is_contiguous() and tuple(poses.shape) == (b * t, 3 * REP_JOINTS)
+    assert joints.dtype == torch.float32 and joints.dim() == 3 and joints.shape[0] == b * t and joints.shape[1] >= REP_JOINTS and joints.shape[2] == 3
+    assert joints.stride(2) == 1 and joints.stride(1) == 3 and (b * t == 1 or joints.stride(0) >= 3 * REP_JOINTS)
+    _motion_rep(poses, joints, float(dt), rep)

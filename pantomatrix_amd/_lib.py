@@ -215,6 +215,13 @@ class EmageKernelError(RuntimeError):
     pass
 
 
+def nonfinite_error(count, precision, where):
+    """What every runner raises when its health counter came back non-zero: `count` non-finite values `where` ("among the network outputs
+    of a tick", "in the generated motion"), computed in `precision`."""
+    return FloatingPointError(f"{int(count)} non-finite values {where} (precision {precision!r}): in f16x3 an activation beyond |x| < 4094 overflows "
+                              "the fp16 planes — run this checkpoint with set_precision('fp32')")
+
+
 def check(code: int, what: str):
     if code != 0:
         kind = "unsupported argument (EMAGE_EINVAL)" if code < 0 else f"hipError {code}"

@@ -18,7 +18,7 @@ import numpy as np
 import torch
 
 from . import motion_io, ops
-from ._lib import EmageKernelError
+from ._lib import EmageKernelError, nonfinite_error
 from .data import SMPLX_FPS
 from .modeling_lstm_audio import ragged_batch_limit
 from .recordings import RecordingSet, _host_ids
@@ -163,8 +163,7 @@ class LstmRecordingRunner:
         self.nonfinite_host.copy_(self.nonfinite, non_blocking=True)
         torch.cuda.current_stream(self.device).synchronize()
         if int(self.nonfinite_host[0]):
-            raise FloatingPointError(f"{int(self.nonfinite_host[0])} non-finite values in the generated motion (precision {self.model.precision!r}): in f16x3 an "
-                                     "activation beyond |x| < 4094 overflows the fp16 planes — run this checkpoint with set_precision('fp32')")
+            raise nonfinite_error(self.nonfinite_host[0], self.model.precision, "in the generated motion")
         if int(self.nonfinite_host[1]):
             raise EmageKernelError("emage_lstm_layer: a block timed out waiting for its group (blocks not co-resident: another kernel holding CUs?); "
                                    "the motion of this pass is invalid")

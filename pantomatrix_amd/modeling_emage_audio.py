@@ -19,13 +19,14 @@ LayerNorm / softmax / arg-min: fastest, not index-exact).
 """
 from __future__ import annotations
 
+import contextlib
 import json
 import os
 from typing import NamedTuple
 
 import torch
 
-from . import ops, spec, synthetic
+from . import ops, spec, synthetic, windows
 from .streams import Fork
 from ._lib import BF16, F32, F16X3, H2
 from .configuration_emage_audio import EmageAudioConfig, EmageVAEConvConfig, EmageVQVAEConvConfig
@@ -76,7 +77,7 @@ class _EmageModule(torch.nn.Module):
         self.hoist_audio = True                # inference(): waveform-only features of all full windows in one pass
         self.seed_only_decode = True           # inference(): per-window decode covers only the frames that feed the seed
         self.health_counter = None             # optional int32 device counter of non-finite logits / latents met by infer_codes (runtime.ClipRunner)
-        self.health_pending = None             # ... or a list that collects those tensors instead: the runner counts them in one launch at the end
+        self.health_pending = None             # ... or a list that collects those tensors instead (`collect_health()`): the caller counts them in one launch
         self.slab_convs = True                 # WavEncoder: LDS-resident-slab convolutions + fused block 0 (A/B switch; same bits)
         self.h2_residual = True                # EMAGE_H2 mode: LayerNorm writes ONE output, the H2 image, and the sub-layers read their residual from
                                                # it ((hi + lo) / 16: 2^-22 relative); False = a float32 twin beside every H2 image (round 3's default:
@@ -1755,6 +1756,42 @@ class EmageAudioModel(_WavEncoderMixin, _EmageModule):
         r = 5 + max(int(getattr(vq_model, f"vq_model_{p}").config.vae_layer) for p in ("face", "upper", "hands", "lower"))
         return min(t, self.config.seed_frames + r)
 
+    @contextlib.contextmanager
+    def collect_health(self):
+        """While the block runs, `_window_codes` appends the logits / latents it takes codes from to the list this yields instead of
+        counting them one by one; the caller counts them with `ops.count_nonfinite_multi` (or hands a counter to `_window_step`).  On ANY
+        exit `health_pending` is None again.  Not re-entrant: a second one inside the first raises RuntimeError (the inner block would
+        otherwise steal the outer one's tensors) and leaves the outer list installed."""
+        if self.health_pending is not None:
+            raise RuntimeError("collect_health: already collecting (the blocks do not nest)")
+        self.health_pending = pending = []
+        try:
+            yield pending
+        finally:
+            self.health_pending = None
+
+    def _window_step(self, vq_model, audio, speaker_id, motion, mask, seed, codes, col0, need_seed, counter=None, _audio_feats=None,
+                     _tables=None, _hints=None):
+        """ONE autoregressive window of M:380-426, for every caller (`_windows` for `infer_codes`, `recordings.RecordingRunner`,
+        `streaming.StreamBatch`, tools/bench_stream.py): the lean forward of `motion` / `mask` ((B, t, 337) views) with the seed rows
+        `seed` (B, seed_frames, 337) spliced in, then the window's code indices into columns [col0, col0 + t) of the (B, L) buffers `codes`,
+        then — with `counter`, an int32 device counter, inside `collect_health()` — one `ops.count_nonfinite_multi` over what was collected
+        so far, then, if `need_seed`, the decode of the window's last frames (M:412-418: as many as can reach the last `seed_frames`
+        outputs, `_seed_decode_frames`; the whole window with `seed_only_decode` off — the same bits).
+        -> the next window's seed, a (B, seed_frames, 337) view of the decode, or None."""
+        b, t = motion.shape[:2]
+        net = self.forward(audio, speaker_id, motion, mask, use_audio=True, _audio_feats=_audio_feats, _tables=_tables, _lean=True, _seed=seed,
+                           _hints=_hints)
+        self._window_codes(net, vq_model, codes, col0, b, t)
+        if counter is not None and self.health_pending:
+            ops.count_nonfinite_multi(list(self.health_pending), counter)
+            del self.health_pending[:]
+        if not need_seed:
+            return None
+        ts = self._seed_decode_frames(vq_model, t) if self.seed_only_decode else t
+        dec = vq_model.decode(**{f"{p}_index": v[:, col0 + t - ts:col0 + t] for p, v in codes.items()})["all_motion4inference"]
+        return dec[:, ts - self.config.seed_frames:]
+
     def _windows(self, audio, speaker_id, vq_model, masked_motion=None, mask=None, want_codes=False):
         """Generator over the autoregressive windows of M:343-470; yields (forward outputs, frames to keep).  Windows
         of the clip tensors (audio, motion, mask, code buffers) are passed to the kernels as views."""
@@ -1764,12 +1801,10 @@ class EmageAudioModel(_WavEncoderMixin, _EmageModule):
         if audio.stride(1) != 1:
             audio = audio.contiguous()
         bs = audio.shape[0]
-        length = audio.shape[1] * 30 // 16000                                                   # M:345
+        length = windows.frames_of(audio.shape[1])                                              # M:345
         key = (bs, length, str(dev))
         if key not in self._templates:               # identity pose + all-ones mask (M:347-358), read-only, reused
-            tmpl = torch.zeros(bs, length, c.pose_dims + 7, device=dev)
-            tmpl[:, :, 0:c.pose_dims:6] = 1.0        # identity rot6d [1,0,0,0,1,0] per joint
-            tmpl[:, :, 4:c.pose_dims:6] = 1.0
+            tmpl = windows.identity_seed(bs, length, c.pose_dims + 7, device=dev)
             self._templates = {key: (tmpl, torch.ones_like(tmpl))}
         motion, full_mask = self._templates[key]
         if masked_motion is not None:
@@ -1779,8 +1814,8 @@ class EmageAudioModel(_WavEncoderMixin, _EmageModule):
             full_mask = full_mask.clone()
             full_mask[:, :mask.shape[1]] = mask.to(dev)
         window, pre = c.pose_length, c.seed_frames
-        rounds, remain = (length - pre) // (window - pre), (length - pre) % (window - pre)       # M:364-368
-        spf = 16000 // 30
+        rounds, _remain, tail_frames = windows.split_length(length, window, pre)                 # M:364-368
+        spf = windows.SPF
         hop = window - pre
         last = motion[:, :pre]                                                                   # M:370: seed of window 0
         routes = self._routes()
@@ -1817,17 +1852,17 @@ class EmageAudioModel(_WavEncoderMixin, _EmageModule):
                 t = end - start
                 a = audio[:, start * spf:start * spf + t * spf]                                      # M:393-394
                 # the seed splice (M:386-391) happens inside the packing kernel: frames < pre take `last` where masked
-                net = self.forward(a, speaker_id, motion[:, start:end], full_mask[:, start:end], use_audio=True,
-                                   _audio_feats=feats, _tables=tables, _lean=want_codes, _seed=last)
-                open_fork = None                        # forward()'s own fork joined the side streams
-                seed = None
                 if want_codes:
-                    self._window_codes(net, vq_model, codes, start, bs, t)
-                    net["_codes"] = codes
-                    sel = {f"{p}_index": v[:, start:end] for p, v in codes.items()}
-                elif need_seed:
-                    sel = self._select_codes(net)
+                    seed = self._window_step(vq_model, a, speaker_id, motion[:, start:end], full_mask[:, start:end], last, codes, start,
+                                             need_seed, _audio_feats=feats, _tables=tables)
+                    open_fork = None                    # forward()'s own fork joined the side streams
+                    return {"_codes": codes}, seed
+                net = self.forward(a, speaker_id, motion[:, start:end], full_mask[:, start:end], use_audio=True,
+                                   _audio_feats=feats, _tables=tables, _seed=last)
+                open_fork = None
+                seed = None
                 if need_seed:
+                    sel = self._select_codes(net)
                     # only the last `seed_frames` of the decode feed the next window (M:418): decode just the frames
                     # that can influence them (exact, see _seed_decode_frames)
                     ts = self._seed_decode_frames(vq_model, t) if self.seed_only_decode else t
@@ -1836,7 +1871,7 @@ class EmageAudioModel(_WavEncoderMixin, _EmageModule):
                     seed = dec[:, ts - pre:]                                                         # (B, pre, 337) view
                 return net, seed
 
-            tail = remain > pre
+            tail = tail_frames > 0
             for i in range(rounds):                                                                  # M:380-426
                 start = i * hop
                 # the decode only feeds the next window's seed: the reference also runs it after the last window
@@ -1847,8 +1882,8 @@ class EmageAudioModel(_WavEncoderMixin, _EmageModule):
                 yield net, window - pre
             if tail:                                                                                 # M:428-470
                 start = rounds * hop
-                net, _ = run_window(start, start + pre + remain, need_seed=False)
-                yield net, pre + remain
+                net, _ = run_window(start, start + tail_frames, need_seed=False)
+                yield net, tail_frames
         finally:
             if open_fork is not None:                   # abandoned before the first window ran: join the side streams
                 open_fork.__exit__(None, None, None)

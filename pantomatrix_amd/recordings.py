@@ -19,7 +19,7 @@ a tail group's seed rows, scatters its codes into each recording's slot and pack
 keyframes, kept body parts) are a third table-driven input: `emage_pack_motion_hints` (csrc/elementwise.hip) packs each forward's window
 operand out of a per-frame hint store (`RecordingRunner(hints=True)`).
 
-* ``window_schedule``   the schedule itself, pure Python (the host tests restate M:364-368 / M:428-431 against it);
+* ``window_schedule``   the schedule itself, pure Python (`windows.py`, re-exported here; the host tests restate M:364-368 / M:428-431 against it);
 * ``RecordingSet``      the recordings of a split (``from_index``) or a list of waveforms / WAV files (``from_audio``) on the device;
 * ``RecordingRunner``   the pass for one tuple of lengths, eager or as one captured graph;
 * ``test_pass``         `inference_fn`: the index JSONs in, `<video_id>_output.npz` files and (test_list, save_list) out;
@@ -34,56 +34,14 @@ import numpy as np
 import torch
 
 from . import motion_io, ops
+from ._lib import nonfinite_error
 from .data import SMPLX_FPS, _is_s16_mono, _speaker_rows, foot_contact_path
+from .runtime import PackedGraphs
+from .windows import MODEL_SR, SEED_DIMS, SPF, Schedule, frames_of, identity_seed, window_schedule      # noqa: F401  (re-exported: `recordings.window_schedule` ...)
 
-MODEL_SR = 16000                                        # `inference()` hard-codes 16000 // 30 samples per frame (M:345, M:393)
-SPF = MODEL_SR // SMPLX_FPS
-SEED_DIMS = 337                                         # 55 joints x 6, trans, foot contact (T:59-60)
 HINT_LD = 344                                           # row pitch of a hint store: 337 rounded up to 8 columns (32 bytes of motion, 8 of flags)
 WIDTHS = (("poses", 165), ("expressions", 100), ("trans", 3))
 STATUS_TEXT = ops.STATUS
-
-
-class Schedule:
-    """What `window_schedule` returns.  rounds / remain / frames: per recording (frames = output frames).  steps: [(start frame, [ids of the
-    recordings that run full window i])]; tails: {tail length: [(recording id, start frame)]} in input order."""
-
-    def __init__(self, lengths, rounds, remain, frames, steps, tails, window, seed_frames):
-        self.lengths, self.rounds, self.remain, self.frames, self.steps, self.tails = lengths, rounds, remain, frames, steps, tails
-        self.window, self.seed_frames = window, seed_frames
-
-    @property
-    def n_windows(self):
-        """(recording, window) pairs of the schedule, tails included."""
-        return sum(len(ids) for _s, ids in self.steps) + sum(len(v) for v in self.tails.values())
-
-
-def window_schedule(lengths, window=64, seed_frames=4):
-    """The windows `EmageAudioModel.inference` (M:364-368, M:380-382, M:428-431) runs for recordings of `lengths` frames, as a lock-step
-    schedule -> `Schedule`.  Full windows: `rounds = (T - seed) // (window - seed)` of them at starts i * (window - seed), each keeping its
-    first window - seed frames.  Tail: when `remain = (T - seed) % (window - seed)` exceeds seed, seed + remain frames from
-    rounds * (window - seed), kept whole; T < window is a tail only, T == window one full window (window - seed frames out, no tail), and a
-    remainder of at most `seed` frames is dropped.  Output frames: (window - seed) * rounds + (seed + remain if remain > seed else 0)."""
-    pre, hop = int(seed_frames), int(window) - int(seed_frames)
-    if hop <= 0:
-        raise ValueError(f"window_schedule: window {window} must exceed seed_frames {seed_frames}")
-    lengths = [int(t) for t in lengths]
-    if any(t <= pre for t in lengths):
-        raise ValueError(f"window_schedule: every recording needs more than {pre} frames, got {lengths}")
-    rounds = [(t - pre) // hop for t in lengths]
-    remain = [(t - pre) % hop for t in lengths]
-    frames = [hop * r + (pre + m if m > pre else 0) for r, m in zip(rounds, remain)]
-    steps = [(i * hop, [k for k, r in enumerate(rounds) if r > i]) for i in range(max(rounds, default=0))]
-    tails = {}
-    for k, (r, m) in enumerate(zip(rounds, remain)):
-        if m > pre:
-            tails.setdefault(pre + m, []).append((k, r * hop))
-    return Schedule(lengths, rounds, remain, frames, steps, tails, int(window), pre)
-
-
-def frames_of(n_samples):
-    """M:345."""
-    return int(n_samples) * SMPLX_FPS // MODEL_SR
 
 
 def axis_angle_to_rot6d(aa):
@@ -102,12 +60,9 @@ def axis_angle_to_rot6d(aa):
                         two_s * (i * j + k * r), 1 - two_s * (i * i + k * k), two_s * (j * k - i * r)), -1)
 
 
-def identity_seed(n, frames=4):
-    """(n, frames, 337): identity rot6d [1, 0, 0, 0, 1, 0] per joint, zero trans / foot contact (M:348-351)."""
-    seed = torch.zeros(n, frames, SEED_DIMS)
-    seed[:, :, 0:330:6] = 1.0
-    seed[:, :, 4:330:6] = 1.0
-    return seed
+def _hint_template(rows):
+    """(rows, HINT_LD) float32: the identity template in the first 337 columns of a hint store, zero padding behind them."""
+    return torch.nn.functional.pad(identity_seed(1, rows)[0], (0, HINT_LD - SEED_DIMS))
 
 
 def part_columns(part):
@@ -237,9 +192,7 @@ class RecordingSet:
         self.hint_offsets = np.cumsum([0] + self.hint_len)
         self.hinted = any(k is not None and bool((k == 0).any()) for k in masks)
         total = int(self.hint_offsets[-1])
-        motion = np.zeros((total, HINT_LD), np.float32)
-        motion[:, 0:330:6] = 1.0                                                        # the identity template (M:348-351) ...
-        motion[:, 4:330:6] = 1.0
+        motion = _hint_template(total).numpy()                                          # the identity template (M:348-351) ...
         keep = np.ones((total, HINT_LD), np.uint8)                                      # ... and the all-ones mask (M:356)
         for a, k, lo in zip(motions, masks, self.hint_offsets[:-1]):
             if a is not None:
@@ -344,12 +297,12 @@ class RecordingRunner:
     Internally the recordings are sorted by length, longest first, so the recordings active in window step i are a PREFIX of the per-recording
     buffers (seed chain, code buffers) and recordings of equal output length are neighbours: every full-window step is one `forward` on a row
     range (split into groups of at most `max_batch` rows), reading its audio from a contiguous batch `emage_gather_windows` fills.  The
-    waveform-only work (WavEncoders, audio projection, cross-attention K / V) is hoisted ahead of the sequential loop as `_windows` does,
+    waveform-only work (WavEncoders, audio projection, cross-attention K / V) is hoisted ahead of the sequential loop as `EmageAudioModel._windows` does,
     in chunks of at most `max_hoist_rows` (recording, window) sequences, so its memory is bounded.  Each tail group — the recordings
     with the same tail length — is one `forward`: audio and seed rows gathered, codes scattered into each recording's slot by the two kernels.
     The final decode runs per group of equal length at the true length with `get_global_motion=True` and each recording's own `ref_trans`;
-    its rows are packed into one flat buffer per output, in INPUT order.  Seed chain, lean code path and health counter are those of
-    `infer_codes` / `ClipRunner._step`; non-finite outputs raise FloatingPointError.
+    its rows are packed into one flat buffer per output, in INPUT order.  Every forward — full-window unit or tail group — is one
+    `EmageAudioModel._window_step` (lean forward, codes, health flush, seed decode); non-finite outputs raise FloatingPointError.
 
     seeded: take the motion seeds and `ref_trans` of the `RecordingSet` handed to `__call__`; False: identity seed, zero `ref_trans`.
     speaker_id: one id for every recording (an int; both reference loops pass zeros) or one id per recording, in input order.  Ids are INPUT
@@ -361,10 +314,10 @@ class RecordingRunner:
     (`load()` refuses the rest: build the runner from the set, `for_set`).  audio_dtype: the flat array's dtype (torch.float32 / int16).
 
     use_graph: the whole pass is ONE captured graph for this tuple of lengths; a second call with other audio of the same lengths replays
-    it — the periodic test pass of a training run.  New weights reach a replay as in `validation.Validator`: the packing of the model's
-    operand set is captured into a second graph over the same memory pool, and `__call__` replays it first whenever the model's version
-    stamp has moved (a training step, `load_state_dict`), so the pass reads operands packed from the current parameters at the addresses it
-    was captured with.  The VQ models are frozen in the reference's training (T:233-245); after changing THEM build a new runner.
+    it — the periodic test pass of a training run.  New weights reach a replay as in `validation.Validator` (`runtime.PackedGraphs`, which
+    `graph` then is): the packing of the model's operand set is captured into a second graph over the same memory pool and replayed first
+    whenever the model's version stamp has moved (a training step, `load_state_dict`), so the pass reads operands packed from the current
+    parameters at the addresses it was captured with.  The VQ models are frozen in the reference's training (T:233-245); after changing THEM build a new runner.
 
     hints: False — every forward reads the read-only templates (identity pose, all-ones mask), the launch sequence of a runner without the
     argument; `load()` of a set whose `hinted` is True raises.  True — the pass honours a set's motion hints (`RecordingSet`:
@@ -415,8 +368,7 @@ class RecordingRunner:
         self.tmpl_motion = identity_seed(mb, w).to(dev)                                # identity pose + all-ones mask (M:347-358), read-only
         self.tmpl_mask = torch.ones_like(self.tmpl_motion)
         if self.hints:                                                                 # the template's contents: a row nobody loaded is no hint
-            self.hint_motion = identity_seed(1, int(self.frame_offsets[-1]))[0].to(dev)
-            self.hint_motion = torch.cat([self.hint_motion, torch.zeros(self.hint_motion.shape[0], HINT_LD - SEED_DIMS, device=dev)], dim=1)
+            self.hint_motion = _hint_template(int(self.frame_offsets[-1])).to(dev)
             self.hint_keep = torch.ones(self.hint_motion.shape[0], HINT_LD, dtype=torch.uint8, device=dev)
             self.hint_table = torch.tensor([[int(self.frame_offsets[r]) + s, 0] for r, s, _t in self.hint_rows], dtype=torch.int64, device=dev)
         routes = model._routes()
@@ -436,12 +388,12 @@ class RecordingRunner:
         self._order_dev = torch.tensor(self.order, dtype=torch.long, device=dev)
         self.set_speaker_ids(ids)
         self.precision = model.precision
-        self.graph, self._pack_graph, self._packed_stamp, self._operands = None, None, None, None
+        self.graph = None
         self._pass()                                                                    # packs weights, warms the allocator, validates shapes
         if on_gpu:
             torch.cuda.synchronize(dev)
         if use_graph and on_gpu:
-            self._capture()
+            self.graph = PackedGraphs(model, vq_model, self._pass, "RecordingRunner: the pass")
 
     # ---- the static plan (host, once) ----------------------------------------------------------------------------------------------
     def _plan(self, sched):
@@ -512,11 +464,6 @@ class RecordingRunner:
         return rows / max(self.steps, 1)
 
     # ---- the pass: launches only, no host state ---------------------------------------------------------------------------------------
-    def _flush_health(self, pending):
-        if pending:
-            ops.count_nonfinite_multi(list(pending), self.nonfinite)
-            del pending[:]
-
     def _sliced_tables(self, tables, lo, n):
         """Rows of the speaker / positional tables for the recordings [lo, lo + n) the tables were built over."""
         from .modeling_emage_audio import _X
@@ -538,10 +485,10 @@ class RecordingRunner:
                 g.ids.copy_(self.speaker_id.index_select(0, g.ranks))
 
     def _hints_of(self, row0, n):
-        """The extra `forward` argument of a unit / tail group whose table rows are [row0, row0 + n): nothing without hints."""
+        """The `_hints` argument of a unit / tail group whose table rows are [row0, row0 + n): None without hints."""
         if not self.hints:
-            return {}
-        return {"_hints": (self.hint_motion[:, :SEED_DIMS], self.hint_keep[:, :SEED_DIMS], self.hint_table[row0:row0 + n], self.status)}
+            return None
+        return self.hint_motion[:, :SEED_DIMS], self.hint_keep[:, :SEED_DIMS], self.hint_table[row0:row0 + n], self.status
 
     def set_hints(self, recording_set):
         """A set's hint rows into the store and the `avail` column of the table: stream-ordered copies into fixed addresses.  Rows of the
@@ -565,11 +512,10 @@ class RecordingRunner:
 
     def _full_windows(self):
         from .modeling_emage_audio import _Ctx, Fork
-        model, vq, w, pre = self.model, self.vq, self.window, self.pre
+        model, vq, w = self.model, self.vq, self.window
         self.nonfinite.zero_()
         self.seeds.copy_(self.seed0)
-        model.health_pending = pending = []
-        try:
+        with model.collect_health():
             tables = None
             if self.units:
                 # equal ids: the table of the widest unit, a prefix of it for every unit; ids that differ: the table of every recording that
@@ -591,38 +537,27 @@ class RecordingRunner:
                     if feats is not None:
                         f = model._feats_of_clips(feats, k0, n, w)
                     row0 = u.lo if self.per_recording_ids else 0
-                    net = model.forward(win[k0:k0 + n], self.speaker_id[row0:row0 + n], self.tmpl_motion[:n], self.tmpl_mask[:n], use_audio=True,
-                                        _audio_feats=f, _tables=self._sliced_tables(tables, row0, n), _lean=True, _seed=self.seeds[u.lo:u.hi],
-                                        **self._hints_of(u.seq, n))
-                    codes = {p: v[u.lo:u.hi] for p, v in self.codes.items()}
-                    model._window_codes(net, vq, codes, u.start, n, w)
-                    self._flush_health(pending)
-                    if u.need_seed:                         # M:412-418: only the last frames of the decode feed the next window's seed
-                        ts = model._seed_decode_frames(vq, w) if model.seed_only_decode else w
-                        sel = {f"{p}_index": v[:, u.start + w - ts:u.start + w] for p, v in codes.items()}
-                        dec = vq.decode(**sel)["all_motion4inference"]
-                        self.seeds[u.lo:u.hi].copy_(dec[:, ts - pre:])
+                    seed = model._window_step(vq, win[k0:k0 + n], self.speaker_id[row0:row0 + n], self.tmpl_motion[:n], self.tmpl_mask[:n],
+                                              self.seeds[u.lo:u.hi], {p: v[u.lo:u.hi] for p, v in self.codes.items()}, u.start, u.need_seed,
+                                              counter=self.nonfinite, _audio_feats=f, _tables=self._sliced_tables(tables, row0, n),
+                                              _hints=self._hints_of(u.seq, n))
+                    if seed is not None:
+                        self.seeds[u.lo:u.hi].copy_(seed)
                 del feats
-        finally:
-            model.health_pending = None
 
     def _tail_groups(self):
         model, vq, pre = self.model, self.vq, self.pre
-        model.health_pending = pending = []
-        try:
+        with model.collect_health():
             for g in self.tails:
                 n, t = g.n, g.t
                 a = self.tail_audio[:n * t * SPF].view(n, t * SPF)
                 ops.gather_windows(self.audio, g.offsets, a, self.status)
                 ops.copy_segments(self.seeds, self.tail_seed, g.seed_segs, pre * SEED_DIMS * 4, 1, self.status)
-                net = model.forward(a, g.ids if self.per_recording_ids else self.speaker_id[:n], self.tmpl_motion[:n, :t], self.tmpl_mask[:n, :t], use_audio=True, _lean=True,
-                                    _seed=self.tail_seed[:n], **self._hints_of(g.hint_lo, n))
-                model._window_codes(net, vq, {p: v[:n * t].view(n, t) for p, v in self.tail_codes.items()}, 0, n, t)
-                self._flush_health(pending)
+                model._window_step(vq, a, g.ids if self.per_recording_ids else self.speaker_id[:n], self.tmpl_motion[:n, :t], self.tmpl_mask[:n, :t],
+                                   self.tail_seed[:n], {p: v[:n * t].view(n, t) for p, v in self.tail_codes.items()}, 0, False,
+                                   counter=self.nonfinite, _hints=self._hints_of(g.hint_lo, n))
                 for p, v in self.tail_codes.items():
                     ops.copy_segments(v, self.codes[p], g.code_segs, 8, t, self.status)
-        finally:
-            model.health_pending = None
 
     def _decode(self):
         vq = self.vq
@@ -633,21 +568,6 @@ class RecordingRunner:
             ops.count_nonfinite_multi(outs, self.nonfinite)
             for src, dst, (_k, wd) in zip(outs, self.flat, WIDTHS):
                 ops.copy_segments(src, dst, d.segs, wd * 4, d.frames, self.status)
-
-    def _capture(self):
-        model, vq = self.model, self.vq
-        pack_graph, graph = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
-        with torch.cuda.graph(pack_graph, capture_error_mode="thread_local"):
-            model.invalidate_packed()
-            packed = model._engine()
-        with torch.cuda.graph(graph, pool=pack_graph.pool(), capture_error_mode="thread_local"):
-            self._pass()
-        if model._packed is not packed:
-            raise RuntimeError("RecordingRunner: the pass re-packed the operand set the packing graph had just built")
-        self._pack_graph, self.graph, self._packed_stamp = pack_graph, graph, None      # the first replay packs
-        # what the captured launches read (and the packing graph re-writes): alive as long as the graphs, and nobody else's
-        self._operands = (packed, [m._packed for m in vq._models()], dict(vq._templates))
-        model.invalidate_packed()
 
     # ---- one pass end to end ------------------------------------------------------------------------------------------------------------
     def load(self, recording_set):
@@ -674,12 +594,8 @@ class RecordingRunner:
         """One pass over the current input buffers, on the current stream; the results stay in `flat` (rows in input order)."""
         if self.graph is None:
             self._pass()
-            return
-        stamp = self.model._version_stamp()
-        if stamp != self._packed_stamp:
-            self._pack_graph.replay()
-            self._packed_stamp = stamp
-        self.graph.replay()
+        else:
+            self.graph.replay()                             # packs first when the model's version stamp has moved
 
     def __call__(self, recording_set=None):
         """-> [(poses (T_r, 165), expressions (T_r, 100), trans (T_r, 3))] per recording in input order: numpy views of pinned buffers,
@@ -697,8 +613,7 @@ class RecordingRunner:
             self.status.zero_()
             raise RuntimeError(f"RecordingRunner: the data-movement kernels reported status {status} ({STATUS_TEXT})")
         if bad:
-            raise FloatingPointError(f"{bad} non-finite values among the network outputs / the generated motion (precision {self.precision!r}): in f16x3 an "
-                                     "activation beyond |x| < 4094 overflows the fp16 planes — run this checkpoint with set_precision('fp32')")
+            raise nonfinite_error(bad, self.precision, "among the network outputs / the generated motion")
         host = [h.numpy() for h in self.host]
         return [tuple(h[self.out_offsets[r]:self.out_offsets[r + 1]] for h in host) for r in range(len(self.sample_counts))]
 

@@ -17,6 +17,7 @@ from __future__ import annotations
 import torch
 
 from . import ops
+from ._lib import nonfinite_error
 
 
 RESCALE_STEP = 4          # on_overflow="rescale": the twin's activation images hold x instead of 16 x (16x the range, 4 bits off the smallest values' lo plane)
@@ -133,16 +134,13 @@ class ClipRunner:
         # health check: inf / NaN among the network outputs the codes are taken from (the quantiser would launder them into valid
         # codes) and among the results — e.g. an activation beyond the f16x3 range
         self.nonfinite.zero_()
-        self.model.health_pending = pending = []
         was = (self.model.activation_shift, self.vq.activation_shift)
         self.model.set_activation_shift(self.shift)          # this runner's own (a rescaled twin differs from the models' setting)
         self.vq.set_activation_shift(self.shift)
         try:
             with ops.splitk_scope(self.splitk):
-                try:
+                with self.model.collect_health() as pending:
                     codes = self.model.infer_codes(self.audio, self.speaker_id, self.vq)
-                finally:
-                    self.model.health_pending = None
                 pred = self.vq.decode(**codes, get_global_motion=True, ref_trans=self.ref_trans)
         finally:
             self.model.set_activation_shift(was[0])
@@ -233,8 +231,37 @@ class ClipRunner:
     def _raise_if_nonfinite(self):
         n = int(self.nonfinite_host[0])
         if n:
-            raise FloatingPointError(f"{n} non-finite values among the network outputs / the generated motion (precision {self.precision!r}): in f16x3 an activation beyond "
-                                     "|x| < 4094 overflows the fp16 planes — run this checkpoint with set_precision('fp32')")
+            raise nonfinite_error(n, self.precision, "among the network outputs / the generated motion")
+
+
+class PackedGraphs:
+    """A captured pass that follows weight updates (`recordings.RecordingRunner`, `validation.Validator`): TWO graphs over one memory
+    pool — the packing of `model`'s operand set from the parameters as they stand when it is replayed, and `body()` over that set.
+    `replay()` runs the packing first whenever the model's version stamp has moved (a training step, `load_state_dict`), so the body reads
+    operands packed from the current parameters at the addresses it was captured with; the first replay always packs.  `who` names the
+    owner in the error raised when the body packs an operand set of its own.  `operands`: what the captured launches read (and the
+    packing graph re-writes) — alive as long as the graphs, and nobody else's: the model is left unpacked."""
+
+    def __init__(self, model, vq_model, body, who):
+        self.model = model
+        self.pack_graph, self.graph, self.packed_stamp = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph(), None
+        with torch.cuda.graph(self.pack_graph, capture_error_mode="thread_local"):
+            model.invalidate_packed()
+            packed = model._engine()
+        with torch.cuda.graph(self.graph, pool=self.pack_graph.pool(), capture_error_mode="thread_local"):
+            body()
+        if model._packed is not packed:
+            raise RuntimeError(f"{who} re-packed the operand set the packing graph had just built")
+        self.operands = (packed, [m._packed for m in vq_model._models()], dict(vq_model._templates))
+        model.invalidate_packed()
+
+    def replay(self, repack=None):
+        """repack: None — pack when a parameter or buffer of the model has changed since the last replay; True / False force or suppress it."""
+        stamp = self.model._version_stamp()
+        if repack or (repack is None and stamp != self.packed_stamp):
+            self.pack_graph.replay()
+            self.packed_stamp = stamp
+        self.graph.replay()
 
 
 class ClipPipeline:
@@ -355,8 +382,7 @@ class LstmClipRunner:
         self.nonfinite_host.copy_(self.nonfinite, non_blocking=True)
         torch.cuda.current_stream(self.device).synchronize()
         if int(self.nonfinite_host[0]):
-            raise FloatingPointError(f"{int(self.nonfinite_host[0])} non-finite values in the generated motion (precision {self.model.precision!r}): in f16x3 an "
-                                     "activation beyond |x| < 4094 overflows the fp16 planes — run this checkpoint with set_precision('fp32')")
+            raise nonfinite_error(self.nonfinite_host[0], self.model.precision, "in the generated motion")
         if int(self.nonfinite_host[1]):
             from ._lib import EmageKernelError
             raise EmageKernelError("emage_lstm_layer: a block timed out waiting for its group (blocks not co-resident: another kernel holding CUs?); "

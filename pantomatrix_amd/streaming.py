@@ -37,8 +37,9 @@ import numpy as np
 import torch
 
 from . import audio, ops, synthetic
+from ._lib import nonfinite_error
 from .audio import available                            # rule 4: the outputs that are final after n input frames
-from .recordings import MODEL_SR, SEED_DIMS, SPF, frames_of, identity_seed
+from .windows import MODEL_SR, SEED_DIMS, SPF, frames_of, identity_seed, split_length
 
 STATUS_TEXT = ops.STREAM_STATUS_TEXT
 _SAMPLE_BYTES = {"s16": 2, "s24": 3, "s32": 4, "f32": 4}
@@ -70,8 +71,8 @@ def tail_of(n_samples, pre=4, hop=60):
     total = frames_of(n_samples)
     if total <= pre:
         return 0, 0
-    rounds, remain = (total - pre) // hop, (total - pre) % hop
-    return rounds, (pre + remain if remain > pre else 0)
+    rounds, _remain, tail = split_length(total, hop + pre, pre)
+    return rounds, tail
 
 
 class Session:
@@ -378,20 +379,13 @@ class StreamBatch:
 
     def _tick(self):
         """The launches of one tick: no host state, so it is capturable."""
-        model, vq, s, w, pre = self.model, self.vq, self.slots, self.window, self.pre
+        model, vq = self.model, self.vq
         self._launch_push()
         ops.stream_windows(self.ring, self.table, self.win_audio, self.status)
-        model.health_pending = pending = []
-        try:
-            net = model.forward(self.win_audio, self.speaker_id, self.tmpl_motion, self.tmpl_mask, use_audio=True, _lean=True, _seed=self.seeds)
-            codes = self._codes_of(self.win_codes)
-            model._window_codes(net, vq, codes, 0, s, w)
-            ops.count_nonfinite_multi(list(pending), self.nonfinite)
-        finally:
-            model.health_pending = None
-        ts = model._seed_decode_frames(vq, w)                                # M:412-418: only the last frames of the decode feed the next seed
-        dec = vq.decode(**{f"{p}_index": v[:, w - ts:] for p, v in codes.items()})["all_motion4inference"]
-        ops.stream_commit(self.table, self.win_codes, self.hop, self.code_ring, self.segment, dec[:, ts - pre:], self.seeds, self.status)
+        with model.collect_health():
+            seed = model._window_step(vq, self.win_audio, self.speaker_id, self.tmpl_motion, self.tmpl_mask, self.seeds,
+                                      self._codes_of(self.win_codes), 0, True, counter=self.nonfinite)
+        ops.stream_commit(self.table, self.win_codes, self.hop, self.code_ring, self.segment, seed, self.seeds, self.status)
         aa, expr, vel = vq._decode_segments(**{f"{p}_index": v for p, v in self._codes_of(self.segment).items()})
         ops.count_nonfinite_multi([aa, expr, vel], self.nonfinite)
         v = self.out_views
@@ -405,8 +399,7 @@ class StreamBatch:
             raise RuntimeError(f"StreamBatch: the stream kernels reported status {status} ({STATUS_TEXT})")
         if bad:
             self.nonfinite.zero_()
-            raise FloatingPointError(f"{bad} non-finite values among the network outputs of a tick (precision {self.precision!r}): in f16x3 an activation "
-                                     "beyond |x| < 4094 overflows the fp16 planes — run this checkpoint with set_precision('fp32')")
+            raise nonfinite_error(bad, self.precision, "among the network outputs of a tick")
 
     def _emitted(self, views, k, n):
         codes = views["codes"][k, :n].numpy()
@@ -486,15 +479,10 @@ class StreamBatch:
                                        samples=t * SPF, ring_codes=self.ring_codes, seg_len=self.seg_len, out_rows=hop)
                 audio = torch.zeros(1, t * SPF, device=dev)
                 ops.stream_windows(self.ring[k:k + 1], torch.from_numpy(row).to(dev), audio, self.status)
-                model.health_pending = pending = []
-                try:
-                    net = model.forward(audio, self.speaker_id[k:k + 1], self.tmpl_motion[:1, :t], self.tmpl_mask[:1, :t], use_audio=True, _lean=True,
-                                        _seed=self.seeds[k:k + 1])
-                    tail = torch.zeros(n_p, 1, t, dtype=torch.int64, device=dev)
-                    model._window_codes(net, vq, self._codes_of(tail), 0, 1, t)
-                    ops.count_nonfinite_multi(list(pending), self.nonfinite)
-                finally:
-                    model.health_pending = None
+                tail = torch.zeros(n_p, 1, t, dtype=torch.int64, device=dev)
+                with model.collect_health():
+                    model._window_step(vq, audio, self.speaker_id[k:k + 1], self.tmpl_motion[:1, :t], self.tmpl_mask[:1, :t], self.seeds[k:k + 1],
+                                       self._codes_of(tail), 0, False, counter=self.nonfinite)
                 table, longest = ops.segment_table([(j * t, j * length + hop * rounds - lo, t) for j in range(n_p)], tail.numel(), last.numel(), dev)
                 ops.copy_segments(tail, last, table, 8, longest, self.status)
             aa, expr, vel = vq._decode_segments(**{f"{p}_index": v for p, v in self._codes_of(last).items()})

@@ -28,6 +28,7 @@ import torch
 from . import ops, training
 from ._lib import EmageKernelError, VAL_ACC_BATCHES, VAL_ACC_HITS, VAL_ACC_METER, VAL_ACC_ROWS, VAL_ACC_STATUS, VAL_LOSSES, VAL_MAX_ENTRIES
 from .modeling_emage_audio import _FOLD_WIDTH, _Ctx
+from .runtime import PackedGraphs
 from .streams import Fork
 
 TAGS = ("seed", "audio", "mask")                          # the three forwards, train_emage_audio.py:156-173
@@ -52,8 +53,7 @@ class Validator:
         self.acc = ops.val_accumulators(model.device)
         self.decoded, self.target_rot6d, self.codes = None, None, {}
         self._ws, self._full, self._frames = None, {}, None
-        self._graph, self._pack_graph, self._packed_stamp = None, None, None
-        self._graph_inputs, self._operands, self._recapture_pending = None, None, False
+        self._graph, self._graph_inputs, self._recapture_pending = None, None, False      # _graph: a `runtime.PackedGraphs`
 
     # ---- one step, device side --------------------------------------------------------------------------------------------------------
     def _n_valid(self, n_valid, bs, dev):
@@ -211,24 +211,15 @@ class Validator:
         for t, v in zip(advanced + [self.acc], rewind):
             t.copy_(v)
         self._graph_inputs = (batch, random_mask, prologue, n_valid, speaker_id)
-        # two graphs over one memory pool: the PACKING of the eval operand set from the parameters as they stand when it is replayed, and
-        # the step over that set.  Inside a validation pass the parameters stand still, so `replay()` runs the packing only when the
-        # model's version stamp has moved (a training step since: `Trainer` advances the counters) — 3.5 ms of a 19 ms replay at 56 clips
-        pack_graph, graph = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
-        with torch.cuda.graph(pack_graph, capture_error_mode="thread_local"):
-            model.invalidate_packed()
-            packed = model._engine()
-        with torch.cuda.graph(graph, pool=pack_graph.pool(), capture_error_mode="thread_local"):
+        # two graphs over one memory pool (`runtime.PackedGraphs`): the PACKING of the eval operand set from the parameters as they stand
+        # when it is replayed, and the step over that set.  Inside a validation pass the parameters stand still, so `replay()` runs the
+        # packing only when the model's version stamp has moved (a training step since: `Trainer` advances the counters) — 3.5 ms of a
+        # 19 ms replay at 56 clips
+        def body():
             if prologue is not None:
                 prologue()
             self._device_step(batch, random_mask, n_valid, speaker_id)
-        if model._packed is not packed:
-            raise RuntimeError("Validator.capture: the step re-packed the operand set the packing graph had just built")
-        self._pack_graph, self._graph, self._recapture_pending = pack_graph, graph, False
-        self._packed_stamp = None                              # the first replay packs
-        # what the captured launches read (and the packing graph re-writes): alive as long as the graphs, and nobody else's
-        self._operands = (packed, [m._packed for m in self.vq._models()], dict(self.vq._templates))
-        model.invalidate_packed()
+        self._graph, self._recapture_pending = PackedGraphs(model, self.vq, body, "Validator.capture: the step"), False
         return self
 
     def replay(self, repack=None):
@@ -239,11 +230,7 @@ class Validator:
             raise RuntimeError("Validator.replay: capture() first")
         if self._recapture_pending:
             self.capture(*self._graph_inputs)
-        stamp = self.model._version_stamp()
-        if repack or (repack is None and stamp != self._packed_stamp):
-            self._pack_graph.replay()
-            self._packed_stamp = stamp
-        self._graph.replay()
+        self._graph.replay(repack)
 
     # ---- a pass ---------------------------------------------------------------------------------------------------------------------
     def reset(self):
@@ -259,7 +246,7 @@ class Validator:
         ints = self.acc.view(torch.int64)
         pieces = [self.acc[VAL_ACC_METER:VAL_ACC_METER + VAL_LOSSES], ints[VAL_ACC_HITS:VAL_ACC_STATUS + 1].to(torch.float64)]      # exact below 2^53
         total = pdist.sum_over_group([torch.cat(pieces)], group=group)[0]
-        flag = self._operands[0].range_flag if (self._graph is not None and self._operands is not None) else None
+        flag = self._graph.operands[0].range_flag if self._graph is not None else None
         host = torch.cat([total, flag.reshape(-1)[:1].to(torch.float64)] if flag is not None else [total]).cpu()
         if flag is not None:
             self._stale_scales(int(host[-1]))

@@ -3,7 +3,7 @@
 them live and one window behind their audio — every tick each session pushes the 32 000 samples of its next window and the batch steps:
   replay     `step()` of a captured batch: staging on the host, two host-to-device copies, ONE graph replay, one device-to-host copy;
   eager      the same tick, its launches issued one by one (use_graph=False);
-  separate   S separate B = 1 windows through the entry points the parent commit has — `forward`, `_window_codes`, the seed decode and a
+  separate   S separate B = 1 windows — `EmageAudioModel._window_step` (forward, codes, seed decode) and a
              `decode(get_global_motion=True)` of the last 116 codes per session — which is what serving S live sessions costs without this
              module (a server there would in fact decode each session's whole history; the arm does not charge for that).
 `decode_ms` is the eager segment decode + emit alone (`_decode_segments` at B = S, T = 60 + 2 lag, and `emage_stream_emit`), and
@@ -180,14 +180,11 @@ def main():
         motion, mask = identity_seed(1, 64).to(dev), torch.ones(1, 64, 337, device=dev)
         codes = {p: torch.zeros(1, 64, dtype=torch.int64, device=dev) for p in sb.parts}
         seg = {f"{p}_index": torch.zeros(1, seg_len, dtype=torch.int64, device=dev) for p in sb.parts}
-        ts = model._seed_decode_frames(vq, 64)
         carry = sb.carry.clone()                                             # the decode arm must not move the live sessions' translation
 
         def separate():
             for _ in range(n):
-                net = model.forward(audio, spk, motion, mask, use_audio=True, _lean=True, _seed=seed1)
-                model._window_codes(net, vq, codes, 0, 1, 64)
-                vq.decode(**{f"{p}_index": v[:, 64 - ts:] for p, v in codes.items()})
+                model._window_step(vq, audio, spk, motion, mask, seed1, codes, 0, True)
                 pred = vq.decode(**seg, get_global_motion=True, ref_trans=torch.zeros(1, 3, device=dev))
                 pred["trans"].cpu()                                          # a session's frames leave the device every window
             torch.cuda.synchronize()

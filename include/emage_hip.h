@@ -944,6 +944,45 @@ int emage_stream_emit(const int* table, int slots, int seg_len, int out_rows, co
                       int ldv, int col0, float dt, const int64_t* segment, int parts, float* carry, float* poses, float* expressions,
                       float* trans, int64_t* codes, int* status, void* stream);
 
+/* Motion hints of live sessions (streaming.StreamBatch(motion_hints=True); rule 5 of pantomatrix_amd/streaming.py): ONE launch over all slots
+ * moves the tick's staged hint frames into the per-slot hint rings and writes the (slots, 2) int64 table emage_pack_motion_hints reads.
+ *   ring_motion (slots, hint_rows + 4, ld) fp32 / ring_keep (same shape) uint8, ld >= 337: frame f of a session lives at row f mod hint_rows,
+ *             and rows hint_rows .. hint_rows + 3 MIRROR rows 0 .. 3 (a frame that lands in a row below 4 is written twice), so the 64 rows from
+ *             (60 i) mod hint_rows are window i, contiguous, for every i (hint_rows: a multiple of 60, >= 120).  Columns 337 .. ld - 1 of a
+ *             written row are 0 (motion) / 1 (keep).
+ *   staged    the tick's hint frames of every slot (staged_bytes bytes, 16-byte aligned); a slot's chunk starts at a 16-byte boundary and holds
+ *             COUNT rows of W floats, then COUNT rows of 337 mask bytes (1 = generate, 0 = given).  FORM EMAGE_STREAM_HINT_PACKED: W = 337, the
+ *             model's layout (55 x rot6d | trans | contact); EMAGE_STREAM_HINT_TRACKER: W = 172 = 165 axis-angle | 3 trans | 4 contact, each
+ *             joint converted with emage_axis_angle_to_rot6d's arithmetic, bit for bit.
+ *   seeds     (slots, 4, 337) fp32, the seed rows of emage_stream_commit: the first SEED_COUNT staged frames' motion also goes to rows SEED_ROW ..
+ *             of the slot's seed (frames 0 .. 3 of a session: window 0's seed, M:379).
+ *   hint_table  EMAGE_STREAM_HINT_WORDS int32 words per slot on the device:
+ *     COUNT       frames staged for the slot this tick (0: none)        SRC16      their first byte in `staged`, in units of 16 bytes
+ *     FORM        EMAGE_STREAM_HINT_PACKED / _TRACKER                   WRITE      ring row of the first staged frame
+ *     SEED_ROW    seed row the first staged frame goes to               SEED_COUNT leading staged frames that are seed frames (0: none)
+ *     READY       the slot runs a window this tick AND reads hints      WIN_FIRST  ring row of the window's frame 0
+ *     WIN_AVAIL   hint frames the window may read from WIN_FIRST on (the frames behind count as masked)
+ *   window_table[slot] = {slot (hint_rows + 4) + WIN_FIRST, WIN_AVAIL} for a READY slot — a row of the rings read as ONE store of
+ *             slots (hint_rows + 4) rows — and {0, 0} for every other slot: a window without hints.
+ * A row is skipped — nothing read, nothing written but window_table[slot] = {0, 0}; EMAGE_STREAM_BAD_HINTS — unless 0 <= COUNT <= hint_rows, the
+ * chunk lies inside `staged`, FORM is known, 0 <= WRITE < hint_rows, SEED_COUNT = 0 or (SEED_ROW = WRITE, SEED_ROW + SEED_COUNT <= 4, SEED_COUNT <=
+ * COUNT), and when READY 0 <= WIN_AVAIL <= window, 0 <= WIN_FIRST and WIN_FIRST + window <= hint_rows + 4. */
+#define EMAGE_STREAM_HINT_WORDS 12
+#define EMAGE_STREAM_HINT_COUNT 0
+#define EMAGE_STREAM_HINT_SRC16 1
+#define EMAGE_STREAM_HINT_FORM 2
+#define EMAGE_STREAM_HINT_WRITE 3
+#define EMAGE_STREAM_HINT_SEED_ROW 4
+#define EMAGE_STREAM_HINT_SEED_COUNT 5
+#define EMAGE_STREAM_HINT_READY 6
+#define EMAGE_STREAM_HINT_WIN_FIRST 7
+#define EMAGE_STREAM_HINT_WIN_AVAIL 8
+#define EMAGE_STREAM_HINT_PACKED 0
+#define EMAGE_STREAM_HINT_TRACKER 1
+#define EMAGE_STREAM_BAD_HINTS 32
+int emage_stream_push_hints(const void* staged, long staged_bytes, const int* hint_table, int slots, float* ring_motion, unsigned char* ring_keep,
+                            int hint_rows, int ld, float* seeds, long long* window_table, int window, int* status, void* stream);
+
 /* The metrics of one validation step (train_emage_audio.py:130-204, mode="val": get_rec_loss / get_cls_loss of the three eval forwards, the
  * arg-max codes) over the REAL clips of a padded batch, in two launches (csrc/val.hip).  `entries`: a HOST array of up to
  * EMAGE_VAL_MAX_ENTRIES rows, one per (forward, body part), validated here and carried to the device by value in the kernel arguments

@@ -137,6 +137,7 @@ SIGNATURES = {
     "emage_copy_segments": [_p, _l, _p, _l, _p, _i, _l, _l, _p, _p],
     "emage_stream_push": [_i, _p, _l, _p, _i, _p, _l, _p, _p],
     "emage_stream_push_resample": [_p, _l, _p, _i, _p, _i, _p, _l, _p, _l, _p, _i, _p, _p],
+    "emage_stream_push_hints": [_p, _l, _p, _i, _p, _p, _i, _i, _p, _p, _i, _p, _p],
     "emage_stream_windows": [_p, _l, _p, _i, _i, _p, _l, _p, _p],
     "emage_stream_commit": [_p, _i, _i, _p, _i, _i, _p, _i, _p, _i, _p, _l, _p, _i, _p, _p],
     "emage_stream_emit": [_p, _i, _i, _i, _p, _p, _p, _i, _i, _f, _p, _i, _p, _p, _p, _p, _p, _p, _p],

@@ -10,8 +10,12 @@
 // Volumes are tiny next to the forward (one window of audio and a few hundred codes per slot): plain element loops, no LDS but the scan's.
 // A fifth, emage_stream_push_resample, stands in for emage_stream_push in batches whose sessions push PCM at other rates and layouts: the
 // polyphase filter of audio.hip continued across pushes (csrc/pcm_taps.h is shared), driven by a second per-tick table of its own.
+// A sixth, emage_stream_push_hints, serves batches whose sessions push MOTION HINTS (keyframes, tracked body parts): it scatters the tick's
+// staged hint frames into per-slot hint rings laid out so that every window is 64 contiguous rows, and writes the table
+// emage_pack_motion_hints (elementwise.hip) reads them through; driven by a third per-tick table.
 #include "common.h"
 #include "pcm_taps.h"
+#include "rot_math.h"
 #include "vel_step.h"
 
 namespace {
@@ -143,6 +147,79 @@ __global__ __launch_bounds__(THREADS) void push_resample_kernel(const unsigned c
     else if (f.pcm == EMAGE_PCM_S24) resample_slot<EMAGE_PCM_S24>(r, f, src, taps, o, ring_len, hist, hist_len, s_resample);
     else if (f.pcm == EMAGE_PCM_S32) resample_slot<EMAGE_PCM_S32>(r, f, src, taps, o, ring_len, hist, hist_len, s_resample);
     else resample_slot<EMAGE_PCM_F32>(r, f, src, taps, o, ring_len, hist, hist_len, s_resample);
+}
+
+// ---- emage_stream_push_hints: the tick's motion hints into the hint rings, and the windows' table -------------------------------------------
+// grid (slots, HINT_SPANS).  Frame f of a session lives at ring row f mod hint_rows; rows hint_rows .. hint_rows + 3 mirror rows 0 .. 3, so a
+// frame that lands below row 4 is written twice and window i is the 64 contiguous rows from (60 i) mod hint_rows.  A slot's chunk of the
+// staged buffer is COUNT rows of W floats and then COUNT rows of HINT_C mask bytes.  Every block of a slot evaluates the same checks; block 0
+// writes the slot's row of the window table.  Volumes: at most hint_rows x 344 x 5 bytes per slot — latency, not bandwidth.
+constexpr int HINT_SPANS = 8;
+constexpr int HINT_C = 337, HINT_JOINTS = 55, HINT_PRE = 4, HINT_TRACKER_W = 172;     // 55 x rot6d | 3 | 4;  55 x axis-angle | 3 | 4
+
+struct HintPush {
+    int count, src16, form, write, seed_row, seed_count, ready, win_first, win_avail;
+    __device__ explicit HintPush(const int* t)
+        : count(t[EMAGE_STREAM_HINT_COUNT]), src16(t[EMAGE_STREAM_HINT_SRC16]), form(t[EMAGE_STREAM_HINT_FORM]), write(t[EMAGE_STREAM_HINT_WRITE]),
+          seed_row(t[EMAGE_STREAM_HINT_SEED_ROW]), seed_count(t[EMAGE_STREAM_HINT_SEED_COUNT]), ready(t[EMAGE_STREAM_HINT_READY]),
+          win_first(t[EMAGE_STREAM_HINT_WIN_FIRST]), win_avail(t[EMAGE_STREAM_HINT_WIN_AVAIL]) {}
+};
+
+__global__ __launch_bounds__(THREADS) void push_hints_kernel(const unsigned char* __restrict__ staged, long staged_bytes, const int* __restrict__ hint_table,
+                                                             float* __restrict__ ring_motion, unsigned char* __restrict__ ring_keep, int hint_rows, int ld,
+                                                             float* __restrict__ seeds, long long* __restrict__ window_table, int window,
+                                                             int* __restrict__ status) {
+    const int s = blockIdx.x, tid = threadIdx.x;
+    const HintPush r(hint_table + (long)s * EMAGE_STREAM_HINT_WORDS);
+    const bool tracker = r.form == EMAGE_STREAM_HINT_TRACKER;
+    const int w = tracker ? HINT_TRACKER_W : HINT_C;
+    bool ok = r.count >= 0 && r.count <= hint_rows && r.src16 >= 0 && (r.form == EMAGE_STREAM_HINT_PACKED || tracker) && r.write >= 0 &&
+              r.write < hint_rows && (long)r.src16 * 16 + (long)r.count * (w * 4 + HINT_C) <= staged_bytes;
+    if (ok && r.seed_count != 0)
+        ok = r.seed_count > 0 && r.seed_row == r.write && r.seed_row + r.seed_count <= HINT_PRE && r.seed_count <= r.count;
+    if (ok && r.ready) ok = r.win_avail >= 0 && r.win_avail <= window && r.win_first >= 0 && r.win_first + window <= hint_rows + HINT_PRE;
+    const long rows = hint_rows + HINT_PRE;                // the slot's rows of the two planes
+    if (blockIdx.y == 0 && tid == 0) {
+        const bool hinted = ok && r.ready;
+        window_table[2 * (long)s] = hinted ? (long long)s * rows + r.win_first : 0;
+        window_table[2 * (long)s + 1] = hinted ? r.win_avail : 0;
+        if (!ok) atomicOr(status, EMAGE_STREAM_BAD_HINTS);
+    }
+    if (!ok || r.count == 0) return;
+    const float* src = (const float*)(staged + (long)r.src16 * 16);
+    const unsigned char* mask = (const unsigned char*)(src + (long)r.count * w);
+    float* om = ring_motion + (long)s * rows * ld;
+    unsigned char* okeep = ring_keep + (long)s * rows * ld;
+    float* seed = seeds + ((long)s * HINT_PRE + r.seed_row) * HINT_C;
+    const int first = blockIdx.y * THREADS + tid, stride = HINT_SPANS * THREADS;
+    // the keep plane, the padding columns, and the motion columns that are copied (all of them in the packed form, 330 .. 336 in the tracker's)
+    for (int i = first; i < r.count * ld; i += stride) {
+        const int j = i / ld, c = i - j * ld;
+        int p = r.write + j;
+        if (p >= hint_rows) p -= hint_rows;
+        const unsigned char k = c < HINT_C ? mask[(long)j * HINT_C + c] : (unsigned char)1;
+        okeep[(long)p * ld + c] = k;
+        if (p < HINT_PRE) okeep[(long)(hint_rows + p) * ld + c] = k;
+        if (tracker && c < 6 * HINT_JOINTS) continue;
+        const float v = c >= HINT_C ? 0.f : tracker ? src[(long)j * HINT_TRACKER_W + c - 6 * HINT_JOINTS + 3 * HINT_JOINTS] : src[(long)j * HINT_C + c];
+        om[(long)p * ld + c] = v;
+        if (p < HINT_PRE) om[(long)(hint_rows + p) * ld + c] = v;
+        if (j < r.seed_count && c < HINT_C) seed[(long)j * HINT_C + c] = v;
+    }
+    if (!tracker) return;
+    for (int i = first; i < r.count * HINT_JOINTS; i += stride) {                 // one joint per thread: emage_axis_angle_to_rot6d's bits
+        const int j = i / HINT_JOINTS, q = i - j * HINT_JOINTS;
+        int p = r.write + j;
+        if (p >= hint_rows) p -= hint_rows;
+        float aa[3], d6[6];
+        for (int c = 0; c < 3; ++c) aa[c] = src[(long)j * HINT_TRACKER_W + q * 3 + c];
+        emage_rot::aa_to_rot6d(aa, d6);
+        for (int c = 0; c < 6; ++c) {
+            om[(long)p * ld + q * 6 + c] = d6[c];
+            if (p < HINT_PRE) om[(long)(hint_rows + p) * ld + q * 6 + c] = d6[c];
+            if (j < r.seed_count) seed[(long)j * HINT_C + q * 6 + c] = d6[c];
+        }
+    }
 }
 
 __global__ __launch_bounds__(THREADS) void windows_kernel(const float* __restrict__ ring, long ring_len, const int* __restrict__ table, int samples,
@@ -293,6 +370,19 @@ extern "C" int emage_stream_push_resample(const void* staged, long staged_bytes,
     if (configured != hipSuccess) return (int)configured;
     hipLaunchKernelGGL(push_resample_kernel, dim3((unsigned)slots, SPANS), dim3(THREADS), (size_t)lds_floats * sizeof(float), (hipStream_t)stream,
                        (const unsigned char*)staged, staged_bytes, rs_table, fmts, taps, ring, ring_len, history, hist_len, status);
+    return launch_status();
+}
+
+extern "C" int emage_stream_push_hints(const void* staged, long staged_bytes, const int* hint_table, int slots, float* ring_motion, unsigned char* ring_keep,
+                                       int hint_rows, int ld, float* seeds, long long* window_table, int window, int* status, void* stream) {
+    if (!staged || !hint_table || !ring_motion || !ring_keep || !seeds || !window_table || !status) return EMAGE_EINVAL;
+    if (slots <= 0 || slots > 65535 || staged_bytes <= 0 || hint_rows < 120 || hint_rows % 60 || hint_rows > (1 << 16) || ld < HINT_C || ld > 4096 || window <= 0 ||
+        window > hint_rows)
+        return EMAGE_EINVAL;
+    if (((uintptr_t)staged & 15) || (((uintptr_t)hint_table | (uintptr_t)ring_motion | (uintptr_t)seeds | (uintptr_t)status) & 3) || ((uintptr_t)window_table & 7))
+        return EMAGE_EINVAL;
+    hipLaunchKernelGGL(push_hints_kernel, dim3((unsigned)slots, HINT_SPANS), dim3(THREADS), 0, (hipStream_t)stream, (const unsigned char*)staged,
+                       staged_bytes, hint_table, ring_motion, ring_keep, hint_rows, ld, seeds, window_table, window, status);
     return launch_status();
 }
 

@@ -1697,7 +1697,7 @@ def copy_segments(src, dst, segments, width_bytes, max_rows, status):
 # ---- the streaming batch (include/emage_hip.h: emage_stream_push ...) -----------------------------------------------------------------
 STREAM_WORDS = 12                                     # EMAGE_STREAM_WORDS and the word indices below: the per-tick table, int32 words per slot
 STREAM_FIELDS = ("ready", "audio_read", "audio_write", "push_count", "push_src", "code_write", "seg_read", "seg_valid", "emit_row", "emit_count")
-STREAM_STATUS_TEXT = "1: a push outside the staged buffer / ring; 2: a window outside its ring; 4: a commit row outside the code rings; 8: an emit range outside the segment; 16: a resample row outside the staged buffer / ring / history / declared formats"
+STREAM_STATUS_TEXT = "1: a push outside the staged buffer / ring; 2: a window outside its ring; 4: a commit row outside the code rings; 8: an emit range outside the segment; 16: a resample row outside the staged buffer / ring / history / declared formats; 32: a hint row outside the staged buffer / hint ring (in a batch with motion hints 4 is also: a window table row outside the hint rings)"
 
 
 def stream_table(rows, *, ring_len, staged_samples, samples, ring_codes, seg_len, out_rows):
@@ -1884,6 +1884,101 @@ def stream_push_resample(staged, rs_table, formats, taps, ring, history, status)
         assert t.device == ring.device, "stream_push_resample: every tensor on one device"
     _stream_push_resample(staged, rs_table, words, taps, ring, history, status)
     return ring
+
+
+# the third per-tick table, of `stream_push_hints` alone (EMAGE_STREAM_HINT_*): motion hints of live sessions
+STREAM_HINT_WORDS = 12
+STREAM_HINT_FIELDS = ("count", "src16", "form", "write", "seed_row", "seed_count", "ready", "win_first", "win_avail")
+STREAM_HINT_PACKED, STREAM_HINT_TRACKER = 0, 1
+STREAM_HINT_WIDTHS = (337, 172)                       # floats per staged frame: rot6d | trans | contact;  axis-angle | trans | contact
+STREAM_HINT_C = 337                                   # mask bytes per staged frame
+STREAM_BAD_HINTS = 32
+
+
+def stream_hint_chunk_bytes(frames, form):
+    """Bytes of a slot's chunk of `frames` staged hint frames (the motion rows, then the mask rows), rounded up to the next 16-byte boundary."""
+    return -(-int(frames) * (STREAM_HINT_WIDTHS[form] * 4 + STREAM_HINT_C) // 16) * 16
+
+
+def stream_hint_table(rows, *, hint_rows, staged_bytes, window=64, hop=60):
+    """The per-tick table of `stream_push_hints`, checked on the host.  `rows`: one dict per slot (None: nothing to do, a window without
+    hints) holding the session's ABSOLUTE counts, from which the int32 words are formed here:
+      frames (hint frames staged this tick), src (byte offset of the slot's chunk in the staged buffer, a multiple of 16), form
+      (STREAM_HINT_PACKED / STREAM_HINT_TRACKER), frames_before (hint frames of the session uploaded by earlier launches), ready (the slot
+      runs a window this tick and is a hinted session), window_index (which window: i).
+    Frame f lives at ring row f % hint_rows; window i is the `window` rows from (hop i) % hint_rows and may read
+    clamp(frames_before + frames - hop i, 0, window) of them.  Every chunk must lie inside the staged buffer without overlapping another
+    slot's, a push must not exceed the ring, and a ready slot must not hold more than hop i + hint_rows frames — the window's rows would have
+    been overwritten -> (slots, STREAM_HINT_WORDS) int32 numpy array."""
+    import numpy as np
+    fields = ("frames", "src", "form", "frames_before", "ready", "window_index")
+    if hint_rows < 2 * hop or hint_rows % hop or not 0 < window <= hop + 4:
+        raise ValueError(f"stream_hint_table: a ring of {hint_rows} rows: a multiple of the hop {hop}, at least two hops, windows of at most {hop + 4} rows")
+    tab = np.zeros((len(rows), STREAM_HINT_WORDS), dtype=np.int32)
+    spans = []
+    for k, row in enumerate(rows):
+        if row is None:
+            continue
+        unknown = set(row) - set(fields)
+        if unknown:
+            raise ValueError(f"stream_hint_table: slot {k}: unknown fields {sorted(unknown)}")
+        r = {f: int(row.get(f, 0)) for f in fields}
+        if r["form"] not in (STREAM_HINT_PACKED, STREAM_HINT_TRACKER):
+            raise ValueError(f"stream_hint_table: slot {k}: form {r['form']} is neither packed (0) nor tracker (1)")
+        nbytes = r["frames"] * (STREAM_HINT_WIDTHS[r["form"]] * 4 + STREAM_HINT_C)
+        if not 0 <= r["frames"] <= hint_rows or r["frames_before"] < 0:
+            raise ValueError(f"stream_hint_table: slot {k}: a push of {r['frames']} frames behind {r['frames_before']} into a ring of {hint_rows} rows")
+        if r["frames"] and (r["src"] < 0 or r["src"] % 16 or r["src"] + nbytes > staged_bytes):
+            raise ValueError(f"stream_hint_table: slot {k}: {r['frames']} frames ({nbytes} bytes) at byte {r['src']} do not fit the staged buffer of "
+                             f"{staged_bytes} bytes from a 16-byte boundary")
+        held = r["frames_before"] + r["frames"]
+        words = [r["frames"], r["src"] // 16 if r["frames"] else 0, r["form"], r["frames_before"] % hint_rows, 0, 0, 0, 0, 0]
+        if r["frames"] and r["frames_before"] < 4:
+            words[4], words[5] = r["frames_before"], min(4 - r["frames_before"], r["frames"])
+        if r["ready"]:
+            i = r["window_index"]
+            if i < 0 or held > hop * i + hint_rows:
+                raise ValueError(f"stream_hint_table: slot {k}: window {i} of a slot that holds {held} hint frames: rows of the window have been "
+                                 f"overwritten in a ring of {hint_rows} rows")
+            words[6:9] = [1, (hop * i) % hint_rows, min(max(held - hop * i, 0), window)]
+        tab[k, :len(words)] = words
+        if r["frames"]:
+            spans.append((r["src"], r["src"] + nbytes))
+    spans.sort()
+    if any(lo < prev_hi for (_l, prev_hi), (lo, _h) in zip(spans, spans[1:])):
+        raise ValueError("stream_hint_table: two slots' chunks overlap in the staged buffer")
+    return tab
+
+
+@_op("stream_push_hints", "(Tensor staged, Tensor hint_table, Tensor(a!) ring_motion, Tensor(b!) ring_keep, Tensor(c!) seeds, Tensor(d!) window_table, "
+                          "int window, Tensor(e!) status) -> ()")
+def _stream_push_hints(staged, hint_table, ring_motion, ring_keep, seeds, window_table, window, status):
+    slots, rows, ld = ring_motion.shape
+    check(_lib.load().emage_stream_push_hints(_ptr(staged), staged.numel(), _ptr(hint_table), slots, _ptr(ring_motion), _ptr(ring_keep), rows - 4, ld,
+                                              _ptr(seeds), _ptr(window_table), window, _ptr(status), _stream()), "stream_push_hints")
+
+
+def stream_push_hints(staged, hint_table, ring_motion, ring_keep, seeds, window_table, window, status):
+    """One launch moves the tick's staged motion hints (`staged`: 1-D uint8, every slot's chunk from a 16-byte boundary: its frames' motion
+    rows — packed (337 floats) or tracker form (165 axis-angle | 3 | 4, converted with `axis_angle_to_rot6d`'s arithmetic) — then their mask
+    rows) into the hint rings `ring_motion` (slots, hint_rows + 4, ld) float32 / `ring_keep` uint8 — frame f at row f % hint_rows, rows
+    hint_rows .. hint_rows + 3 mirroring rows 0 .. 3 — copies a session's frames 0 .. 3 into its rows of `seeds` (slots, 4, 337), and writes
+    `window_table` (slots, 2) int64: what `pack_motion_hints` reads the rings through, as ONE store of slots * (hint_rows + 4) rows.
+    hint_table: `stream_hint_table`.  See include/emage_hip.h: emage_stream_push_hints."""
+    _dev(ring_motion)
+    assert staged.dtype == torch.uint8 and staged.dim() == 1 and staged.is_contiguous() and staged.numel() > 0
+    assert ring_motion.dtype == torch.float32 and ring_keep.dtype == torch.uint8 and ring_motion.dim() == 3 and ring_motion.shape == ring_keep.shape
+    assert ring_motion.is_contiguous() and ring_keep.is_contiguous()
+    slots, rows, ld = ring_motion.shape
+    assert rows >= 124 and (rows - 4) % 60 == 0 and STREAM_HINT_C <= ld <= 4096 and 0 < int(window) <= rows - 4
+    assert seeds.dtype == torch.float32 and tuple(seeds.shape) == (slots, 4, STREAM_HINT_C) and seeds.is_contiguous()
+    assert hint_table.dtype == torch.int32 and tuple(hint_table.shape) == (slots, STREAM_HINT_WORDS) and hint_table.is_contiguous()
+    assert window_table.dtype == torch.int64 and tuple(window_table.shape) == (slots, 2) and window_table.is_contiguous()
+    assert status.dtype == torch.int32 and status.numel() == 1
+    for t in (staged, hint_table, ring_keep, seeds, window_table, status):
+        assert t.device == ring_motion.device, "stream_push_hints: every tensor on one device"
+    _stream_push_hints(staged, hint_table, ring_motion, ring_keep, seeds, window_table, int(window), status)
+    return window_table
 
 
 @_op("stream_windows", "(Tensor ring, Tensor table, Tensor(a!) out, Tensor(b!) status) -> ()")

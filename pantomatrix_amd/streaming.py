@@ -26,8 +26,22 @@ channels, 16 / 24 / 32-bit integer or float32 — and resamples it inside the ti
    them wait for more input or for `end()`, which computes them against zeros: the offline right edge.  The ring then holds, bit for
    bit, the offline kernel's samples, and rules 1-3 apply to them unchanged.
 
+A batch built with ``motion_hints=True`` takes MOTION HINTS from its sessions while they run (`open(motion=True)`, `push_motion`,
+`end_motion`) — keyframes, a body part tracked by a headset and controllers, a pose to hold: the `masked_motion` / `mask` of the reference's
+`inference()` (M:343-359), as `recordings.RecordingRunner(hints=True)` honours them offline — with a fifth rule:
+
+5. WHICH hint frames a window needs.  A hinted session's concatenated output equals, code for code, the offline hinted pass
+   (`RecordingSet(masked_motion=[m], mask=[k])` through `RecordingRunner(hints=True)`: the reference's B = 1 call), m / k being the
+   prefix of motion and mask rows the session pushed before it ended its hints.  Window i packs frames [60 i, 60 i + 64) (M:380-391): a
+   hint frame f is read by window (f - 4) // 60 as one of its frames 4 .. 63, and, when f % 60 < 4 and f >= 60, by window f // 60 too, as a
+   seed frame — there mask == 0 makes the hint win over the decoded seed (M:386-390).  So window i of a session whose hints are open runs
+   only once rule 1 holds AND the session holds hint frames up to 60 i + 64 or has ended its hints (`end_motion()`): only then does the
+   window read what the offline pass reads, whatever is pushed later.  Frames behind the end of the hints count as template and masked (the
+   reference's prefix semantics, M:352-359); window 0's seed is the first four rows of the hinted motion over the identity template
+   (M:379), whatever their mask says.  Until then `Session.ready` is False and `Session.waiting` says "motion".
+
 * ``StreamBatch``  the slots, their device state and the tick;
-* ``Session``      one live stream: `push(pcm)`, `end()`, `close()`;
+* ``Session``      one live stream: `push(pcm)`, `end()`, `push_motion(...)`, `end_motion()`, `close()`;
 * ``Emitted``      what a session receives: poses (n, 165), expressions (n, 100), trans (n, 3), codes {part: (n,) int64}."""
 from __future__ import annotations
 
@@ -39,6 +53,7 @@ import torch
 from . import audio, ops, synthetic
 from ._lib import nonfinite_error
 from .audio import available                            # rule 4: the outputs that are final after n input frames
+from .recordings import HINT_LD, _hint_template
 from .windows import MODEL_SR, SEED_DIMS, SPF, frames_of, identity_seed, split_length
 
 STATUS_TEXT = ops.STREAM_STATUS_TEXT
@@ -79,16 +94,33 @@ class Session:
     """One live stream in one slot of a `StreamBatch`.  pushed: 16 kHz samples the slot holds; windows: full windows run; emitted: frames
     handed out; frames_in: raw frames accepted (= pushed, unless the batch resamples: then pushed counts the FINAL outputs, rule 4)."""
 
-    def __init__(self, batch, slot, speaker_id, fmt=None):
+    def __init__(self, batch, slot, speaker_id, fmt=None, motion=False):
         self.batch, self.slot, self.speaker_id = batch, slot, speaker_id
         self.pushed = self.windows = self.emitted = self.frames_in = 0
         self.closed = self.ended = False
         self.fmt = fmt                                      # row of the batch's declared audio inputs (None: the 16 kHz path)
         self._staged = []                                   # host chunks not on the device yet
         self._sent = self._written = 0                      # resampling batch: frames uploaded / outputs written to the ring so far
+        # motion hints (rule 5).  hint_frames: hint frames pushed; hint_frames_unused: after close(), those beyond the frames produced
+        self.motion, self.hints_ended = bool(motion), not motion
+        self.hint_frames = self.hint_frames_unused = 0
+        self._hint_staged, self._hint_sent = [], 0          # (form, motion rows or None, mask rows) not on the device yet / frames uploaded
 
     def push(self, pcm):
         self.batch._push(self, pcm)
+
+    def push_motion(self, motion=None, mask=None, *, poses=None, trans=None, contact=None):
+        """Append n consecutive hint frames behind those already pushed (a session opened with motion=True).  Packed form: motion (n, 337)
+        float32 in the model's layout (55 x rot6d | trans | contact).  Tracker form: poses (n, 165) axis-angle with trans (n, 3) and contact
+        (n, 4), missing ones zero — converted on the device, the bits of `ops.axis_angle_to_rot6d`.  mask (n, 337) of exactly 0 / 1, 1 =
+        generate, 0 = given (`RecordingSet`'s rule; anything else raises ValueError); None: all ones.  A mask with neither motion nor poses
+        hints the identity template.  Hints wait on the host for the next tick; the two forms do not mix among the frames of one tick.  A
+        push that would make the slot hold more than 60 * windows + hint_rows hint frames raises."""
+        self.batch._push_motion(self, motion, mask, poses, trans, contact)
+
+    def end_motion(self):
+        """No more hints: the frames behind those pushed are generated freely (rule 5).  Idempotent; `close()` calls it."""
+        self.batch._end_motion(self)
 
     def end(self):
         """No more input.  In a resampling batch the outputs held back for lack of later frames (rule 4) are released — computed against
@@ -99,8 +131,20 @@ class Session:
         return self.batch._close(self)
 
     @property
+    def waiting(self):
+        """What the session's next full window waits for: "audio" (rule 1), "motion" (rule 5: the audio is there, hint frames up to
+        60 windows + 64 are not and the hints have not ended), or None (it runs at the next tick; a closed session waits for nothing)."""
+        if self.closed:
+            return None
+        if self.pushed < window_need(self.windows, self.batch.window, self.batch.hop):
+            return "audio"
+        if not self.hints_ended and self.hint_frames < self.batch.hop * self.windows + self.batch.window:
+            return "motion"
+        return None
+
+    @property
     def ready(self):
-        return not self.closed and self.pushed >= window_need(self.windows, self.batch.window, self.batch.hop)
+        return not self.closed and self.waiting is None
 
 
 class StreamBatch:
@@ -121,9 +165,20 @@ class StreamBatch:
     uploaded once.  The tick's first launch is then `ops.stream_push_resample`: each slot's raw PCM is decoded, down-mixed and resampled to
     16 kHz on the device, filter state carried per slot, so that the ring holds bit for bit what `ops.audio_resample` gives for the
     session's whole PCM (rule 4); `open(audio_input=...)` picks a session's format, `push` takes (n, channels) frames of it (packed 24-bit:
-    (n, 3 * channels) uint8).  `audio_format` is not used then; max_push and max_seconds stay in 16 kHz samples."""
+    (n, 3 * channels) uint8).  `audio_format` is not used then; max_push and max_seconds stay in 16 kHz samples.
 
-    def __init__(self, model, vq_model, slots=8, audio_format="f32", max_seconds=3600, use_graph=True, max_push=3 * MODEL_SR, audio_inputs=None):
+    motion_hints: False — nothing is allocated for hints and the tick is the launch sequence of a batch without the argument.  True — every
+    slot owns a hint ring, `hint_ring_motion` (slots, hint_rows + 4, 344) float32 / `hint_ring_keep` uint8 with
+    hint_rows = 60 * ceil((64 + max_hint_push) / 60): hint frame f of a session lives at row f % hint_rows and rows hint_rows .. + 3 mirror
+    rows 0 .. 3, so window i is the 64 contiguous rows from (60 i) % hint_rows.  The tick has one more launch, `ops.stream_push_hints`,
+    which scatters the hint frames staged since the last tick into the rings (tracker-form frames converted on the way), copies a session's
+    frames 0 .. 3 into its seed rows and writes the (slots, 2) table through which the forward's packing launch
+    (`ops.pack_motion_hints`, as in `RecordingRunner(hints=True)`) reads every slot's window — {0, 0}, a window without hints, for slots
+    that are not ready and for sessions opened without `motion=True`, whose bits are those of a batch without hints.  max_hint_push: the most
+    hint frames a session may hold beyond the 64 its next window needs; the pinned staging buffer is sized for it at construction."""
+
+    def __init__(self, model, vq_model, slots=8, audio_format="f32", max_seconds=3600, use_graph=True, max_push=3 * MODEL_SR, audio_inputs=None,
+                 motion_hints=False, max_hint_push=90):
         dev = model.device
         model._require_device(dev)                          # an MI355X: there is no CPU path (the host tests lift this check over stand-in ops)
         on_gpu = dev.type == "cuda"
@@ -178,6 +233,23 @@ class StreamBatch:
         self.tmpl_motion = identity_seed(s, self.window).to(dev)           # identity pose + all-ones mask (M:347-358), read-only
         self.tmpl_mask = torch.ones_like(self.tmpl_motion)
         self._ident = identity_seed(1)[0]
+        self.motion_hints = bool(motion_hints)
+        if self.motion_hints:
+            if int(max_hint_push) <= 0:
+                raise ValueError("StreamBatch: max_hint_push must be positive")
+            self.hint_rows = self.hop * -(-(self.window + int(max_hint_push)) // self.hop)
+            rows = self.hint_rows + self.pre
+            self.hint_ring_motion = _hint_template(s * rows).view(s, rows, HINT_LD).to(dev)      # the template's contents: a row nobody pushed is no hint
+            self.hint_ring_keep = torch.ones(s, rows, HINT_LD, dtype=torch.uint8, device=dev)
+            self._hint_store = (self.hint_ring_motion.view(s * rows, HINT_LD)[:, :SEED_DIMS], self.hint_ring_keep.view(s * rows, HINT_LD)[:, :SEED_DIMS])
+            self.window_table = torch.zeros(s, 2, dtype=torch.int64, device=dev)
+            self.hint_table = torch.zeros(s, ops.STREAM_HINT_WORDS, dtype=torch.int32, device=dev)
+            self.hint_table_host = torch.zeros(s, ops.STREAM_HINT_WORDS, dtype=torch.int32, pin_memory=on_gpu)
+            # the most a slot can have staged: a full ring of frames in the wider (packed) form
+            hint_bytes = s * ops.stream_hint_chunk_bytes(self.hint_rows, ops.STREAM_HINT_PACKED)
+            self.hint_staged = torch.zeros(hint_bytes, dtype=torch.uint8, device=dev)
+            self.hint_staged_host = torch.zeros(hint_bytes, dtype=torch.uint8, pin_memory=on_gpu)
+            self.hint_bytes_staged = 0                      # bytes the last tick uploaded (tools/bench_stream.py)
         # the output rows and the two flags [non-finite values, status word] in ONE buffer: one device-to-host copy per tick
         self.out, self.out_views = self._output_buffer(s, self.hop, dev, False)
         self.out_host, self.host_views = self._output_buffer(s, self.hop, torch.device("cpu"), on_gpu)
@@ -222,10 +294,17 @@ class StreamBatch:
         return (self.model._version_stamp(),) + tuple(m._version_stamp() for m in self.vq._models())
 
     # ---- sessions -----------------------------------------------------------------------------------------------------------------------
-    def open(self, speaker_id=0, seed=None, ref_trans=None, audio_input=None):
+    def open(self, speaker_id=0, seed=None, ref_trans=None, audio_input=None, motion=False):
         """A new session in the lowest free slot (raises when there is none).  seed (4, 337) / ref_trans (3,): as `RecordingSet` seeds a
         recording; None: identity pose, zero translation (test_emage_audio.py).  audio_input: in a batch built with `audio_inputs`, the one
-        of them this session pushes (None: the first).  The session starts with an empty filter history, whatever the slot held before."""
+        of them this session pushes (None: the first).  The session starts with an empty filter history, whatever the slot held before.
+        motion=True (a batch built with motion_hints=True): a hinted session — it pushes motion hints (`push_motion`) and its windows wait
+        for them (rule 5) until `end_motion()`.  Its seed is the first four frames of its hints over the identity (M:379), so `seed` and
+        motion=True exclude each other, as `seeds` and `masked_motion` do in `RecordingSet`."""
+        if motion and seed is not None:
+            raise ValueError("StreamBatch.open: pass `seed` or motion=True, not both (the seed is the first four frames of the hints, M:379)")
+        if motion and not self.motion_hints:
+            raise ValueError("StreamBatch.open: motion=True needs a batch built with motion_hints=True")
         free = [k for k, s in enumerate(self.sessions) if s is None]
         if not free:
             raise RuntimeError(f"StreamBatch: all {self.slots} slots are in use")
@@ -249,7 +328,7 @@ class StreamBatch:
         self.seeds[k].copy_(seed)                           # stream-ordered copies into fixed addresses: the next replay reads them
         self.carry[k].copy_(ref_trans)
         self.speaker_id[k].fill_(int(speaker_id))
-        self.sessions[k] = s = Session(self, k, int(speaker_id), fmt)
+        self.sessions[k] = s = Session(self, k, int(speaker_id), fmt, motion)
         return s
 
     def _fits(self, s, pushed, n):
@@ -307,6 +386,100 @@ class StreamBatch:
             s.pushed += n
             s.frames_in += n
 
+    # ---- motion hints (rule 5) ----------------------------------------------------------------------------------------------------------------
+    def _push_motion(self, s, motion, mask, poses, trans, contact):
+        if s.closed:
+            raise RuntimeError("Session.push_motion: the session is closed")
+        if not s.motion:
+            raise RuntimeError("Session.push_motion: the session was opened without motion=True")
+        if s.hints_ended:
+            raise RuntimeError("Session.push_motion: the session's hints have ended")
+        if motion is not None and poses is not None:
+            raise ValueError("Session.push_motion: pass `motion` (packed, (n, 337)) or `poses` (tracker, (n, 165)), not both")
+        if poses is None and (trans is not None or contact is not None):
+            raise ValueError("Session.push_motion: `trans` / `contact` belong to the tracker form: pass `poses` with them")
+
+        def rows_of(name, a, width):
+            if a is None:
+                return None
+            a = np.asarray(a.detach().cpu().numpy() if torch.is_tensor(a) else a)
+            if a.ndim != 2 or a.shape[1] != width:
+                raise ValueError(f"Session.push_motion: {name} must be (n, {width}), got {a.shape}")
+            return a
+        given = [(nm, rows_of(nm, a, w)) for nm, a, w in (("motion", motion, SEED_DIMS), ("mask", mask, SEED_DIMS), ("poses", poses, 165),
+                                                           ("trans", trans, 3), ("contact", contact, 4)) if a is not None]
+        if not given:
+            raise ValueError("Session.push_motion: nothing to push: pass motion, poses or mask")
+        n = int(given[0][1].shape[0])
+        if any(a.shape[0] != n for _nm, a in given):
+            raise ValueError(f"Session.push_motion: the arrays disagree on the number of frames: {[(nm, a.shape[0]) for nm, a in given]}")
+        given = dict(given)
+        if "mask" in given and not ((given["mask"] == 0) | (given["mask"] == 1)).all():       # RecordingSet's rule (np.isin costs ten times this)
+            raise ValueError("Session.push_motion: mask must hold exactly 0 (given) and 1 (generate)")
+        if s.hint_frames + n > self.hop * s.windows + self.hint_rows:
+            raise ValueError(f"Session.push_motion: {n} frames do not fit: the slot would hold {s.hint_frames + n - self.hop * s.windows} hint frames "
+                             f"behind its next window, its ring {self.hint_rows} (call step(), or build the batch with a larger max_hint_push)")
+        form, data = None, None
+        if "motion" in given:
+            form, data = ops.STREAM_HINT_PACKED, np.array(given["motion"], dtype=np.float32)      # a copy: the frames wait here until the next tick
+        elif "poses" in given:
+            form, data = ops.STREAM_HINT_TRACKER, np.zeros((n, ops.STREAM_HINT_WIDTHS[ops.STREAM_HINT_TRACKER]), dtype=np.float32)
+            data[:, :165] = given["poses"]
+            if "trans" in given:
+                data[:, 165:168] = given["trans"]
+            if "contact" in given:
+                data[:, 168:172] = given["contact"]
+        if form is not None and any(f is not None and f != form for f, _d, _k in s._hint_staged):
+            raise ValueError("Session.push_motion: packed and tracker frames do not mix among the frames of one tick; call step() between them")
+        if n:
+            keep = np.ones((n, SEED_DIMS), np.uint8) if "mask" not in given else given["mask"].astype(np.uint8)
+            s._hint_staged.append((form, data, keep))
+            s.hint_frames += n
+
+    def _end_motion(self, s):
+        if s.closed:
+            raise RuntimeError("Session.end_motion: the session is closed")
+        s.hints_ended = True
+
+    def _hint_rows(self, ready):
+        """One row of the hint table per slot (`ops.stream_hint_table`): the staged hint frames of every hinted session go to the pinned
+        staging buffer — a mask-only push as the identity template, in the form of the frames beside it — and the sessions of `ready` that
+        are hinted name their window -> (rows, staged bytes)."""
+        rows, lo = [None] * self.slots, 0
+        host = self.hint_staged_host.numpy()
+        for k, s in enumerate(self.sessions):
+            if s is None or not s.motion:
+                continue
+            row = {}
+            if s._hint_staged:
+                form = next((f for f, _d, _k in s._hint_staged if f is not None), ops.STREAM_HINT_PACKED)
+                w = ops.STREAM_HINT_WIDTHS[form]
+                n = sum(len(keep) for _f, _d, keep in s._hint_staged)
+                dst = host[lo:lo + n * w * 4].view(np.float32).reshape(n, w)
+                keeps = host[lo + n * w * 4:lo + n * (w * 4 + SEED_DIMS)].reshape(n, SEED_DIMS)
+                at = 0
+                for _f, data, keep in s._hint_staged:
+                    m = len(keep)
+                    if data is not None:
+                        dst[at:at + m] = data
+                    elif form == ops.STREAM_HINT_PACKED:
+                        dst[at:at + m] = self._ident[0].numpy()
+                    else:
+                        dst[at:at + m] = 0.0                                   # the zero rotation: aa_to_rot6d gives the identity's bits
+                    keeps[at:at + m] = keep
+                    at += m
+                row.update(frames=n, src=lo, form=form, frames_before=s._hint_sent)
+                lo += ops.stream_hint_chunk_bytes(n, form)
+                s._hint_staged, s._hint_sent = [], s._hint_sent + n
+            if s in ready:
+                row.update(ready=1, window_index=s.windows, frames_before=s._hint_sent - row.get("frames", 0))
+            rows[k] = row or None
+        return rows, lo
+
+    def _launch_push_hints(self):
+        ops.stream_push_hints(self.hint_staged, self.hint_table, self.hint_ring_motion, self.hint_ring_keep, self.seeds, self.window_table,
+                              self.window, self.status)
+
     # ---- the tick ---------------------------------------------------------------------------------------------------------------------------
     def _rows(self, ready):
         """One table row per slot: the staged PCM of every open session, and for the sessions of `ready` the window they run (rule 2)."""
@@ -354,7 +527,15 @@ class StreamBatch:
         s._sent, s._written = s._sent + frames, upto
         return lo + -(-nbytes // 16) * 16, row
 
-    def _upload(self, rows, staged=0):
+    def _upload(self, rows, staged=0, hint_rows=None, hint_staged=0):
+        if self.motion_hints:                              # the third table and the staged hint frames (rule 5)
+            tab = ops.stream_hint_table(hint_rows or [None] * self.slots, hint_rows=self.hint_rows, staged_bytes=self.hint_staged.numel(),
+                                        window=self.window, hop=self.hop)
+            self.hint_table_host.copy_(torch.from_numpy(tab))
+            if hint_staged:
+                self.hint_staged[:hint_staged].copy_(self.hint_staged_host[:hint_staged], non_blocking=True)
+            self.hint_table.copy_(self.hint_table_host, non_blocking=True)
+            self.hint_bytes_staged = int(hint_staged)
         if self.audio_inputs is not None:                  # a resampling batch: the pushes travel in the second table, under the key "resample"
             rs_rows = [r.get("resample") if r else None for r in rows]
             rows = [{f: v for f, v in r.items() if f != "resample"} if r else None for r in rows]
@@ -381,10 +562,14 @@ class StreamBatch:
         """The launches of one tick: no host state, so it is capturable."""
         model, vq = self.model, self.vq
         self._launch_push()
+        hints = None
+        if self.motion_hints:                              # the rings, frames 0 .. 3 into the seed rows, and every slot's row of the window table
+            self._launch_push_hints()
+            hints = (*self._hint_store, self.window_table, self.status)
         ops.stream_windows(self.ring, self.table, self.win_audio, self.status)
         with model.collect_health():
             seed = model._window_step(vq, self.win_audio, self.speaker_id, self.tmpl_motion, self.tmpl_mask, self.seeds,
-                                      self._codes_of(self.win_codes), 0, True, counter=self.nonfinite)
+                                      self._codes_of(self.win_codes), 0, True, counter=self.nonfinite, _hints=hints)
         ops.stream_commit(self.table, self.win_codes, self.hop, self.code_ring, self.segment, seed, self.seeds, self.status)
         aa, expr, vel = vq._decode_segments(**{f"{p}_index": v for p, v in self._codes_of(self.segment).items()})
         ops.count_nonfinite_multi([aa, expr, vel], self.nonfinite)
@@ -417,7 +602,7 @@ class StreamBatch:
         if self._version_stamp() != self._stamp:
             raise RuntimeError("StreamBatch.step: the models' parameters changed; weights are fixed for the life of a StreamBatch — build a new one")
         rows, staged = self._rows(ready)
-        self._upload(rows, staged)
+        self._upload(rows, staged, *(self._hint_rows(ready) if self.motion_hints else ()))
         if self.graph is not None:
             self.graph.replay()
         else:
@@ -443,12 +628,14 @@ class StreamBatch:
             raise RuntimeError("Session.close: the session is closed")
         if s.fmt is not None:
             self._end(s)                                                    # releases the outputs held back: one more full window may be ready
+        s.hints_ended = True                                                # `end_motion()`: a window that waited for hints is ready now
         if s.ready:
             raise RuntimeError("Session.close: a full window is still pending — call step() first")
         rounds, t = tail_of(s.pushed, self.pre, self.hop)
         assert s.windows == rounds, (s.windows, rounds)                     # rule 1
         result = self._finish(s, rounds, t)
         s.emitted, s.closed = self.hop * rounds + t, True
+        s.hint_frames_unused = max(0, s.hint_frames - s.emitted)            # the offline set would have refused them (rule 5)
         self.sessions[s.slot] = None
         return result
 
@@ -456,9 +643,14 @@ class StreamBatch:
         """The device side of `close()`: the tail window of `t` frames (0: none) behind `rounds` full windows, the last decode, the emit."""
         model, vq, dev, k, pre, hop = self.model, self.vq, self.device, s.slot, self.pre, self.hop
         rows, staged = self._rows([])
-        if staged or any(r and "resample" in r for r in rows):             # PCM pushed since the last tick (or a filter's tail to flush): a push-only launch
-            self._upload(rows, staged)
-            self._launch_push()
+        hint_rows, hint_staged = self._hint_rows([]) if self.motion_hints else (None, 0)
+        push_audio = staged or any(r and "resample" in r for r in rows)    # PCM pushed since the last tick (or a filter's tail to flush)
+        if push_audio or hint_staged:                                      # push-only launches
+            self._upload(rows, staged, hint_rows, hint_staged)
+            if push_audio:
+                self._launch_push()
+            if hint_staged:                                                # hints pushed since the last tick; no slot is ready: the window table is all {0, 0}
+                self._launch_push_hints()
         frames_out = hop * rounds + t
         lo = max(0, hop * rounds - 2 * self.lag) if rounds else 0           # first code of the last decode: R behind the first frame to emit
         length, n_emit, n_p = frames_out - lo, frames_out - s.emitted, len(self.parts)
@@ -480,9 +672,14 @@ class StreamBatch:
                 audio = torch.zeros(1, t * SPF, device=dev)
                 ops.stream_windows(self.ring[k:k + 1], torch.from_numpy(row).to(dev), audio, self.status)
                 tail = torch.zeros(n_p, 1, t, dtype=torch.int64, device=dev)
+                hints = None
+                if s.motion:                                                # the tail's t rows of the slot's ring: contiguous, as every window's
+                    first = k * (self.hint_rows + pre) + (hop * rounds) % self.hint_rows
+                    avail = min(max(s.hint_frames - hop * rounds, 0), t)
+                    hints = (*self._hint_store, torch.tensor([[first, avail]], dtype=torch.int64).to(dev), self.status)
                 with model.collect_health():
                     model._window_step(vq, audio, self.speaker_id[k:k + 1], self.tmpl_motion[:1, :t], self.tmpl_mask[:1, :t], self.seeds[k:k + 1],
-                                       self._codes_of(tail), 0, False, counter=self.nonfinite)
+                                       self._codes_of(tail), 0, False, counter=self.nonfinite, _hints=hints)
                 table, longest = ops.segment_table([(j * t, j * length + hop * rounds - lo, t) for j in range(n_p)], tail.numel(), last.numel(), dev)
                 ops.copy_segments(tail, last, table, 8, longest, self.status)
             aa, expr, vel = vq._decode_segments(**{f"{p}_index": v for p, v in self._codes_of(last).items()})

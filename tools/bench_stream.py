@@ -12,7 +12,11 @@ Wall time per tick around work that ends in a device synchronise (`step()` ends 
 median and the run-to-run spread are reported.  Writes one JSON document to `--out` and prints it.
 `--audio-input RATE:CH:FMT` measures something else: the captured tick of a batch built with `audio_inputs=(that input,)` — raw PCM staged,
 `stream_push_resample` as the first launch — against the captured 16 kHz f32 tick of the same tree, the two interleaved on the same device,
-into profiles/stream_resample_bench.json.  The kernel's own time needs a kernel trace of such a run (`rocprofv3 --kernel-trace --stats`)."""
+into profiles/stream_resample_bench.json.  The kernel's own time needs a kernel trace of such a run (`rocprofv3 --kernel-trace --stats`).
+`--hints` measures a third thing: the captured tick of a batch built with `motion_hints=True` whose every session is hinted (upper body kept,
+60 hint frames staged per slot and tick: `stream_push_hints`, `pack_motion_hints`) against the captured tick without hints, interleaved, with
+the staged bytes per tick, into profiles/stream_hints_bench.json.  The difference holds host staging and the launch alike; their split needs
+a kernel trace taken in a run of its own."""
 import argparse
 import json
 import os
@@ -135,6 +139,70 @@ def resample_arm(args, inp):
     return result
 
 
+class LiveHinted(Live):
+    """`Live` in a batch built with motion_hints=True: every session is hinted — the upper body kept from a 'capture' — and pushes the 60 hint
+    frames of its next window with the window's audio, every tick."""
+
+    def __init__(self, sb, base):
+        from pantomatrix_amd.recordings import identity_seed, part_columns
+        self.sb, self.waves = sb, [base[1009 * k:] for k in range(sb.slots)]
+        g = np.random.default_rng(0)
+        self.motion = identity_seed(1, 64)[0].numpy() + (0.05 * g.standard_normal((64, 337))).astype(np.float32)
+        self.mask = np.ones((64, 337), np.uint8)
+        self.mask[:, part_columns("upper")] = 0
+        self.sessions = [sb.open(motion=True) for _ in range(sb.slots)]
+        self.tick(first=True)
+
+    def tick(self, first=False):
+        from pantomatrix_amd import streaming
+        n = 64 if first else 60
+        for s, w in zip(self.sessions, self.waves):
+            s.push(w[s.pushed:streaming.window_need(s.windows)])
+            s.push_motion(self.motion[:n], self.mask[:n])
+        out = self.sb.step()
+        assert len(out) == self.sb.slots and (first or all(e.poses.shape[0] == 60 for e in out.values()))
+
+
+def hints_arm(args):
+    """`--hints`: the captured tick of a batch whose every slot is hinted (upper body kept, 60 hint frames pushed per slot and tick) against
+    the captured tick of a batch without motion hints, same tree, the two interleaved on the same device."""
+    from pantomatrix_amd import streaming, synthetic
+    from tools import workloads
+    model, vq = workloads.product_models(precision=args.precision, device="cuda")
+    ticks = 2 + args.runs * (args.steps + 1)
+    seconds = (ticks + 2) * HOP_SAMPLES // 16000 + 4
+    base = synthetic.synthetic_audio(1, seconds * 16000 + 1009 * max(args.slots))[0].numpy()
+    result = {"what": "one captured tick of StreamBatch, every slot live: every session hinted (motion_hints=True; upper body kept, 60 hint frames "
+                      "staged per slot and tick, stream_push_hints + pack_motion_hints) vs a batch without motion hints; same tree, arms interleaved",
+              "commit": args.commit,
+              "config": {"precision": args.precision, "ticks_per_run": args.steps, "runs": args.runs, "samples_per_slot_and_tick": HOP_SAMPLES,
+                         "hint_frames_per_slot_and_tick": 60}, "slots": {}}
+    for n in args.slots:
+        live = {"plain": Live(streaming.StreamBatch(model, vq, slots=n, max_seconds=seconds, use_graph=True), base),
+                "hinted": LiveHinted(streaming.StreamBatch(model, vq, slots=n, max_seconds=seconds, use_graph=True, motion_hints=True), base)}
+        ms = {k: [] for k in live}
+        for _ in range(args.runs):
+            for name, l in live.items():
+                l.tick()
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for _ in range(args.steps):
+                    l.tick()
+                torch.cuda.synchronize()
+                ms[name].append(1e3 * (time.perf_counter() - t0) / args.steps)
+        med = {k: float(np.median(v)) for k, v in ms.items()}
+        sb = live["hinted"].sb
+        result["slots"][str(n)] = {"tick_ms": {k: summary(v) for k, v in ms.items()}, "hinted_minus_plain_ms": round(med["hinted"] - med["plain"], 3),
+                                   "hinted_over_plain": round(med["hinted"] / med["plain"], 3), "staged_hint_bytes_per_tick": sb.hint_bytes_staged,
+                                   "hint_ring_rows": sb.hint_rows, "hint_ring_bytes_per_slot": (sb.hint_rows + 4) * 344 * 5}
+        for l in live.values():
+            for s in l.sessions:
+                s._staged, s._hint_staged, s.closed = [], [], True           # dropped, not closed: the tail of a benchmark session is nobody's output
+        del live, sb
+        torch.cuda.empty_cache()
+    return result
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--slots", type=int, nargs="+", default=[1, 8, 32, 64])
@@ -145,8 +213,19 @@ def main():
     ap.add_argument("--commit", default=None, help="recorded in the document (the measured tree is not always a git checkout)")
     ap.add_argument("--audio-input", default=None, metavar="RATE:CH:FMT", help="measure the resampling tick for this input (e.g. 44100:2:s16) "
                     "against the 16 kHz f32 tick instead of the three arms above")
+    ap.add_argument("--hints", action="store_true", help="measure the tick of a batch whose every session pushes motion hints against the tick "
+                    "without hints instead of the three arms above (profiles/stream_hints_bench.json)")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "bench_stream needs an MI355X: none of its figures means anything on a CPU"
+    if args.hints:
+        result = hints_arm(args)
+        result["peak_memory_gb"] = round(torch.cuda.max_memory_allocated() / 2 ** 30, 2)
+        out = args.out or os.path.join(ROOT, "profiles", "stream_hints_bench.json")
+        with open(out, "w") as f:
+            json.dump(result, f, indent=1)
+            f.write("\n")
+        print(json.dumps(result))
+        return
     if args.audio_input:
         from pantomatrix_amd.audio import AudioInput
         rate, ch, fmt = args.audio_input.split(":")
